@@ -4,6 +4,21 @@
     python bench.py --gpus N --steps K --warmup W            (N > 1: starts its own N ranks, one per GPU -- launch_ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W                (the same ranks under an external launcher)
+    python bench.py ... --full                                (everything else this script measures, see below)
+    python bench.py ... --dump-outputs DIR                    (the last timed step's outputs as DIR/<name>.npy)
+
+Plain run vs --full.  A plain run does only what the headline figure needs: set-up, W warm-up steps, ONE block of exactly K timed
+steps, the outputs if --dump-outputs is given, the result line.  --full adds what the line carried before the split: 3 timed
+blocks per row (median reported, throttled blocks replaced), the public-API loop (`api_ms_per_step`), the secondary configurations
+(`also`), the CPU baseline, the live rocprofv3 counter passes behind `roofline`, and for N > 1 `no_gather` and the exchange sweep.
+The options --also, --cpu-baseline, --pmc and --blocks default to their --full values with --full and to off / 1 without it; given
+explicitly they hold either way.
+
+--dump-outputs DIR: after the timed steps, what the timed path handed its caller on its last step -- obs [N,12], reward, terminated,
+truncated, status and final_obs [N,12] of HipBackend.step (N > 1: rank 0 writes the gathered global obs, reward, terminated,
+truncated) -- as float32 DIR/<name>.npy, written before anything else steps the env.  Inputs are seeded: the same arguments give
+the same inputs in every run (no block is replaced when outputs are dumped).  Above 60 MB in all, every array is cut to the same
+seeded sample of env rows, whose indices go to DIR/sample_index.npy (float64).
 
 A "step" is one env.step() of every environment of the batch: one launch of the fused step kernel per GPU (action
 clamp -> LLGS integration over the pulse -> energy -> observation -> reward -> termination), and for N > 1 the single
@@ -21,20 +36,20 @@ device-physics torque terms, and with one parameter record per env; cfg2a; the a
 here is compared with the oracle at the same size in tests/test_gpu_fullsize.py.
 
 What is timed.  `value` / `ms_per_step`: host wall time of a block of exactly --steps calls of the C-ABI step
-(HipBackend.step -> stg_step_many) between synchronizes (+ barriers for N > 1), max over ranks; --blocks (3) such blocks
-are timed and the MEDIAN one is reported -- where the dispatcher places the wavefronts differs from launch to launch by a
-few per cent, one block cannot tell a regression from placement luck.  `api_ms_per_step`: the
+(HipBackend.step -> stg_step_many) between synchronizes (+ barriers for N > 1), max over ranks; --blocks such blocks (1 in a
+plain run, 3 with --full) are timed and the MEDIAN one is reported -- where the dispatcher places the wavefronts differs from
+launch to launch by a few per cent, one block cannot tell a regression from placement luck.  `api_ms_per_step` (--full): the
 same steps through the public SpinTorqueVecEnv.step() with Gym-convention [N, 2] actions (headline and cfg2).
 Timing hygiene (profiles/r03_stall_root_cause.txt): the GPU boxes show 256 CPUs but the container's CFS quota is 16; torch's
 default pool of 128 host threads made the container get THROTTLED for up to 100 ms right after a row's set-up -- the
 "sporadic ~80 ms stall" of rounds 1-2.  The pool is capped (cap_host_threads), the collector is off inside a block, events
-exist before the block, and a block is discarded and replaced (at most twice) ONLY if cgroup cpu.stat reports a throttling
-event during it -- never on the measured times.  Every block's wall time is printed: `block_walls_ms`, `block_throttled`,
+exist before the block, and (--full) a block is discarded and replaced (at most twice) ONLY if cgroup cpu.stat reports a
+throttling event during it -- never on the measured times.  Every block's wall time is printed: `block_walls_ms`, `block_throttled`,
 `block_used`, `blocks_timed` are the LAST keys of the line.
 
-Output: ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+Output: ONE JSON line on rank 0 with `roofline` and `cpu_baseline` (null in a plain run).
 
-roofline.  The binding roof of a full env-step is fp64 VALU, not HBM.  `achieved` is
+roofline (live counters with --full only).  The binding roof of a full env-step is fp64 VALU, not HBM.  `achieved` is
 the EXECUTED fp64 rate -- 64 lanes x (2 SQ_INSTS_VALU_FMA_F64 + _MUL_F64 + _ADD_F64) per launch, from the hardware
 counters, over the kernel's HIP-event time -- so `frac` <= 1 by construction; `valu_issue_frac` is the share of the
 SIMDs' VALU issue slots the launch used; the reference formulation's flop count (305 per RK4 sub-step, 745
@@ -106,8 +121,13 @@ def parse_args():
     ap.add_argument("--envs-per-gpu", type=int, default=65536)
     ap.add_argument("--solver", default="rk45", choices=["rk4", "rk45", "euler"])
     ap.add_argument("--thermal", type=int, default=1)
-    ap.add_argument("--also", type=int, default=1, help="run the secondary configurations too (N=1 only)")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything, not just the headline: 3 blocks per row, the public-API loop, the secondary "
+                         "configurations, the CPU baseline, the live counter passes, for N > 1 no_gather and the exchange sweep")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as float32 DIR/<name>.npy (under 64 MB in all)")
+    ap.add_argument("--also", type=int, default=None, help="run the secondary configurations too (N=1 only; default: 1 with --full, else 0)")
+    ap.add_argument("--cpu-baseline", type=int, default=None, help="time the CPU oracle too (default: 1 with --full, else 0)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--lane-sort", default="auto", choices=["auto", "on", "off"],
                     help="duration-sorted lane schedule (auto = on)")
@@ -119,14 +139,24 @@ def parse_args():
                     help="N > 1: RCCL all-gather (default) or the one-shot point-to-point exchange")
     ap.add_argument("--sweep-timeout", type=float, default=120.0,
                     help="N > 1: seconds the exchange sweep (all_gather / in-place / p2p by themselves) may take before it is abandoned")
-    ap.add_argument("--pmc", default="auto", choices=["auto", "off"],
-                    help="auto: collect the hardware counters live with rocprofv3 child passes (N = 1 only)")
+    ap.add_argument("--pmc", default=None, choices=["auto", "off"],
+                    help="auto: collect the hardware counters live with rocprofv3 child passes (default: auto with --full, else off)")
     ap.add_argument("--pmc-dump", default=None, help="write the per-row counter table (JSON) here as well")
     ap.add_argument("--pmc-child", default=None, help=argparse.SUPPRESS)     # internal: run the rows once, write a manifest
-    ap.add_argument("--blocks", type=int, default=3, help="timed blocks of --steps steps per row; the MEDIAN block is reported")
+    ap.add_argument("--blocks", type=int, default=None, help="timed blocks of --steps steps per row; the MEDIAN block is reported "
+                    "(default: 3 with --full, else 1)")
     ap.add_argument("--master-port", type=int, default=0, help="--gpus N > 1 without a launcher: rendezvous port of the ranks this "
                     "command starts itself (0 = pick a free one)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.also is None:
+        args.also = int(args.full)
+    if args.cpu_baseline is None:
+        args.cpu_baseline = int(args.full)
+    if args.pmc is None:
+        args.pmc = "auto" if args.full else "off"
+    if args.blocks is None:
+        args.blocks = 3 if args.full else 1
+    return args
 
 
 def library_sha256():
@@ -233,9 +263,11 @@ class BlockTimer:
         a block during which the container was throttled is DISCARDED and replaced (twice at most; if every block was throttled
         all are kept) -- the throttle counter decides what is discarded, the measured times never decide what is selected: the
         reported block is the median of the kept ones by wall time (max over ranks).  `pre` runs before every block and `post(b)`
-        after it, both outside the timed region (resetting / reading the on-device work counters).  retime=False: one block."""
+        after it, both outside the timed region (resetting / reading the on-device work counters).  retime=False: exactly one
+        block; REPLACE_THROTTLED = False: exactly `nblocks`, none replaced."""
         import torch.distributed as dist
         want = 1 if not retime else max(1, int(nblocks if nblocks is not None else DEFAULT_BLOCKS))
+        spare = 2 if retime and REPLACE_THROTTLED else 0
         blocks = []
         while True:
             if pre is not None:
@@ -255,7 +287,7 @@ class BlockTimer:
                     tag, len(blocks), b["wall_s"] * 1e3, b["device_span_s"] * 1e3, sum(b["kernel_ms"]), b["throttled"], b["throttled_usec"]),
                     file=sys.stderr, flush=True)
             clean = [x for x in blocks if not x["discard"]]
-            if len(clean) >= want or len(blocks) >= want + 2:
+            if len(clean) >= want or len(blocks) >= want + spare:
                 break
         kept = clean if clean else blocks
         med = sorted(kept, key=lambda x: x["wall_max_s"])[(len(kept) - 1) // 2]
@@ -265,6 +297,7 @@ class BlockTimer:
 
 
 DEFAULT_BLOCKS = 3
+REPLACE_THROTTLED = True          # main(): only with --full (a plain run times exactly --steps steps) and never with --dump-outputs
 
 
 def block_report(blocks):
@@ -329,11 +362,43 @@ def mixed_kwargs(solver, n_global, per_env=False):
     return kw, cls
 
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6      # (under 64 MB with the .npy headers, in either sense of MB)
+
+
+def step_outputs(backend, global_views=None):
+    """Host float32 copies of what the last step handed its caller, env-major ([N, ...]): HipBackend.step's obs / reward /
+    terminated / truncated / status and the auto-reset's final_obs; for N > 1 the gathered global (obs, reward, terminated,
+    truncated) views instead."""
+    if global_views is not None:
+        names, ts = ("obs", "reward", "terminated", "truncated"), global_views
+    else:
+        names = ("obs", "reward", "terminated", "truncated", "status", "final_obs")
+        ts = (backend.obs.t(), backend.reward, backend.terminated, backend.truncated, backend.status,
+              None if backend.final_obs is None else backend.final_obs.t())
+    return {k: t.to(torch.float32).cpu().numpy() for k, t in zip(names, ts) if t is not None}
+
+
+def write_outputs(out_dir, arrays, seed=0):
+    """arrays {name: float32 [N, ...]} -> out_dir/<name>.npy; above DUMP_LIMIT_BYTES in all, the same seeded sample of rows from
+    every array, its row indices in out_dir/sample_index.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a[0].nbytes for a in arrays.values())
+    if row_bytes * n > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(seed).choice(n, DUMP_LIMIT_BYTES // (row_bytes + 8), replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        np.save(os.path.join(out_dir, "sample_index.npy"), idx.astype(np.float64))
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def run_config(n_local, solver, thermal, steps, warmup, rank, world, device_index, mixed=False, seed=1234, lane_sort=None,
                torque_model="reference", wave_spec=None, gather_algo="all_gather", retime=True, per_env=False, api=False,
-               inplace=False, extras=True):
+               inplace=False, extras=True, dump=False):
     """Builds the env, runs warmup + timed steps, returns a dict of measurements (times are this rank's).
-    The env is the product default: diagnostics off (a step writes the RL-facing outputs only), records layout."""
+    The env is the product default: diagnostics off (a step writes the RL-facing outputs only), records layout.
+    extras (N > 1): also time the loop without the gather and the gather by itself.  dump: the measurements carry `outputs`,
+    what the last timed step handed its caller (host copies, taken before anything else steps the env)."""
     import spin_torque_gym_amd as stg
     import torch.distributed as dist
     kw = dict(include_thermal_fluctuations=bool(thermal), temperature=300.0, solver=solver, seed=seed, autoreset=True,
@@ -374,9 +439,11 @@ def run_config(n_local, solver, thermal, steps, warmup, rank, world, device_inde
                 env.gather_end()                                     # step k-1's gather ran under step k's kernel
             env.gather_begin()                                       # the single collective of a step, on its own stream
 
+    views = [None]
+
     def drain():
         if world > 1 and env.gather_in_flight:
-            env.gather_end()                                         # (typed global views: obs [N,12], reward, flags)
+            views[0] = env.gather_end()                              # (typed global views: obs [N,12], reward, flags)
 
     for k in range(warmup):
         one_step(k)
@@ -396,10 +463,12 @@ def run_config(n_local, solver, thermal, steps, warmup, rank, world, device_inde
                kernel_ms_min=float(np.min(last["kernel_ms"])), env_steps=c["env_steps"], work_units=c["work_units"],
                noop_steps=c["noop_steps"], launches=steps, warmup=warmup, **block_report(blocks))
     out.update(gather_only_ms=None, wall_no_gather_s=None, api_ms_per_step=None, lane_sort=lane_sort)
+    if dump:
+        out["outputs"] = step_outputs(backend, views[0] if world > 1 else None)
     if world > 1 and extras:
         # SURVEY 8e "report both": a learner that is data-parallel over the same ranks needs no gather at all
         out["wall_no_gather_s"] = timer.timed(lambda k: one_step(warmup + k, gather=False), None, retime, tag + " no-gather")[0]["wall_max_s"]
-    if world > 1:
+    if world > 1 and extras:
         out["gather_only_ms"] = gather_only(env, acts[warmup], steps, dev)
     if api and world == 1:
         # the public API: SpinTorqueVecEnv.step() with Gym-convention [N, 2] actions (host-side views, the transposition of
@@ -548,11 +617,12 @@ def row_specs(args):
     return rows
 
 
-def run_row(spec, rank, world, local_rank, retime=True, gather_algo="all_gather", api=True):
+def run_row(spec, rank, world, local_rank, retime=True, gather_algo="all_gather", api=True, extras=True, dump=False):
     if spec["kind"] == "step":
         m = run_config(spec["n"], spec["solver"], spec["thermal"], spec["steps"], spec["warmup"], rank, world, local_rank,
                        mixed=spec["mixed"], torque_model=spec["tm"], lane_sort=spec["lane_sort"], wave_spec=spec["wave_spec"],
-                       gather_algo=gather_algo, retime=retime, per_env=spec["per_env"], api=api and spec["api"])
+                       gather_algo=gather_algo, retime=retime, per_env=spec["per_env"], api=api and spec["api"], extras=extras,
+                       dump=dump)
         m["kind"] = "step"
         return m
     if spec["kind"] == "short":
@@ -682,7 +752,7 @@ def pmc_for_run(args, argv, world=1):
                                "units": "mean per timed launch; FETCH_SIZE / WRITE_SIZE in KB (uncorrected)", "rows": tab}, f, indent=1)
             return tab, note
     else:
-        note = "--pmc off"
+        note = "--pmc off" if args.full else "no live counter passes (they run with --full)"
     try:
         committed = json.load(open(PMC_TABLE))
     except (OSError, ValueError):
@@ -944,8 +1014,10 @@ def launch_ranks(args):
 
 def main():
     args = parse_args()
-    global DEFAULT_BLOCKS
+    global DEFAULT_BLOCKS, REPLACE_THROTTLED
     DEFAULT_BLOCKS = max(1, args.blocks)
+    # a plain run times exactly --blocks x --steps steps; a dump must see the same state from run to run whatever the throttle counter says
+    REPLACE_THROTTLED = args.full and not args.dump_outputs
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -993,7 +1065,10 @@ def main():
     n_local = args.envs_per_gpu
     specs = row_specs(args)
     row = lambda key: (pmc_tab or {}).get(key)
-    meas = run_row(specs[0][1], rank, world, local_rank, gather_algo=args.gather_algo)
+    meas = run_row(specs[0][1], rank, world, local_rank, gather_algo=args.gather_algo, api=args.full, extras=args.full,
+                   dump=bool(args.dump_outputs) and rank == 0)
+    if "outputs" in meas:
+        write_outputs(args.dump_outputs, meas.pop("outputs"))
     wall = torch.tensor([meas["wall_s"]], dtype=torch.float64, device=torch.device("cuda", local_rank))
     if world > 1:
         dist.all_reduce(wall, op=dist.ReduceOp.MAX)
@@ -1015,17 +1090,20 @@ def main():
                                    f"(obs [N,12], reward, terminated, truncated) -- no copies") if world > 1 else "single GPU"},
         "host": host,
         "timing": {"value_is": f"C-ABI step (HipBackend.step -> stg_step_many): host wall time of a block of exactly `steps` steps between "
-                               f"synchronizes (+ barriers, max over ranks); {DEFAULT_BLOCKS} such blocks are timed and the MEDIAN one is "
-                               f"reported (block_walls_ms lists all, block_used which)",
-                   "api_ms_per_step_is": "the same steps through the public SpinTorqueVecEnv.step() with [N,2] actions",
+                               f"synchronizes (+ barriers, max over ranks); " + (f"{DEFAULT_BLOCKS} such blocks are timed and the MEDIAN one is "
+                               f"reported (block_walls_ms lists all, block_used which)" if DEFAULT_BLOCKS > 1 else "one such block is timed"),
+                   "api_ms_per_step_is": "the same steps through the public SpinTorqueVecEnv.step() with [N,2] actions" if args.full else
+                                         "not measured (--full)",
                    "retime_rule": "a block is DISCARDED and replaced (at most twice) only if the container's cgroup cpu.stat shows "
                                   "nr_throttled increasing during it (CFS bandwidth throttling of the whole container); the measured "
-                                  "times never decide what is kept",
+                                  "times never decide what is kept" if REPLACE_THROTTLED else
+                                  "no block is replaced (block_throttled shows whether the container was throttled during one)",
                    "gc": "Python collector disabled inside a timed block"},
         "roofline": roofline_step(meas, n_local, args.solver, False, row("headline"), pmc_src),
     }
     if world > 1:
         out["ranks"] = ranks
+    if world > 1 and args.full:
         wng = torch.tensor([meas["wall_no_gather_s"]], dtype=torch.float64, device=torch.device("cuda", local_rank))
         dist.all_reduce(wng, op=dist.ReduceOp.MAX)
         out["no_gather"] = {"value": round(n_total * args.steps / float(wng.item()), 1), "unit": "env-steps/s",
@@ -1036,6 +1114,7 @@ def main():
         out["gather_only"] = {"ms": round(float(gm.item()), 4), "bytes_per_rank": 56 * n_local, "algo": args.gather_algo,
                               "note": "the exchange by itself, back to back with nothing to hide under (max over ranks); in the "
                                       "timed loop it runs on its own stream under the next step's kernel"}
+    if world > 1:
         # CPU baseline beside the N > 1 number too: rank 0 times the oracle on the host cores AFTER the timed region while the other
         # ranks sleep on a key of the rendezvous store (no collective is pending meanwhile, nobody spins on a GPU queue)
         out["cpu_baseline"] = None
@@ -1056,6 +1135,7 @@ def main():
                 except Exception:   # noqa: BLE001
                     pass
             dist.barrier()
+    if world > 1 and args.full:
         if rank == 0:
             # the in-place all-gather and the point-to-point exchange below have never run over RCCL with N > 1 (one-GPU build
             # boxes): a safety copy of the measured line goes to stderr first, in case one of them does not come back

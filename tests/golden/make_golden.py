@@ -629,7 +629,21 @@ def G18():
     save("G18_stable_states", **out)
 
 
-ALL = dict(G18=G18, G17=G17, G16=G16, G15=G15, G14=G14, G1=G1, G2=G2, G3=G3, G4=G4, G5=G5, G6=G6, G7=G7, G8=G8, G9=G9, G10=G10, G11=G11, G12=G12, G13=G13)
+def G19():
+    """the package's final Gym registrations (spin_torque_gym/__init__.py:14-24 overridden by envs/__init__.py:14-26): id,
+    entry point, max_episode_steps and kwargs (as JSON) of every registered env."""
+    import json
+    import spin_torque_gym.envs  # noqa: F401  (both modules register; the second one wins, SURVEY H10)
+    reg = sys.modules["gymnasium.envs.registration"].registry
+    ids = sorted(reg)
+    print("    G19 registered ids:", ids)
+    save("G19_registrations", ids=np.array(ids), entry_point=np.array([reg[k]["entry_point"] for k in ids]),
+         max_episode_steps=np.array([reg[k]["max_episode_steps"] for k in ids]),
+         kwargs_json=np.array([json.dumps(reg[k]["kwargs"], sort_keys=True) for k in ids]))
+
+
+ALL = dict(G18=G18, G17=G17, G16=G16, G15=G15, G14=G14, G1=G1, G2=G2, G3=G3, G4=G4, G5=G5, G6=G6, G7=G7, G8=G8, G9=G9, G10=G10, G11=G11, G12=G12, G13=G13,
+           G19=G19)
 
 if __name__ == "__main__":
     which = sys.argv[1:] or list(ALL)

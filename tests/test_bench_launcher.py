@@ -49,3 +49,27 @@ def test_traffic_from_counters_prices_scattered_and_coalesced_reads():
     assert bench.traffic_bytes(c, 0) == (1000 + 3000) * 1024                         # every read a scattered record
     assert bench.traffic_bytes(c, 200 * 1024) == (1000 + 100 + 3000) * 1024          # + half the coalesced streams' bytes
     assert bench.traffic_bytes(c, 10 ** 12) == bench.traffic_bytes(c)                # never more than all reads doubled
+
+
+def test_dump_writes_float32_arrays_and_a_seeded_sample_above_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: every array as float32 <name>.npy; above the size limit the same seeded rows of every array, their indices in
+    sample_index.npy (float64), the same sample in every run."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(0)
+    arrays = {"obs": rng.normal(size=(1000, 12)).astype(np.float32), "terminated": (rng.random(1000) < 0.5).astype(np.float32)}
+    bench.write_outputs(str(tmp_path / "all"), arrays)
+    assert sorted(os.listdir(tmp_path / "all")) == ["obs.npy", "terminated.npy"]
+    for k, a in arrays.items():
+        got = np.load(tmp_path / "all" / (k + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, a)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 20000)
+    for d in ("s1", "s2"):
+        bench.write_outputs(str(tmp_path / d), arrays)
+    idx = np.load(tmp_path / "s1" / "sample_index.npy")
+    assert idx.dtype == np.float64 and np.array_equal(idx, np.load(tmp_path / "s2" / "sample_index.npy"))
+    assert 0 < len(idx) < 1000 and np.all(np.diff(idx) > 0)
+    assert sum(np.load(tmp_path / "s1" / f).nbytes for f in os.listdir(tmp_path / "s1")) <= 20000
+    for k, a in arrays.items():
+        assert np.array_equal(np.load(tmp_path / "s1" / (k + ".npy")), a[idx.astype(np.int64)])

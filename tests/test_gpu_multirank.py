@@ -177,10 +177,10 @@ def test_two_hip_ranks_sharded_env_equals_single_process_and_oracle():
 
 @pytest.mark.timeout(1200)
 def test_bench_py_gpus_2_launches_its_own_ranks():
-    """`python3 bench.py --gpus 2 ...` with NO launcher around it starts its two ranks itself (before any GPU
-    call), prints ONE JSON line with n_gpus 2, both ranks seen, `cpu_baseline` and a non-null `roofline.frac`, and exits 0."""
+    """`python3 bench.py --gpus 2 ... --full` with NO launcher around it starts its two ranks itself (before any
+    GPU call), prints ONE JSON line with n_gpus 2, both ranks seen, `cpu_baseline` and a non-null `roofline.frac`, and exits 0."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "4", "--warmup", "1",
-           "--envs-per-gpu", "16384"]
+           "--envs-per-gpu", "16384", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1100)
     assert r.returncode == 0, (r.returncode, r.stderr[-3000:])

@@ -472,19 +472,17 @@ o, info = arr.reset(seed=1)
 o2, r, te, tr, info = arr.step(np.array([3, 0.0, 1e-10], dtype=np.float32))
 assert np.asarray(o2).shape == np.asarray(o).shape and isinstance(r, float)
 arr.close()
-# where the reference is present (the build container): its own final registrations, from the unmodified package
-if os.path.isdir("/root/reference/spin_torque_gym"):
-    for k in [k for k in reg if k.startswith(("SpinTorque", "Skyrmion"))]:
-        del reg[k]
-    sys.path.insert(0, "/root/reference")
-    import logging, warnings
-    warnings.simplefilter("ignore"); logging.disable(logging.CRITICAL)
-    import spin_torque_gym, spin_torque_gym.envs    # noqa: F401  (both modules register; the second one wins)
-    for k, mine in ours.items():
-        ref = reg[k]
-        assert ref["max_episode_steps"] == mine["max_episode_steps"] and ref["kwargs"] == mine["kwargs"], (k, ref, mine)
-        assert ref["entry_point"].split(":")[1] == mine["entry_point"].split(":")[1]
-    print("reference registrations checked")
+# the unmodified reference's own final registrations, recorded by tests/golden/make_golden.py (G19)
+import json
+g = np.load(os.path.join(root, "tests", "golden", "G19_registrations.npz"), allow_pickle=False)
+refreg = {str(k): dict(entry_point=str(e), max_episode_steps=int(s), kwargs=json.loads(str(kw)))
+          for k, e, s, kw in zip(g["ids"], g["entry_point"], g["max_episode_steps"], g["kwargs_json"])}
+for k, mine in ours.items():
+    ref = refreg[k]
+    assert ref["max_episode_steps"] == mine["max_episode_steps"], (k, ref, mine)
+    assert ref["kwargs"] == json.loads(json.dumps(mine["kwargs"], sort_keys=True)), (k, ref, mine)
+    assert ref["entry_point"].split(":")[1] == mine["entry_point"].split(":")[1]
+print("reference registrations checked")
 print("ok")
 """
 
@@ -494,7 +492,7 @@ def test_gym_make_drop_in_registrations(oracle_mod):
     `import spin_torque_gym_amd` registers 'SpinTorque-v0' and 'SpinTorqueArray-v0' with the reference's final
     max_episode_steps / kwargs (spin_torque_gym/__init__.py:14-24 overridden by envs/__init__.py:14-26: 100 / 200), the entry
     points resolve to the facade classes, and `gymnasium.make(id, **kwargs)` builds working envs (stepped here on the oracle
-    backend).  In the build container the unmodified reference's own registry is compared as well.  Runs in a fresh
+    backend).  The unmodified reference's own registry, recorded as G19, is compared as well.  Runs in a fresh
     interpreter so that the stand-in `gymnasium` does not leak into the other tests' modules."""
     import os
     import subprocess

@@ -5,10 +5,10 @@ set -u
 tag=${1:-rXX}
 out=gpurun_out/$tag; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --cpu-baseline 0 > $out/bench_under_rocprof.json 2> $out/stats.err || echo "stats run failed"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --full --cpu-baseline 0 > $out/bench_under_rocprof.json 2> $out/stats.err || echo "stats run failed"
 bash tools/pmc_passes.sh $out/pmc --steps 3 --warmup 1 > $out/pmc.log 2>&1
 python3 tools/pmc_summary.py $out/pmc > $out/pmc_summary.txt 2>&1
-timeout -k 10 400 python3 bench.py > $out/bench.json 2> $out/bench.err || echo "bench failed"
+timeout -k 10 400 python3 bench.py --full > $out/bench.json 2> $out/bench.err || echo "bench failed"
 {
   echo "== tools/probes/clock_vs_load (shader clock and fp64 FMA issue vs number of wavefronts)"
   timeout -k 10 60 tools/probes/clock_vs_load

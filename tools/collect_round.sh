@@ -13,12 +13,12 @@ if [ "${2:-}" = "tests" ]; then
   timeout -k 10 1100 python3 -m pytest tests -m gpu -x -q --durations=15 > $out/pytest_gpu.log 2>&1 || { echo "GPU TESTS FAILED"; tail -30 $out/pytest_gpu.log; exit 1; }
   tail -3 $out/pytest_gpu.log
 fi
-timeout -k 10 600 python3 bench.py --steps 20 --warmup 2 --pmc-dump $out/pmc_rows.json > $out/bench.json 2> $out/bench.err || { echo "bench failed"; tail -20 $out/bench.err; }
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --steps 20 --warmup 2 --cpu-baseline 0 --pmc off > $out/bench_under_rocprof.json 2> $out/stats.err || echo "stats run failed"
+timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 2 --pmc-dump $out/pmc_rows.json > $out/bench.json 2> $out/bench.err || { echo "bench failed"; tail -20 $out/bench.err; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --full --steps 20 --warmup 2 --cpu-baseline 0 --pmc off > $out/bench_under_rocprof.json 2> $out/stats.err || echo "stats run failed"
 cp $out/stats/*/*kernel_stats.csv $out/kernel_stats.csv 2>/dev/null
 # (bench.py starts its own two ranks -- no launcher; the same command under torch.distributed.run is what the driver uses for N > 1)
-timeout -k 10 600 python3 bench.py --gpus 2 --backend gloo --steps 4 --warmup 1 --envs-per-gpu 16384 > $out/bench_2rank_gloo.json 2> $out/bench_2rank.err || { echo "2-rank rehearsal failed"; tail -20 $out/bench_2rank.err; }
-timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --backend gloo --steps 4 --warmup 1 --envs-per-gpu 16384 > $out/bench_2rank_gloo_torchrun.json 2> $out/bench_2rank_torchrun.err || { echo "2-rank rehearsal under torch.distributed.run failed"; tail -20 $out/bench_2rank_torchrun.err; }
+timeout -k 10 600 python3 bench.py --full --gpus 2 --backend gloo --steps 4 --warmup 1 --envs-per-gpu 16384 > $out/bench_2rank_gloo.json 2> $out/bench_2rank.err || { echo "2-rank rehearsal failed"; tail -20 $out/bench_2rank.err; }
+timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --backend gloo --steps 4 --warmup 1 --envs-per-gpu 16384 > $out/bench_2rank_gloo_torchrun.json 2> $out/bench_2rank_torchrun.err || { echo "2-rank rehearsal under torch.distributed.run failed"; tail -20 $out/bench_2rank_torchrun.err; }
 timeout -k 10 200 python3 -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.txt 2>&1 || echo "smoke failed"
 tail -1 $out/smoke.txt
 python3 - "$out" <<'PY'

@@ -7,7 +7,7 @@ for rep in $(seq $reps); do
   for cfg in "rk45 36864" "rk45 45000" "rk45 50000" "rk45 60000" "rk45 65536" "rk4 50000" "rk4 60000" "euler 60000"; do
    set -- $cfg
    if [ $mode = old ]; then export STG_SNAKE=0; else unset STG_SNAKE; fi
-   python3 bench.py --steps 8 --warmup 2 --cpu-baseline 0 --also 0 --pmc off --solver $1 --thermal 1 --envs-per-gpu $2 2>/dev/null | python3 -c "
+   python3 bench.py --full --steps 8 --warmup 2 --cpu-baseline 0 --also 0 --pmc off --solver $1 --thermal 1 --envs-per-gpu $2 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print('$mode $1 n=$2 thermal: kernel %.4f ms' % d['roofline']['kernel_ms_avg'])"
   done

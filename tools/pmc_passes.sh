@@ -11,6 +11,6 @@ for pass in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES 
             "FETCH_SIZE" "WRITE_SIZE" \
             "GRBM_GUI_ACTIVE SQ_INSTS_VALU_TRANS SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_THREAD_CYCLES_VALU"; do
   i=$((i+1))
-  timeout -k 10 240 rocprofv3 --kernel-trace --pmc $pass --output-format csv -d "$out/pass$i" -- python3 bench.py --cpu-baseline 0 --also 0 "$@" > "$out/pass$i.json" 2> "$out/pass$i.err" || echo "pass $i ($pass) failed: $(tail -2 $out/pass$i.err)"
+  timeout -k 10 240 rocprofv3 --kernel-trace --pmc $pass --output-format csv -d "$out/pass$i" -- python3 bench.py --full --cpu-baseline 0 --also 0 "$@" > "$out/pass$i.json" 2> "$out/pass$i.err" || echo "pass $i ($pass) failed: $(tail -2 $out/pass$i.err)"
 done
 find "$out" -name "*counter_collection.csv" | head

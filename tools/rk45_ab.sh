@@ -5,7 +5,7 @@ for rep in $(seq $reps); do
 for lib in $LIBS; do
  for cfg in "65536 1" "4096 0" "262144 1"; do
   set -- $cfg
-  STG_HIP_LIBRARY=$PWD/$lib python3 bench.py --steps 8 --warmup 2 --cpu-baseline 0 --also 0 --pmc off --solver rk45 --thermal $2 --envs-per-gpu $1 2>/dev/null | python3 -c "
+  STG_HIP_LIBRARY=$PWD/$lib python3 bench.py --full --steps 8 --warmup 2 --cpu-baseline 0 --also 0 --pmc off --solver rk45 --thermal $2 --envs-per-gpu $1 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print('$(basename $lib) rk45 n=$1 thermal=$2: kernel %.4f ms' % d['roofline']['kernel_ms_avg'])"
  done
