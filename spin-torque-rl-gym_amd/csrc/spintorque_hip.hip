@@ -168,7 +168,7 @@ struct PlanArgs {
     const double* ctab;
     const uint8_t* env_type;  // (per-env parameters: the kind of each env)
     int32_t by_kind;
-    int32_t regroup;          // by_kind: renumber the tile's groups of four blocks longest-first (launches that are resident as a whole)
+    int32_t regroup;          // (with by_kind) kind-pure groups of four blocks, renumbered by estimated cost; 0: kind-major order
     uint32_t* perm;
     void* act_sorted;         // [N][2] in the actions' dtype, slot order: the step kernel reads its action with one coalesced load
                               // instead of two scattered 4-byte reads through the permutation
@@ -215,28 +215,23 @@ __global__ void __launch_bounds__(PLAN_THREADS) stg_plan_tile_kernel(const PlanA
         __syncthreads();
     }
     // Grouped by device kind, the tile's slot sequence is one long-to-short ramp PER KIND, so its 64-slot blocks -- the step launch's
-    // wavefronts, dealt longest rank first -- are not in order of work (the longest block of the last kind has rank ~43).  GROUPS OF
-    // FOUR consecutive blocks (= one 4-wavefront workgroup of the step launch) are therefore renumbered by the pulse duration of their
-    // first env (stable): rank order becomes longest-first again, which is what the step kernel's schedule (stg_slot_block) assumes,
-    // while a workgroup's four wavefronts stay of one kind and of nearly one duration -- they have to finish together for their four
-    // SIMD slots to come free together, and a sub-step of one kind costs up to 1.5x that of another (renumbering single blocks mixed
-    // the kinds inside workgroups: 262 144 envs 0.72 -> 0.96 ms).  Only where it measured faster (tools/devphys_ab.py): launches of
-    // 98 304 ... 131 072 envs with 4-wavefront workgroups, i.e. one and a half to two workgroups per CU, which the boustrophedon order
-    // pairs long with short -- 131 072 envs 0.634 -> 0.508 ms, with the thermal field 1.51 -> 1.28 ms; 100 000 envs 0.623 -> 0.555 ms.
-    // Elsewhere the kind-major order is as good or better: up to 65 536 envs nothing shares a SIMD; at 70 000 envs the few workgroups
-    // of the second round land on the CUs holding the longest ones, which longest-first makes the costliest kind's (0.39 -> 0.60 ms);
-    // with more rounds than fit 262 144 envs 0.72 against 0.82 ms, 1 048 576 envs 2.30 against 2.47; per-env records (64-thread
-    // workgroups) 131 072 envs 0.557 against 0.745 ms.
+    // wavefronts, dealt longest rank first -- are not in order of work (the longest block of the last kind has rank ~43).  With
+    // `regroup`, GROUPS OF FOUR consecutive blocks (= one 4-wavefront workgroup of the step launch) are renumbered longest-first again,
+    // which is what the step kernel's schedule (stg_slot_block) assumes, while a workgroup's four wavefronts stay of one kind and of
+    // nearly one duration -- they have to finish together for their four SIMD slots to come free together, and a sub-step of one
+    // kind costs up to 1.5x that of another (renumbering single blocks mixed the kinds inside workgroups: 262 144 envs 0.72 -> 0.96 ms).
+    // Without it the order stays kind-major: per-env records (then 64-thread workgroups) measured 131 072 envs 0.557 ms kind-major
+    // against 0.745 ms with the rounds 2-3 grouping (groups keyed by their first env).
     __shared__ int grp_d[TILE_WAVES / 4];
     __shared__ uint8_t grp_rank[TILE_WAVES / 4];
-    // Kind-pure groups (regroup >= 2).  A kind's ramp rarely ends on a group boundary (256 slots), so one group per boundary held the
-    // SHORT end of one kind's ramp and the LONG start of the next: a 4-wavefront workgroup whose wavefronts run 150 ... 1000 sub-steps
-    // keeps its CU slot until the longest is through.  Each kind therefore keeps a whole number of groups of its longest envs in
-    // place and hands its remainder (< 256 slots, its SHORTEST envs) to a common tail behind all kinds: every group but the (at most
-    // three) tail groups is of one kind and one duration, and the tail groups are short throughout.
+    // Kind-pure groups.  A kind's ramp rarely ends on a group boundary (256 slots), so one group per boundary held the SHORT end of one
+    // kind's ramp and the LONG start of the next: a 4-wavefront workgroup whose wavefronts run 150 ... 1000 sub-steps keeps its CU
+    // slot until the longest is through.  Each kind therefore keeps a whole number of groups of its longest envs in place and hands
+    // its remainder (< 256 slots, its SHORTEST envs) to a common tail behind all kinds: every group but the (at most three) tail
+    // groups is of one kind and one duration, and the tail groups are short throughout.
     __shared__ uint32_t k_start[3], k_main[3], k_main_off[3], k_tail_off[3];
-    const bool kind_pure = a.by_kind && a.regroup >= 2;
-    if (kind_pure) {
+    const bool regroup = a.by_kind && a.regroup;
+    if (regroup) {
         if (tid == 0) {
             uint32_t main_off = 0, tail_tot = 0, cnt_k[3];
             for (int k = 0; k < 3; ++k) {
@@ -251,14 +246,14 @@ __global__ void __launch_bounds__(PLAN_THREADS) stg_plan_tile_kernel(const PlanA
     }
     auto slot_of = [&](int r) -> uint32_t {
         uint32_t sl = (start[key[r]] - cnt[key[r]]) + rank[r];                                     // exclusive start of the bucket + rank in it
-        if (kind_pure) {
+        if (regroup) {
             const int k = key[r] / PLAN_DUR;
             const uint32_t pos = sl - k_start[k];
             sl = pos < k_main[k] ? k_main_off[k] + pos : k_tail_off[k] + (pos - k_main[k]);
         }
         return sl;
     };
-    if (a.by_kind && a.regroup) {
+    if (regroup) {
         constexpr int NG = TILE_WAVES / 4;
         if (tid < NG) grp_d[tid] = 0x7fffffff;                 // (groups beyond N: last)
         __syncthreads();
@@ -266,15 +261,13 @@ __global__ void __launch_bounds__(PLAN_THREADS) stg_plan_tile_kernel(const PlanA
         for (int r = 0; r < PLAN_ITEMS; ++r)
             if (key[r] >= 0) {
                 const uint32_t sl = slot_of(r);
-                // regroup 1: by the pulse duration of the group's first env; 2 / 3: by the group's LONGEST block (a group that straddles the
-                // boundary between two kinds holds the short end of one ramp and the long start of the next: keyed by its first env it sorts
-                // last and its long block then runs at the very end) -- 2: estimated cost = duration x the kind's cost of a sub-step (measured
-                // on homogeneous batches, profiles/r03_devphys_regroup.txt: STT 0.466, SOT 0.646, VCMA 0.419 ms per step -> 32 : 44 : 29),
-                // 3: duration
+                // a group is keyed by its LONGEST block (keyed by its first env, a group that straddled the boundary between two kinds
+                // sorted last and its long block then ran at the very end), at its estimated cost = duration x the kind's cost of a
+                // sub-step (measured on homogeneous batches, profiles/r03_devphys_regroup.txt: STT 0.466, SOT 0.646, VCMA 0.419 ms per
+                // step -> 32 : 44 : 29)
                 const int dq = key[r] % PLAN_DUR, kind = key[r] / PLAN_DUR;
                 const int f = kind == 1 ? 44 : (kind == 2 ? 29 : 32);
-                if (a.regroup == 1) { if ((sl & 255u) == 0u) grp_d[sl >> 8] = dq; }
-                else if ((sl & 63u) == 0u) atomicMin(&grp_d[sl >> 8], a.regroup == 2 ? (1 << 20) - (PLAN_DUR - dq) * f : dq);
+                if ((sl & 63u) == 0u) atomicMin(&grp_d[sl >> 8], (1 << 20) - (PLAN_DUR - dq) * f);
             }
         __syncthreads();
         // (a ragged tile's last, partly filled group keeps its place behind the full ones: the step kernel's "slot < N" test relies on
@@ -295,7 +288,7 @@ __global__ void __launch_bounds__(PLAN_THREADS) stg_plan_tile_kernel(const PlanA
         const int64_t i = base + r * PLAN_THREADS + tid;
         if (key[r] >= 0) {
             uint32_t sl = slot_of(r);
-            if (a.by_kind && a.regroup) sl = ((uint32_t)grp_rank[sl >> 8] << 8) | (sl & 255u);
+            if (regroup) sl = ((uint32_t)grp_rank[sl >> 8] << 8) | (sl & 255u);
             const int64_t slot = base + sl;
             a.perm[slot] = (uint32_t)i;
             if (a.act_f64) ((double2*)a.act_sorted)[slot] = make_double2(((const double*)a.actions)[i], ((const double*)a.actions)[a.N + i]);
@@ -355,15 +348,13 @@ constexpr int64_t STG_REFILL_AUTO_ENVS = 131073, STG_REFILL_AUTO_ENVS_THERMAL = 
 constexpr int32_t STG_REFILL_CHECK_DEFAULT = 32;
 static inline void refill_auto(int64_t n, bool thermal, int& r, int64_t& nw) {
     r = 0; nw = 0;
-    static const int64_t min_env = std::getenv("STG_REFILL_MIN") ? std::atoll(std::getenv("STG_REFILL_MIN")) : 0;   // (experiments)
-    if (n < (min_env > 0 ? min_env : (thermal ? STG_REFILL_AUTO_ENVS_THERMAL : STG_REFILL_AUTO_ENVS))) return;
+    if (n < (thermal ? STG_REFILL_AUTO_ENVS_THERMAL : STG_REFILL_AUTO_ENVS)) return;
     const int64_t nblk = ((n + TILE_ENVS - 1) / TILE_ENVS) * TILE_WAVES;      // blocks of whole tiles (a ragged tile's empty blocks included)
     nw = 1024;
     int64_t rr = (nblk + nw - 1) / nw;
     if (rr > 8) { nw = 2048; rr = (nblk + nw - 1) / nw; }
     r = (int)(rr < 2 ? 2 : (rr > 0x7FFFFFFF ? 0x7FFFFFFF : rr));              // (envs per lane on average; only != 0 matters to the launch)
 }
-constexpr int32_t STG_WALK_TILES_DEFAULT = 1 << 20;   // all tiles of the group (fastest, see stg_slot_block)
 
 struct stg_ctx {
     int device;
@@ -390,24 +381,7 @@ struct stg_ctx {
     int32_t env_layout = ENV_LAYOUT_CORE;
     uint8_t* env_type = nullptr;      // [N]: the device kind by itself, for the plan kernel (read in env order)
     bool per_env = false;
-    int32_t walk_tiles = STG_WALK_TILES_DEFAULT;   // sorted schedule: tiles an XCD group keeps in flight (stg_slot_block)
-    int32_t spread_max = 256;                      // STG_SPREAD_MAX (experiments), see StepArgs
-    int32_t hybrid = 1;                            // STG_HYBRID=0 switches the hybrid wave-specialised launch off (experiments)
-    int32_t hybrid_min = -1;                       // fewest producer/consumer pairs for which the hybrid launch is used (STG_HYBRID_MIN; -1: by solver)
-    int32_t refill = -1, refill_check = STG_REFILL_CHECK_DEFAULT;        // STG_REFILL experiment override of cfg.lane_refill (-1: none)
 };
-
-static int32_t walk_tiles_from_env() {
-    // experiment knob (A/B runs of the schedule): STG_WALK_TILES=<n>; results never depend on it
-    const char* e = std::getenv("STG_WALK_TILES");
-    const int v = e ? std::atoi(e) : 0;
-    int32_t w = v > 0 ? v : STG_WALK_TILES_DEFAULT;
-    const char* sn = std::getenv("STG_SNAKE");       // unset: automatic (see stg_slot_block)
-    if (sn) w |= (int32_t)(std::atoi(sn) != 0 ? STG_WALK_SNAKE_ON : STG_WALK_SNAKE_OFF);
-    // STG_SNAKE_ROUNDS=<n> (with STG_SNAKE=1): the boustrophedon applies to the first n rounds only (0 = every round)
-    if (const char* sr = std::getenv("STG_SNAKE_ROUNDS")) w |= (int32_t)(((unsigned)std::atoi(sr) & 0xFFu) << STG_WALK_ROUNDS_SHIFT);
-    return w;
-}
 
 static EnvParams env_params_of(const stg_ctx* ctx) {
     EnvParams e{};
@@ -472,14 +446,6 @@ int stg_create(stg_ctx** out, int device_id, int64_t n_envs, int64_t env_id0, co
     c->device = device_id; c->N = n_envs; c->env_id0 = env_id0; c->cfg = *cfg;
     // per-env parameter records hold what this context's kernels read: their solver and torque model are fixed here
     c->env_layout = cfg->solver == STG_SOLVER_RK45 ? ENV_LAYOUT_LLGS : (cfg->torque_model == 1 ? ENV_LAYOUT_DEV : ENV_LAYOUT_CORE);
-    c->walk_tiles = walk_tiles_from_env();
-    if (const char* e = std::getenv("STG_HYBRID")) c->hybrid = std::atoi(e);
-    if (const char* e = std::getenv("STG_HYBRID_MIN")) c->hybrid_min = std::atoi(e);
-    if (const char* e = std::getenv("STG_SPREAD_MAX")) c->spread_max = std::atoi(e);
-    if (const char* e = std::getenv("STG_REFILL")) {
-        int r = 0, chk = 0;
-        if (std::sscanf(e, "%d,%d", &r, &chk) >= 1) { c->refill = r; if (chk > 0) c->refill_check = chk; }
-    }
     // one slab: the state records, the class table, the counter stripes, the lane permutation (each 256-B aligned)
     auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
     const size_t N = (size_t)n_envs;
@@ -681,13 +647,12 @@ int stg_step_many(stg_ctx* ctx, int32_t K, const void* actions, int32_t act_f64,
         pa.cls = ctx->cls; pa.ctab = ctx->ctab;
         pa.env_type = ctx->per_env ? ctx->env_type : nullptr;
         pa.by_kind = (ctx->cfg.torque_model == 1 && ((ctx->ncls > 1 && ctx->cls) || ctx->per_env)) ? 1 : 0;
-        // (measured range, tools/devphys_ab.py: 4-wavefront workgroups, between one and a half and two workgroups per CU)
         // device-physics model with a class table: kind-pure groups of four blocks (= whole workgroups of the step launch), dealt by the
         // estimated cost of their longest block (round 4, profiles/r04_devphys_order_ab.txt: 1.08-1.37x at 98 304 ... 1 048 576 envs;
-        // rounds 2-3 keyed the groups by their first env and only at 98 304 ... 131 072 envs).  Per-env parameter records launch
-        // one-wavefront workgroups: no groups there.  STG_REGROUP=0/1/2/3 forces a mode (experiments).
-        pa.regroup = (pa.by_kind && !ctx->per_env) ? 2 : 0;
-        if (const char* rg = std::getenv("STG_REGROUP")) pa.regroup = std::atoi(rg);
+        // 65 537 ... 98 303 envs not measured; there the rounds 2-3 grouping, keyed by a group's first env, lost to kind-major at 70 000
+        // envs: 0.39 -> 0.60 ms).  Per-env parameter records keep the kind-major order, measured ahead when their launches were
+        // one-wavefront workgroups (see stg_plan_tile_kernel) and not re-measured since they use 4-wavefront ones from 65 536 envs on.
+        pa.regroup = (pa.by_kind && !ctx->per_env) ? 1 : 0;
         const dim3 g((unsigned)((ctx->N + TILE_ENVS - 1) / TILE_ENVS));
         hipLaunchKernelGGL(stg_plan_tile_kernel, g, dim3(PLAN_THREADS), 0, st, pa);
         a.perm = ctx->perm;
@@ -695,35 +660,29 @@ int stg_step_many(stg_ctx* ctx, int32_t K, const void* actions, int32_t act_f64,
     }
     a.actions = actions; a.K = K; a.out_every = out_every ? 1 : 0; a.autoreset = autoreset ? 1 : 0;
     a.records = records ? 1 : 0;
-    a.walk = ctx->walk_tiles;
-    a.spread_max = ctx->spread_max;
     a.obs = obs; a.final_obs = final_obs; a.reward = reward; a.reward64 = reward_f64; a.energy = energy; a.term = terminated; a.trunc = truncated; a.status = status;
     // the Simple solver only draws a thermal field when temperature > 0 (simple_solver.py:321,378)
     const bool thermal = ctx->cfg.thermal && ctx->cfg.temperature > 0;
     const int multi = ctx->per_env ? 2 : (ctx->ncls > 1 ? 1 : 0);      // (2: every lane derives its constants from its env's record, in registers)
     const bool devphys = ctx->cfg.torque_model == 1;
-    a.force_wg1 = 0;
     // wave_spec: 0 = automatic (thermal launches of at most STG_WAVE_SPEC_MAX_ENVS envs, i.e. latency-bound ones),
     // 1 = always, -1 = never.  Results do not depend on it.
     bool pc = ctx->cfg.wave_spec > 0 || (ctx->cfg.wave_spec == 0 && ctx->N <= STG_WAVE_SPEC_MAX_ENVS);
     // hybrid (RK45 / RK4 + thermal, sorted schedule, 65 536 < N <= 131 072, automatic mode): 1024 two-wavefront workgroups -- producer /
     // consumer pairs for the 2048 - nblk longest blocks, two blocks with inline normals in each of the others (stg_kernels.hpp:
-    // stg_hybrid_block); experiment knobs STG_HYBRID=0/1, STG_HYBRID_MIN=<fewest pairs worth it>
+    // stg_hybrid_block)
     a.hybrid = 0;
     if ((ctx->cfg.solver == STG_SOLVER_RK45 || (ctx->cfg.solver == STG_SOLVER_RK4 && thermal && !devphys)) &&
         ctx->cfg.thermal && ctx->cfg.wave_spec == 0 && a.perm && !ctx->per_env &&
-        ctx->N > STG_WAVE_SPEC_MAX_ENVS && ctx->hybrid != 0) {
+        ctx->N > STG_WAVE_SPEC_MAX_ENVS) {
         const int64_t nblk = ((ctx->N + TILE_ENVS - 1) / TILE_ENVS) * TILE_WAVES;      // blocks of whole tiles
         // (a) up to 131 072 envs: pairs for the 2048 - nblk longest blocks, two fixed blocks in each other workgroup -- measured
         // (profiles/r04_hybrid_range_ab.txt) ahead of the alternatives down to 512 pairs (RK45, 98 304 envs) / 640 pairs (RK4, 90 112 envs)
         const int64_t n_pair = 2048 - nblk;
-        const int64_t min_pairs = ctx->hybrid_min >= 0 ? ctx->hybrid_min : (ctx->cfg.solver == STG_SOLVER_RK45 ? 512 : 640);
-        if (ctx->N <= 2 * STG_WAVE_SPEC_MAX_ENVS && n_pair >= min_pairs) {
-            pc = true; a.hybrid = (int32_t)n_pair + 1; a.hybrid_prio = getenv("STG_HYB_PRIO") ? atoi(getenv("STG_HYB_PRIO")) : 1;
-        }
+        const int64_t min_pairs = ctx->cfg.solver == STG_SOLVER_RK45 ? 512 : 640;
+        if (ctx->N <= 2 * STG_WAVE_SPEC_MAX_ENVS && n_pair >= min_pairs) { pc = true; a.hybrid = (int32_t)n_pair + 1; }
     }
-    // lane refill (RK45 throughput launches, see stg_step_refill_kernel).  cfg.lane_refill: 0 = automatic, -1 never, >= 2 forced;
-    // experiment knob STG_REFILL=<envs per lane>[,<attempts between refill points>] overrides the configuration
+    // lane refill (RK45 throughput launches, see stg_step_refill_kernel).  cfg.lane_refill: 0 = automatic, -1 never, >= 2 forced
     a.refill = 0; a.refill_check = STG_REFILL_CHECK_DEFAULT; a.refill_nw = 0;
     if (ctx->cfg.solver == STG_SOLVER_RK45 && K == 1 && !ctx->per_env) {
         const int64_t nblk = ((ctx->N + TILE_ENVS - 1) / TILE_ENVS) * TILE_WAVES;
@@ -732,15 +691,14 @@ int stg_step_many(stg_ctx* ctx, int32_t K, const void* actions, int32_t act_f64,
         if (ctx->cfg.lane_refill == 0) {
             refill_auto(ctx->N, ctx->cfg.thermal != 0, r, nw);
             // (two wavefronts per SIMD: a refill point every 16 attempts -- 1 048 576 envs 13.3 against 13.6 ms; with one per SIMD 16 ... 64
-            // are alike, 8 and 128 worse: tools/refill_check_sweep.py)
+            // are alike, 8 and 128 worse)
             if (nw >= 2048) chk = 16;
         }
         else if (ctx->cfg.lane_refill > 0) { r = ctx->cfg.lane_refill; nw = (nblk + r - 1) / r; }
-        if (ctx->refill >= 0) { r = ctx->refill; chk = ctx->refill_check; nw = r >= 2 ? (nblk + r - 1) / r : 0; }
         // (not combined with the wave-specialised launch: a forced wave_spec = 1 keeps the one-env-per-lane kernel)
         if (r >= 2 && nw >= 1 && !(ctx->cfg.thermal && ctx->cfg.wave_spec > 0)) {
             if (nw > 0x7FFFFFFFll) return fail(STG_E_INVALID, "lane refill: too many wavefronts");
-            a.refill = r; a.refill_check = chk > 0 ? chk : STG_REFILL_CHECK_DEFAULT; a.refill_nw = (int32_t)nw;
+            a.refill = r; a.refill_check = chk; a.refill_nw = (int32_t)nw;
             // two cursors alternate: this launch finds its own at 0 (zeroed by the previous refill launch, or by stg_create) and
             // zeroes the next one's -- launches of a context are ordered on their stream
             a.refill_cursor = ctx->refill_cursor + (ctx->refill_seq & 1) * (REFILL_STRIPES * REFILL_CURSOR_STRIDE);

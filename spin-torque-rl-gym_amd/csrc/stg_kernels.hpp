@@ -71,18 +71,14 @@ struct StepArgs {
     const uint8_t* cls;
     int32_t ncls;
     EnvParams ep;                 // per-env parameters (soa == nullptr: class table)
-    int32_t force_wg1;
     const void* actions;          // [K][2][N]
     int32_t K, out_every, autoreset;
-    int32_t walk;                 // tiles of an XCD group in flight together (sorted schedule, see stg_slot_block)
+    int32_t snake_rounds;         // sorted schedule: leading rounds of workgroups dealt in boustrophedon order, 0 = none (stg_slot_block)
     int32_t records;              // STG_OUT_RECORDS: `obs` is the record array [K or 1][N][STG_RECORD_BYTES], reward/term/trunc unused
     int32_t refill, refill_check; // lane-refill launch (stg_step_refill_kernel): != 0 selects it; attempts between refill points
     int32_t refill_nw;            // ... and its number of (persistent) wavefronts
     unsigned long long* refill_cursor;   // ... the cursors of its global queue's stripes (all 0 when the launch starts)
     unsigned long long* refill_cursor_next;   // ... and the cursors of the NEXT refill launch, which this launch zeroes (two sets alternate)
-    int32_t spread_max;           // sorted schedule, 4-wavefront workgroups: up to this many workgroups a workgroup takes ranks u, u+16, u+32,
-                                  // u+48 of its tile (spread), beyond it four consecutive ranks (stg_slot_block)
-    int32_t hybrid_prio;          // experiment knob (STG_HYB_PRIO=0): hybrid launch with the old numbering of the two-block workgroups
     int32_t hybrid;               // wave-specialised launch of 1024 workgroups over more than 1024 blocks: number of producer/consumer pairs + 1
                                   // (the other workgroups integrate two blocks with the normals inline); 0: every workgroup is a pair.
                                   // See stg_hybrid_block
@@ -397,23 +393,20 @@ constexpr int TILE_WAVES = TILE_ENVS / 64;             // = 64 wavefronts of the
 //    workgroup on the four SIMDs of a CU one each, deterministically -- 64-thread workgroups were observed to double up
 //    on some SIMDs and leave others empty (tools/probes/wave_placement.hip: up to 104 of 1024 SIMDs with two wavefronts
 //    at 65 536 envs), which a launch with one wavefront per SIMD pays for in full.
-//  * With the sorted schedule, a tile's workgroups share an XCD (so its L2 merges their scattered accesses): workgroups
-//    are observed to be dealt round-robin over the 8 XCDs (b % 8 labels the XCD group; a speed heuristic only, never a
-//    correctness assumption), XCD group r takes tiles r, r+8, r+16, ... and walks them rank-major (longest wavefronts of
-//    every tile first).  Tiles beyond the last complete group of 8 keep the identity map.
+//  * With the sorted schedule the workgroups are dealt rank-major over all tiles (every tile's longest wavefronts first):
+//    workgroups are observed to be dealt round-robin over the 8 XCDs (b % 8 labels the XCD group; a speed heuristic only,
+//    never a correctness assumption), and position q of XCD group r takes position o = 8 q + r of that order.  When the
+//    tile count is a multiple of 8, group r thereby takes exactly tiles r, r+8, r+16, ..., so a tile's workgroups share an
+//    XCD, whose L2 merges their scattered accesses.  All of a group's tiles are in flight at once: walking them a few at a
+//    time, so that their windows fit the 4 MB L2, cut HBM traffic but measured slower (profiles/r02_walk_ab.txt, 262 144
+//    envs RK45 + thermal: one tile at a time 8.04 ms, all 5.80 ms).
 //  * Which wavefronts of a tile share a workgroup (= a CU): with one workgroup per CU, strided ranks u, u+16, u+32, u+48
 //    -- measured 1.96 ms against 2.23 ms for consecutive ranks on the RK45 step at 65 536 envs: four wavefronts that
 //    are busy for the whole launch slow each other down, a long one next to progressively shorter ones does not.
-//  * How many tiles an XCD group has in flight (`walk`).  A tile's 64 wavefronts make scattered 4-8 B accesses over the
-//    tile's whole window of every state/output row (~0.7 MB per tile); the XCD's 4 MB L2 merges them into full lines
-//    only while the windows of all tiles in flight fit into it.  The group therefore walks its tiles `walk` at a time,
-//    rank-major inside such a set (longest wavefronts of the set first): measured at 262 144 mixed envs, all 8 tiles of
-//    a group at once = 363 MB of HBM traffic per launch for 42 MB of algorithmic bytes, see DESIGN.md section 3.
-constexpr uint32_t STG_WALK_SNAKE_ON = 0x40000000u, STG_WALK_SNAKE_OFF = 0x20000000u;      // flag bits in `walk`
-// with STG_WALK_SNAKE_ON: the number of leading rounds the boustrophedon order applies to (bits 21..28; 0 = every round)
-constexpr uint32_t STG_WALK_ROUNDS_SHIFT = 21u, STG_WALK_ROUNDS_MASK = 0xFFu << STG_WALK_ROUNDS_SHIFT;
+//  * The boustrophedon order over the XCD's 32 CUs for the first `snake_rounds` rounds (the host's rule: snake_rounds_of).
+constexpr uint32_t STG_SPREAD_MAX_WGS = 256;          // spread ranks up to this many workgroups (one per CU)
 template <int WGW>
-__device__ __forceinline__ int64_t stg_slot_block(uint32_t b, uint32_t nwg, bool sorted, int cw, bool pairs, uint32_t walk, uint32_t spread_max = 256u) {
+__device__ __forceinline__ int64_t stg_slot_block(uint32_t b, uint32_t nwg, bool sorted, int cw, bool pairs, uint32_t snake_rounds) {
     // (nwg: the workgroups of the batch, ceil(N / (WGW * 64)); the grid holds whole tiles, see step_grid)
     constexpr uint32_t TILE_WGS = TILE_WAVES / WGW;                   // workgroups per tile
     if (!sorted) return (int64_t)b * WGW + cw;
@@ -427,14 +420,15 @@ __device__ __forceinline__ int64_t stg_slot_block(uint32_t b, uint32_t nwg, bool
     // One workgroup per CU at most (everything resident from the start, nobody shares a SIMD): a workgroup takes ranks u, u+16,
     // u+32, u+48 of its tile (spread).  With more workgroups than CUs some CU holds two, wavefront w of both on the same SIMD: then
     // a workgroup takes four consecutive ranks, so that the workgroups dispatched last are short throughout and whoever doubles up
-    // with them loses little (spread there puts a long wavefront into EVERY workgroup: 73 728 envs RK45 2.38 ms against 1.74 ms).
-    const bool spread = nwg <= spread_max;
-    const uint32_t snake_rounds = (walk & STG_WALK_ROUNDS_MASK) >> STG_WALK_ROUNDS_SHIFT;
+    // with them loses little (spread there puts a long wavefront into EVERY workgroup: 73 728 envs RK45 2.38 ms against 1.74 ms),
+    // and a workgroup's four SIMD slots come free together for the next one (262 144 envs 6.0 ms against 7.6 ms).
+    const bool spread = nwg <= STG_SPREAD_MAX_WGS;
     if (b >= tiles * TILE_WGS) return (int64_t)tiles * TILE_WAVES;    // (beyond the grid of step_grid: no env)
-    nwg = tiles * TILE_WGS;
     const uint32_t r = b % 8;                                         // XCD group
+    const uint32_t n_q = tiles * TILE_WGS / 8u;                       // workgroups per XCD group (TILE_WGS is a multiple of 8)
     uint32_t q = b / 8;                                               // position inside the group
-    if (WGW == 1 && pairs && tiles > 8u && tiles <= 16u && !(walk & STG_WALK_SNAKE_OFF)) {
+    const uint32_t round = q / 32u, p = q % 32u;
+    if (WGW == 1 && pairs && tiles > 8u && tiles <= 16u) {
         // Wave-specialised launch with three or four workgroups per CU (32 768 < N <= 65 536 envs: 128-thread workgroups, everything
         // resident at once).  Observed (tools/probes/wave_placement.hip, 513 ... 1024 x 128 threads; profiles/r03_pair_placement.txt):
         // workgroup b runs on XCD b % 8, a CU takes the workgroups q, q+32, q+64, q+96 of its XCD group, and whatever the workgroup
@@ -446,7 +440,6 @@ __device__ __forceinline__ int64_t stg_slot_block(uint32_t b, uint32_t nwg, bool
         // 60 000 envs 2.40 ms against 2.14, RK4 + thermal 0.65 against 0.53.  At exactly 16 tiles the rule keeps each tile on one XCD
         // group (position q of group r is block 8 q + r of the order = tile r or 8 + r); rounds 1-2 had a separate map for that size
         // -- ranks j, 63-j of both tiles on CU j -- which this one replaces: RK45 the same, RK4 0.592 -> 0.559 ms.)
-        const uint32_t n_q = tiles * TILE_WGS / 8u, round = q / 32u, p = q % 32u;
         // (the fourth arrival -- whose producer shares a SIMD with the FIRST arrival's integrating wavefront, the longest of the CU --
         // takes the very shortest blocks, the second arrival the next shortest)
         const uint32_t len3 = n_q > 96u ? n_q - 96u : 0u;                     // workgroups of the group's fourth round
@@ -454,44 +447,17 @@ __device__ __forceinline__ int64_t stg_slot_block(uint32_t b, uint32_t nwg, bool
         const uint32_t o = q * 8u + r, u = o / tiles, t = o % tiles;
         return (int64_t)t * TILE_WAVES + u;
     }
-    if (tiles % 8u != 0u) {
-        // Tile counts that are no multiple of 8 (round 3: until then the tiles beyond the last complete group of 8 kept the identity
-        // map at the END of the grid, where their long wavefronts doubled up with other long ones -- 81 920 envs RK45 + thermal took
-        // 4.9 ms, more than 131 072).  No tile-to-XCD affinity is possible here (the dispatcher deals the workgroups evenly over the XCDs, the tiles
-        // do not divide evenly), and with per-env records none is needed; what matters is the order: rank-major over ALL tiles
-        // (every tile's longest workgroup first), position o = q * 8 + r of that order, with the same boustrophedon rule per XCD
-        // group.  For tile counts that are multiples of 8 this formula IS the map below (u = q / tiles_per_xcd, t = (q %
-        // tiles_per_xcd) * 8 + r).
-        const uint32_t n_q = tiles * TILE_WGS / 8u, round = q / 32u, p = q % 32u;          // (TILE_WGS is a multiple of 8)
-        const bool snake = (walk & STG_WALK_SNAKE_ON) ? true : ((walk & STG_WALK_SNAKE_OFF) ? false : n_q <= 64u);
-        const uint32_t len = (n_q - round * 32u) < 32u ? (n_q - round * 32u) : 32u;
-        if (snake && (round & 1u) && (snake_rounds == 0u || round < snake_rounds)) q = round * 32u + (len - 1u - p);
-        const uint32_t o = q * 8u + r, u = o / tiles, t = o % tiles;
-        const uint32_t rank = spread ? (u + TILE_WGS * cw) : (WGW * u + cw);
-        return (int64_t)t * TILE_WAVES + rank;
-    }
-    const uint32_t tiles_per_xcd = tiles / 8;
-    {
-        // Boustrophedon order over the XCD's 32 CUs.  The dispatcher deals a group's workgroups to its CUs in rounds of 32;
-        // when every workgroup is resident from the start (at most two rounds: every kernel fits two workgroups per CU) the
-        // assignment is static, and with the plain longest-first order CU j gets the j-th longest workgroup of BOTH rounds
-        // (131 072 envs: 1.5 work units on the first CUs, 0.6 on the last).  Reversing the second round gives every CU the
-        // same sum: RK45 + thermal at 131 072 envs 4.03 -> 3.09 ms, RK4 + thermal 0.95 -> 0.77 ms.  With more rounds the
-        // later workgroups go to whichever CU frees up first, where longest-first is the better order (262 144 envs:
-        // 5.61 ms against 6.00 ms reversed) -- so: two rounds at most (STG_SNAKE=0/1 forces it off/on for experiments).
-        const uint32_t n_q = tiles_per_xcd * TILE_WGS, round = q / 32u, p = q % 32u;
-        const bool snake = (walk & STG_WALK_SNAKE_ON) ? true : ((walk & STG_WALK_SNAKE_OFF) ? false : n_q <= 64u);
-        const uint32_t len = (n_q - round * 32u) < 32u ? (n_q - round * 32u) : 32u;
-        if (snake && (round & 1u) && (snake_rounds == 0u || round < snake_rounds)) q = round * 32u + (len - 1u - p);
-    }
-    walk &= ~(STG_WALK_SNAKE_ON | STG_WALK_SNAKE_OFF | STG_WALK_ROUNDS_MASK);
-    const uint32_t W = walk < tiles_per_xcd ? (walk ? walk : 1u) : tiles_per_xcd;        // tiles walked together
-    const uint32_t set = q / (W * TILE_WGS), within = q % (W * TILE_WGS);
-    const uint32_t Ws = (tiles_per_xcd - set * W) < W ? (tiles_per_xcd - set * W) : W;   // (the last set may be smaller)
-    const uint32_t u = within / Ws, t = (set * W + within % Ws) * 8 + r;
-    // one workgroup per CU at most (everything resident from the start): spread; otherwise keep wavefronts of similar
-    // duration together, so that a workgroup's four SIMD slots come free together for the next one (measured 6.0 ms
-    // against 7.6 ms at 262 144 envs)
+    // Boustrophedon order: the dispatcher deals a group's workgroups to its CUs in rounds of 32, and for the rounds that are resident
+    // from the start the assignment is static: with the plain longest-first order CU j gets the j-th longest workgroup of EVERY such
+    // round (131 072 envs: 1.5 work units on the first CUs, 0.6 on the last).  Reversing the odd rounds gives every CU the same sum:
+    // RK45 + thermal at 131 072 envs 4.03 -> 3.09 ms, RK4 + thermal 0.95 -> 0.77 ms.  Later rounds go to whichever CU frees up
+    // first, where longest-first is the better order (262 144 envs: 5.61 ms against 6.00 ms reversed).
+    const uint32_t len = (n_q - round * 32u) < 32u ? (n_q - round * 32u) : 32u;
+    if ((round & 1u) && round < snake_rounds) q = round * 32u + (len - 1u - p);
+    // (Tile counts that are no multiple of 8, round 3: until then the tiles beyond the last complete group of 8 kept the identity
+    // map at the END of the grid, where their long wavefronts doubled up with other long ones -- 81 920 envs RK45 + thermal took
+    // 4.9 ms, more than 131 072.  No tile-to-XCD affinity is possible for them, and with per-env records none is needed.)
+    const uint32_t o = q * 8u + r, u = o / tiles, t = o % tiles;
     const uint32_t rank = spread ? (u + TILE_WGS * cw) : (WGW * u + cw);
     return (int64_t)t * TILE_WAVES + rank;
 }
@@ -516,7 +482,7 @@ __device__ __forceinline__ int64_t refill_slot_base(int64_t idx, int64_t tiles) 
 // second wavefront that retired at once -- which broke that structure beyond 1024 workgroups: 66 000 envs 2.60 ms.)
 // Speed heuristics only: results never depend on the schedule.
 // -> first slot of the block of wavefront `wave` (0 / 1) of workgroup b; `paired`: the workgroup is a producer/consumer pair
-__device__ __forceinline__ int64_t stg_hybrid_block(uint32_t b, int wave, uint32_t n_pair, int64_t tiles, bool& paired, bool a_split = true) {
+__device__ __forceinline__ int64_t stg_hybrid_block(uint32_t b, int wave, uint32_t n_pair, int64_t tiles, bool& paired) {
     const uint32_t r = b % 8u, q = b / 8u, round = q / 32u, p = q % 32u;            // 1024 workgroups: 128 per XCD group
     const uint32_t qq = (round == 0u) ? p : (round == 2u) ? (32u + p) : (round == 3u) ? (127u - p) : (95u - p);   // (as in stg_slot_block)
     const uint32_t k = qq * 8u + r;                                                  // rank of the workgroup, longest first
@@ -526,10 +492,9 @@ __device__ __forceinline__ int64_t stg_hybrid_block(uint32_t b, int wave, uint32
     // fourth with the first arrival's (measured: profiles/r04_simd_timeline.txt) -- and SIMD arbitration is by age: wavefront 1 of a
     // two-block workgroup (the fourth, youngest arrival) sits next to the CU's LONGEST integrating wavefront and gets only the leftover
     // slots until that one retires.  It used to take block 2j+1 next to wavefront 0's 2j -- at 81 920 envs an 867-attempt block that
-    // ended the launch at 2.65 ms, 0.9 ms after its SIMD's pair; with the shortest blocks there it ends sooner (a_split = false: the old
-    // numbering, experiments).
+    // ended the launch at 2.65 ms, 0.9 ms after its SIMD's pair; with the shortest blocks there it ends sooner.
     const int64_t n_in = 1024 - (int64_t)n_pair, j = (int64_t)k - (int64_t)n_pair;
-    const int64_t blk = paired ? (int64_t)k : (a_split ? (int64_t)n_pair + (wave ? n_in + j : j) : (int64_t)n_pair + 2 * j + wave);
+    const int64_t blk = paired ? (int64_t)k : (int64_t)n_pair + (wave ? n_in + j : j);
     return blk < tiles * TILE_WAVES ? refill_slot_base(blk, tiles) : tiles * TILE_ENVS;
 }
 
@@ -843,13 +808,13 @@ stg_step_kernel(const StepArgs a) {
     // wavefronts integrate a block of their own with the normals inline (stg_hybrid_block)
     bool paired = PC;
     int64_t hyb_slot = 0;
-    if (PC && a.hybrid) hyb_slot = stg_hybrid_block(blockIdx.x, wave, (uint32_t)(a.hybrid - 1), (a.N + TILE_ENVS - 1) / TILE_ENVS, paired, a.hybrid_prio != 0);
+    if (PC && a.hybrid) hyb_slot = stg_hybrid_block(blockIdx.x, wave, (uint32_t)(a.hybrid - 1), (a.N + TILE_ENVS - 1) / TILE_ENVS, paired);
     const bool producer = PC && paired && wave >= WGW;
     const int cw = producer ? (2 * WGW - 1 - wave) : (wave < WGW ? wave : wave - WGW);   // the integrating wavefront this one is, or serves
     record_placement(a.placement, wave, lane, producer);
     const int64_t lane_slot = ((PC && a.hybrid) ? hyb_slot
                                                 : stg_slot_block<WGW>(blockIdx.x, (uint32_t)((a.N + WGW * 64 - 1) / (WGW * 64)), a.perm != nullptr, cw, PC,
-                                                                      (uint32_t)a.walk, (uint32_t)a.spread_max) * 64) + lane;
+                                                                      (uint32_t)a.snake_rounds) * 64) + lane;
     const bool live = lane_slot < a.N;
     // duration-sorted schedule: slot j of the launch integrates env perm[j], so the 64 lanes of a wavefront have
     // (nearly) equal trip counts; all state and outputs stay at the env's own index
@@ -1032,32 +997,28 @@ static int resident_workgroups_per_cu(const void* kernel, int block, size_t lds)
 // four wavefronts per CU (262 144 envs = four rounds, all resident: cfg4 0.532 -> 0.500 ms, RK4 at T = 0 K 0.54 -> 0.49 ms), the
 // device-physics and thermal ones three or two.  So the host asks the runtime and the boustrophedon applies to that many leading
 // rounds (a launch a little over two rounds keeps its first two balanced: RK4 + thermal 132 000 envs).
-static StepArgs with_snake_rule(const StepArgs& a, const void* kernel, int wgw, size_t lds, unsigned nwg) {
-    StepArgs b = a;
-    if (!a.perm || (a.walk & (int32_t)(STG_WALK_SNAKE_ON | STG_WALK_SNAKE_OFF))) return b;          // identity schedule / forced by STG_SNAKE
-    const unsigned tile_wgs = (unsigned)(TILE_WAVES / wgw), n_q = ((nwg + tile_wgs - 1) / tile_wgs) * tile_wgs / 8u;   // workgroups per XCD group
+static int32_t snake_rounds_of(const StepArgs& a, const void* kernel, int wgw, size_t lds) {
+    if (!a.perm) return 0;                                            // (identity schedule)
+    const unsigned n_q = step_grid(a, wgw) / 8u;                      // workgroups per XCD group
     const int nb = resident_workgroups_per_cu(kernel, wgw * 64, lds);
     // ... while the launch is at most half a round over what is resident: with a whole further round of workgroups waiting, plain
     // longest-first measured better throughout (cfg4 device-physics kernel, three of four rounds resident: 0.72 ms against 0.765;
     // RK4 + thermal 262 144 envs, two of four: 1.47 against 1.51)
-    if (n_q > 32u && nb >= 2 && n_q <= 32u * (unsigned)nb + 16u)
-        b.walk |= (int32_t)(STG_WALK_SNAKE_ON | ((unsigned)(nb > 255 ? 255 : nb) << STG_WALK_ROUNDS_SHIFT));
-    else b.walk |= (int32_t)STG_WALK_SNAKE_OFF;
-    return b;
+    return (n_q > 32u && nb >= 2 && n_q <= 32u * (unsigned)nb + 16u) ? nb : 0;
 }
 
 template <int SOLVER, bool THERMAL, int MULTI, bool AXIS_Z, bool DEVPHYS, int WGW>
 static void launch_step_w(const StepArgs& a, int act_f64, bool pc, hipStream_t st) {
     const dim3 grid(step_grid(a, WGW));
-    const unsigned nwg = (unsigned)((a.N + WGW * 64 - 1) / (WGW * 64));
     const size_t lds = step_dyn_lds<MULTI>(a);
+    StepArgs b = a;
     // (launched by name, not through a function-pointer variable: a host build with -fsanitize=address was seen to push the call
     // configuration and then NOT launch through the pointer -- no error, no kernel; the pointer only serves the occupancy query)
     if (act_f64) {
-        const StepArgs b = with_snake_rule(a, (const void*)&stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, double, false, WGW>, WGW, lds, nwg);
+        b.snake_rounds = snake_rounds_of(a, (const void*)&stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, double, false, WGW>, WGW, lds);
         hipLaunchKernelGGL((stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, double, false, WGW>), grid, dim3(WGW * 64), lds, st, b);
     } else {
-        const StepArgs b = with_snake_rule(a, (const void*)&stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, float, false, WGW>, WGW, lds, nwg);
+        b.snake_rounds = snake_rounds_of(a, (const void*)&stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, float, false, WGW>, WGW, lds);
         hipLaunchKernelGGL((stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, float, false, WGW>), grid, dim3(WGW * 64), lds, st, b);
     }
 }
@@ -1069,14 +1030,18 @@ static void launch_step(const StepArgs& a, int act_f64, bool pc, hipStream_t st)
         // device-physics model
         constexpr bool PC = THERMAL && !DEVPHYS;
         const dim3 grid(a.hybrid ? 1024u : step_grid(a, 1));          // (hybrid: always 1024 workgroups, see stg_hybrid_block)
+        // boustrophedon order over every round while the launch is at most two rounds (n_q <= 64 workgroups per XCD group), i.e.
+        // resident from the start; 32 768 < N <= 65 536 envs take the pair placement instead (stg_slot_block)
+        StepArgs b = a;
+        b.snake_rounds = (a.perm && step_grid(a, 1) / 8u <= 64u) ? 2 : 0;
         if (act_f64)
-            hipLaunchKernelGGL((stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, double, PC, 1>), grid, dim3(128), step_dyn_lds<MULTI>(a), st, a);
+            hipLaunchKernelGGL((stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, double, PC, 1>), grid, dim3(128), step_dyn_lds<MULTI>(a), st, b);
         else
-            hipLaunchKernelGGL((stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, float, PC, 1>), grid, dim3(128), step_dyn_lds<MULTI>(a), st, a);
+            hipLaunchKernelGGL((stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, float, PC, 1>), grid, dim3(128), step_dyn_lds<MULTI>(a), st, b);
         return;
     }
     // workgroups of 4 integrating wavefronts once there is one per CU, of 1 below that
-    if (a.N >= STG_WG4_MIN_ENVS && !a.force_wg1) launch_step_w<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, 4>(a, act_f64, pc, st);
+    if (a.N >= STG_WG4_MIN_ENVS) launch_step_w<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, 4>(a, act_f64, pc, st);
     else launch_step_w<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, 1>(a, act_f64, pc, st);
 }
 template <int SOLVER, bool AXIS_Z, bool DEVPHYS>

@@ -274,20 +274,9 @@ struct NormalStream {
     __device__ __forceinline__ void pair(float& a, float& b) {
         // the two mantissa-trick subtractions and the two final products go through packed fp32 (v_pk_add_f32 /
         // v_pk_mul_f32: one instruction for both lanes of the pair, same IEEE results)
-#ifdef STG_EXP_CHEAP_NORMALS
-        // EXPERIMENT BUILD ONLY (tools/build_variant.sh cheapn "-DSTG_EXP_CHEAP_NORMALS"; never shipped): a stand-in with the COST of a
-        // hypothetical cheaper generator -- the two xoshiro words converted and scaled, no transcendental at all, ~9.5 issue slots per
-        // value against ~18.5 -- and the WRONG distribution (uniform, unit variance).  It measures the ceiling a cheaper normal could
-        // buy before anyone designs one (profiles/EXPERIMENTS.md).
-        const f32x2 u{(float)(int32_t)next(), (float)(int32_t)next()};
-        const f32x2 v = u * f32x2{8.0654e-10f, 8.0654e-10f};          // sqrt(3) / 2^31
-        a = v.x;
-        b = v.y;
-#else
         float t, c, s_;
         pair_head(t, c, s_);
         finish_pair(t, c, s_, a, b);
-#endif
     }
     // the same pair in two halves: pair() == finish_pair(pair_head(...)); a producer wavefront can hand over the head
     // (t = -2 ln u0, cos, sin) and leave the square root and the products to the integrating wavefront
@@ -865,35 +854,6 @@ __device__ __forceinline__ double llgs_torque_norms(const V3& m, double bJ, doub
 
 __device__ __forceinline__ double rms3(const V3& a) { return sqrt(dot(a, a)) / 1.7320508075688772; }   // common.py:63-65
 
-#ifdef STG_PROFILE_LOOP
-// experiment builds only (-DSTG_PROFILE_LOOP): per integrating wavefront (first STG_PROF_WAVES of the launch) start/end
-// s_memtime, start/end s_memrealtime (100 MHz), HW_ID, attempts of its worst lane -- where each wavefront ran, for how long,
-// and at which shader clock; read back with stg_debug_waves() (tools/probe_wave_records.py)
-#define STG_PROF_WAVES 8192
-static __device__ long long g_stg_wave[STG_PROF_WAVES * 6];
-struct WaveProf {
-    long long t0, r0;
-    __device__ __forceinline__ void start() { t0 = __builtin_readcyclecounter(); r0 = __builtin_amdgcn_s_memrealtime(); }
-    __device__ __forceinline__ void stop(long long attempts) {
-        const int wid_ = blockIdx.x * ((int)blockDim.x / 64) + (int)threadIdx.x / 64;
-        long long att_max_ = attempts;
-        for (int o_ = 32; o_ > 0; o_ >>= 1) { const long long v_ = __shfl_xor(att_max_, o_); att_max_ = v_ > att_max_ ? v_ : att_max_; }
-        if ((threadIdx.x & 63) == 0 && wid_ < STG_PROF_WAVES) {
-            long long* r_ = g_stg_wave + 6 * wid_;
-            r_[0] = t0; r_[1] = __builtin_readcyclecounter(); r_[2] = r0; r_[3] = __builtin_amdgcn_s_memrealtime();
-            r_[4] = (long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11))      // HW_REG_HW_ID, 32 bits
-                    | ((long long)__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) << 32);    // HW_REG_XCC_ID
-            r_[5] = att_max_;
-        }
-    }
-};
-#else
-struct WaveProf {
-    __device__ __forceinline__ void start() {}
-    __device__ __forceinline__ void stop(long long) {}
-};
-#endif
-
 // The solve is split into begin / attempt / finish on a per-lane state (LlgsLane), so that the same arithmetic serves the
 // one-env-per-lane loop (llgs_solve) and the lane-refill step kernel (stg_kernels.hpp: stg_step_refill_kernel), in which a
 // lane that has finished its env takes the next one of its wavefront's queue while its neighbours keep integrating.
@@ -1120,8 +1080,6 @@ __device__ __forceinline__ SolveOut llgs_solve(const V3& m0, double J, double T,
     llgs_lane_begin<THERMAL, RECORD, AXIS_Z>(L, out_m, m0, J, T, k, beta, betap, rtol, atol, max_step, rk, rec, ek, ns, enabled);
     // SharedNormals: the prologue's two RHS calls were chunk 0; every attempt is one further chunk and the loop is
     // wave-uniform (a finished lane idles until the wavefront's last lane is through)
-    WaveProf prof;
-    prof.start();
     bool wave_go = true;
     if (NSRC::kShared) wave_go = ns.chunk_end(L.active);
     if (wave_go)
@@ -1138,7 +1096,6 @@ __device__ __forceinline__ SolveOut llgs_solve(const V3& m0, double J, double T,
       llgs_lane_attempt<THERMAL, RECORD, AXIS_Z>(L, out_m, k, tb, rtol, atol, max_step, rec, ek, ns, z2, z3);
       if (NSRC::kShared && !ns.chunk_end(L.active)) break;
     }
-    prof.stop(L.attempts);
     return llgs_lane_finish<RECORD>(L, out_m, rec, ek, ns);
 }
 

@@ -6,7 +6,7 @@ import bench
 import spin_torque_gym_amd as stg
 bench.cap_host_threads()
 n = 1048576
-tag = os.path.basename(os.environ.get("STG_HIP_LIBRARY", "shipped")) + " refill=" + os.environ.get("STG_REFILL", "auto")
+tag = os.path.basename(os.environ.get("STG_HIP_LIBRARY", "shipped"))
 env = stg.SpinTorqueVecEnv(n, solver="rk45", include_thermal_fluctuations=False, seed=1, autoreset=True, device_index=0, lane_sort=False)
 env.reset(seed=0)
 b = env.backend

@@ -16,7 +16,7 @@ e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=Tr
 e0.record()
 for _ in range(10): b.step(a, autoreset=True)
 e1.record(); torch.cuda.synchronize()
-print("ms per launch", e0.elapsed_time(e1) / 10, "knobs", os.environ.get("STG_REFILL"))
+print("ms per launch", e0.elapsed_time(e1) / 10)
 p = b.placement(0, raw=True)
 t0, t1, work = p["t0_us"], p["t1_us"], p["work"]
 print("waves", len(t0), "span", p["span_us"], "busy", p["simd_busy_frac"], "durations min/med/max", np.min(t1 - t0), np.median(t1 - t0), np.max(t1 - t0), "start max", (t0 - t0.min()).max(), "work min/med/max", work.min(), np.median(work), work.max())

@@ -14,12 +14,6 @@ timeout -k 10 400 python3 bench.py --full > $out/bench.json 2> $out/bench.err ||
   timeout -k 10 60 tools/probes/clock_vs_load
   echo "== tools/probes/clock_vs_load 200000 3 (sustained)"
   timeout -k 10 60 tools/probes/clock_vs_load 200000 3
-  if [ -f build/lib_prof.so ]; then
-    echo "== tools/probe_wave_records.py 65536 1 3 8 (library built with -DSTG_PROFILE_LOOP)"
-    STG_HIP_LIBRARY=$PWD/build/lib_prof.so timeout -k 10 120 python3 tools/probe_wave_records.py 65536 1 3 8
-    echo "== tools/probe_wave_records.py 65536 0 2 8"
-    STG_HIP_LIBRARY=$PWD/build/lib_prof.so timeout -k 10 120 python3 tools/probe_wave_records.py 65536 0 2 8
-  fi
 } > $out/probes.txt 2>&1
 timeout -k 10 200 python3 -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.txt 2>&1 || echo "smoke failed"
 tail -2 $out/smoke.txt; cat $out/pmc_summary.txt | head -20; head -3 $out/stats/*/*kernel_stats.csv

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Soak of the lane-refill kernel: random batch sizes, envs per lane, refill windows, class tables, thermal on/off, action
+"""Soak of the lane-refill kernel: random batch sizes, envs per lane, class tables, thermal on/off, action
 dtypes, bad actions and exhausted attempt budgets -- every output bit, the state and the on-device counters against the
 one-env-per-lane launch.  usage: python3 tools/soak_refill.py [seed] [cases] [max_envs]"""
 import os
@@ -25,7 +25,6 @@ t_start = time.time()
 for case in range(cases):
     n = int(rng.choice([rng.integers(1, 200), rng.integers(200, 9000), rng.integers(9000, max_envs)]))
     r = int(rng.integers(2, 10))
-    chk = int(rng.choice([1, 2, 7, 16, 64, 200]))
     thermal = bool(rng.integers(0, 2))
     mixed = bool(rng.integers(0, 2))
     f64 = bool(rng.integers(0, 2))
@@ -50,15 +49,11 @@ for case in range(cases):
         a[torch.rand(n, generator=g) < 0.01, 1] = float("inf")
         acts.append(a)
     outs = []
-    for refill in (False, f"{r},{chk}"):
-        if refill:
-            os.environ["STG_REFILL"] = refill
-        else:
-            os.environ["STG_REFILL"] = "0"
+    for refill in (False, r):
         env = stg.SpinTorqueVecEnv(n, include_thermal_fluctuations=thermal, solver="rk45", seed=11 + case, autoreset=not skip, skip_done=skip,
                                    max_steps=1 if skip else 2,
                                    diagnostics=True, class_index=cls, wave_spec=False, lane_sort=sort, max_attempts=budget,
-                                   out_layout=layout, **kw)
+                                   out_layout=layout, lane_refill=refill, **kw)
         env.reset(seed=case)
         rec = []
         for a in acts:
@@ -71,7 +66,7 @@ for case in range(cases):
         outs.append((rec, c))
     same = all(torch.equal(x, y) for s1, s2 in zip(outs[0][0], outs[1][0]) for x, y in zip(s1, s2)) and outs[0][1] == outs[1][1]
     noop = outs[0][1]["noop_steps"]
-    print(f"case {case}: n={n} R={r} check={chk} thermal={thermal} mixed={mixed} f64={f64} budget={budget} sort={sort} {layout} skip_done={skip}: "
+    print(f"case {case}: n={n} R={r} thermal={thermal} mixed={mixed} f64={f64} budget={budget} sort={sort} {layout} skip_done={skip}: "
           f"{'identical' if same else 'DIFFERENT'} (noop steps {noop}) [{time.time() - t_start:.0f} s]", flush=True)
     bad += not same
 print("soak:", "ok" if not bad else f"{bad} cases differ")
