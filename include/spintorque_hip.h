@@ -25,13 +25,14 @@
 #ifndef SPINTORQUE_HIP_H
 #define SPINTORQUE_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-#define STG_ABI_VERSION 4
+#define STG_ABI_VERSION 5
 
 typedef struct stg_ctx stg_ctx;
 
@@ -60,7 +61,8 @@ enum {
                                   (spin_torque_env.py:461-467; robust_solver.py:140-150) */
     STG_STATUS_RESET = 2,      /* success, but >= 1 sub-step took the non-finite -> [0,0,1] branch
                                   (simple_solver.py:213-216) */
-    STG_STATUS_INACTIVE = 3    /* env was already terminated/truncated and autoreset is off: not stepped */
+    STG_STATUS_INACTIVE = 3,   /* env was already terminated/truncated and autoreset is off: not stepped */
+    STG_STATUS_BAD_ID = 4      /* stg_step_ids: the list entry's env id is >= n_envs (nothing was read or written for it) */
 };
 
 enum { STG_OUT_SOA = 0, STG_OUT_RECORDS = 1 };
@@ -221,6 +223,34 @@ int stg_step(stg_ctx* ctx, const void* actions, int32_t act_f64, float* obs, flo
 int stg_step_many(stg_ctx* ctx, int32_t K, const void* actions, int32_t act_f64, int32_t out_every, int32_t autoreset,
                   float* obs, float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated,
                   uint8_t* truncated, uint8_t* status, void* stream);
+
+/* SpinTorqueEnv.step for the M envs env_ids[0..M) only (ABI v5; EnvPool-style asynchronous stepping, event-driven control,
+ * curricula in which some envs wait).  Semantics: stg_step_many with K = 1 applied to the listed envs -- autoreset and cfg.skip_done
+ * as there, for every solver, thermal field, class table, per-env parameter records, torque model, out_layout and action dtype --
+ * while every other env's state stays bit for bit as it is.  An env's results do not depend on which other envs share the launch.
+ *   env_ids [dev] uint32[M]; actions [dev] [2][M] in LIST order (float32, act_f64 = 0, or float64).
+ *   Outputs are compact and in list order: output j belongs to env_ids[j].  STG_OUT_SOA: obs float[12][M], reward float[M],
+ *   terminated / truncated / status uint8[M]; STG_OUT_RECORDS: obs is the record array uint8[M][STG_RECORD_BYTES].  final_obs,
+ *   reward_f64, energy, status: as stg_step_many with N = M.
+ *   Ids: an id >= n_envs is never dereferenced; its slot reports STG_STATUS_BAD_ID with a zero observation, reward and flags.
+ *   Duplicate ids give unspecified results for those envs, but no access leaves the arrays.
+ *   workspace [dev]: stg_step_ids_workspace_bytes(ctx, M) bytes (one sized for M serves every smaller list), 16-byte aligned, owned by
+ *   the caller.  It holds the launch's lane schedule, its slot-order actions and -- RK45 lane-refill launches -- its own queue cursors,
+ *   zeroed by hipMemsetAsync on `stream`: the call enqueues kernels and memsets only, touches no context-owned scratch other than the
+ *   on-device counters (atomics) and the placement ring, and can be captured in a graph and replayed.
+ * Concurrency contract.  Launches of one context on different streams may overlap if
+ *   (1) each has its own workspace (and its own output arrays), and
+ *   (2) their id sets are disjoint at 128-byte-line granularity: env records are 64 B, so envs 2k and 2k+1 share a line -- both ids of a
+ *       pair are in one in-flight set, or the partner is in none.
+ * (2) is needed because the L2 caches of the XCDs are not coherent with one another: a kernel that writes env 2k while another one on
+ * another XCD holds a stale clean copy of the same line (env 2k+1 written) could write that stale half back.  Pair-closed sets never
+ * share a line, so no kernel-boundary cache action is relied on.  The schedule heuristics (lane sort above 64 ids, wave specialisation
+ * up to 65 536, RK45 lane refill, all decided by M) never change results.  The C-ABI caller owns the bookkeeping; SpinTorqueVecEnv's
+ * send/recv pool enforces both conditions. */
+size_t stg_step_ids_workspace_bytes(const stg_ctx* ctx, int64_t M);
+int stg_step_ids(stg_ctx* ctx, int64_t M, const uint32_t* env_ids, const void* actions, int32_t act_f64, int32_t autoreset,
+                 void* workspace, float* obs, float* final_obs, float* reward, double* reward_f64, double* energy,
+                 uint8_t* terminated, uint8_t* truncated, uint8_t* status, void* stream);
 
 /* state access for parity checks and checkpoint/resume; all pointers [dev], any may be NULL.
  * m, target: double[3][N]; total_energy: double[N]; step_count: int32[N]; rng_step: uint32[N]; done: uint8[N] */

@@ -172,20 +172,32 @@ struct PlanArgs {
     uint32_t* perm;
     void* act_sorted;         // [N][2] in the actions' dtype, slot order: the step kernel reads its action with one coalesced load
                               // instead of two scattered 4-byte reads through the permutation
+    const uint32_t* ids;      // stg_step_ids (IDS kernel): N is the list length, i a list position, ids[i] its env (state, kind)
+    int64_t n_state;          // ... the context's env count: an id beyond it is not dereferenced and sorts last (no work)
 };
 
+template <bool IDS>
 __device__ __forceinline__ int plan_key(const PlanArgs& a, int64_t i) {
     double J, T;
     if (a.act_f64) parse_action<double>(((const double*)a.actions)[i], ((const double*)a.actions)[a.N + i], a.max_current, a.max_duration, J, T);
     else parse_action<float>(((const float*)a.actions)[i], ((const float*)a.actions)[a.N + i], a.max_current, a.max_duration, J, T);
-    if (a.skip_done && (a.state[i].stepw & STG_DONE_BIT)) return (a.by_kind ? PLAN_BUCKETS : PLAN_DUR) - 1;
+    int64_t e = i;                                             // the env of list position i
+    if constexpr (IDS) {
+        const uint32_t id = a.ids[i];
+        if ((int64_t)id >= a.n_state) return (a.by_kind ? PLAN_BUCKETS : PLAN_DUR) - 1;
+        e = (int64_t)id;
+    }
+    if (a.skip_done && (a.state[e].stepw & STG_DONE_BIT)) return (a.by_kind ? PLAN_BUCKETS : PLAN_DUR) - 1;
     const double w = fmax(T, 1e-10) / a.max_duration;          // below 0.1 ns the RK4 sub-step count stays at ~100
     int b = (int)(w * (PLAN_DUR - 1));
     b = b < 0 ? 0 : (b > PLAN_DUR - 2 ? PLAN_DUR - 2 : b);
-    const int kind = a.by_kind ? (a.env_type ? (int)a.env_type[i] : (int)a.ctab[(int)a.cls[i] * C_COUNT + C_DEVTYPE]) : 0;
+    const int kind = a.by_kind ? (a.env_type ? (int)a.env_type[e] : (int)a.ctab[(int)a.cls[e] * C_COUNT + C_DEVTYPE]) : 0;
     return kind * PLAN_DUR + (PLAN_DUR - 2) - b;               // descending work inside each kind: long pulses first
 }
 
+// IDS (stg_step_ids): the same sort over list positions 0..M); perm then maps a slot to a list position and act_sorted holds the actions of
+// the list (read in list order), while the state and the device kind are read through ids.
+template <bool IDS>
 __global__ void __launch_bounds__(PLAN_THREADS) stg_plan_tile_kernel(const PlanArgs a) {
     __shared__ uint32_t cnt[PLAN_BUCKETS], start[PLAN_BUCKETS];
     const int nb = a.by_kind ? PLAN_BUCKETS : PLAN_DUR;       // buckets in use
@@ -200,7 +212,7 @@ __global__ void __launch_bounds__(PLAN_THREADS) stg_plan_tile_kernel(const PlanA
         const int64_t i = base + r * PLAN_THREADS + tid;
         key[r] = -1;
         if (i < a.N) {
-            key[r] = plan_key(a, i);
+            key[r] = plan_key<IDS>(a, i);
             rank[r] = atomicAdd(&cnt[key[r]], 1u);             // rank inside the bucket (LDS atomic)
         }
     }
@@ -654,7 +666,7 @@ int stg_step_many(stg_ctx* ctx, int32_t K, const void* actions, int32_t act_f64,
         // one-wavefront workgroups (see stg_plan_tile_kernel) and not re-measured since they use 4-wavefront ones from 65 536 envs on.
         pa.regroup = (pa.by_kind && !ctx->per_env) ? 1 : 0;
         const dim3 g((unsigned)((ctx->N + TILE_ENVS - 1) / TILE_ENVS));
-        hipLaunchKernelGGL(stg_plan_tile_kernel, g, dim3(PLAN_THREADS), 0, st, pa);
+        hipLaunchKernelGGL(stg_plan_tile_kernel<false>, g, dim3(PLAN_THREADS), 0, st, pa);
         a.perm = ctx->perm;
         a.act_sorted = ctx->act_sorted;
     }
@@ -722,6 +734,112 @@ int stg_step(stg_ctx* ctx, const void* actions, int32_t act_f64, float* obs, flo
              double* energy, uint8_t* terminated, uint8_t* truncated, uint8_t* status, void* stream) {
     return stg_step_many(ctx, 1, actions, act_f64, 1, 0, obs, nullptr, reward, reward_f64, energy, terminated, truncated,
                          status, stream);
+}
+
+// stg_step_ids's workspace (caller-owned, one per launch in flight): slot -> list position, the slot-order actions, the refill launch's
+// cursor set (zeroed on the launch's stream) and the set a refill kernel zeroes for the context's next launch (unused here).  The offsets
+// grow with M, so a workspace sized for M serves every smaller list.
+struct IdsWorkspace {
+    uint32_t* perm;
+    void* act_sorted;
+    unsigned long long *cursor, *cursor_next;
+    size_t cursor_bytes, bytes;
+};
+static IdsWorkspace ids_workspace(void* base, int64_t M) {
+    auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+    IdsWorkspace w{};
+    const size_t rp = al((size_t)M * 4), ra = al((size_t)M * 16);
+    w.cursor_bytes = al(REFILL_STRIPES * REFILL_CURSOR_STRIDE * sizeof(unsigned long long));
+    char* p = (char*)base;
+    w.perm = (uint32_t*)p;
+    w.act_sorted = (void*)(p + rp);
+    w.cursor = (unsigned long long*)(p + rp + ra);
+    w.cursor_next = (unsigned long long*)(p + rp + ra + w.cursor_bytes);
+    w.bytes = rp + ra + 2 * w.cursor_bytes;
+    return w;
+}
+
+size_t stg_step_ids_workspace_bytes(const stg_ctx* ctx, int64_t M) {
+    if (!ctx || M < 1) return 0;
+    return ids_workspace(nullptr, M).bytes;
+}
+
+int stg_step_ids(stg_ctx* ctx, int64_t M, const uint32_t* env_ids, const void* actions, int32_t act_f64, int32_t autoreset,
+                 void* workspace, float* obs, float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated,
+                 uint8_t* truncated, uint8_t* status, void* stream) {
+    if (!ctx) return fail(STG_E_INVALID, "ctx is NULL");
+    if (!ctx->have_params || !ctx->have_state) return fail(STG_E_STATE, "stg_set_params and stg_reset must precede stg_step_ids");
+    if (M < 1 || M > 0xFFFFFFFFll) return fail(STG_E_INVALID, "M must be in [1, 2^32)");
+    const bool records = ctx->cfg.out_layout == STG_OUT_RECORDS;
+    if (!env_ids || !actions || !obs || !workspace) return fail(STG_E_INVALID, "env_ids/actions/obs/workspace must not be NULL");
+    if ((uintptr_t)workspace & 15u) return fail(STG_E_INVALID, "the workspace must be 16-byte aligned");
+    if (!records && (!reward || !terminated || !truncated)) return fail(STG_E_INVALID, "reward/terminated/truncated must not be NULL (cfg.out_layout = STG_OUT_SOA)");
+    if (records && ((uintptr_t)obs & 7u)) return fail(STG_E_INVALID, "the record array must be 8-byte aligned");
+    if (records && ((uintptr_t)final_obs & 7u)) return fail(STG_E_INVALID, "final_obs must be 8-byte aligned (cfg.out_layout = STG_OUT_RECORDS)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const IdsWorkspace ws = ids_workspace(workspace, M);
+    hipStream_t st = (hipStream_t)stream;
+    StepArgs a{};
+    a.s = ctx->s; a.c = cfg_view(ctx->cfg); a.N = M; a.env_id0 = ctx->env_id0;
+    a.ids = env_ids; a.n_state = ctx->N;
+    a.ctab = ctx->ctab; a.cls = ctx->cls; a.ncls = ctx->ncls; a.ep = env_params_of(ctx);
+    a.counters = ctx->counters;
+    a.placement = ctx->placement + (size_t)(ctx->launch_seq % PLACEMENT_RING) * PLACEMENT_WORDS;
+    ctx->launch_seq += 1;
+    a.perm = nullptr;
+    // schedules decided by M, as stg_step_many decides them by N (results do not depend on them): the sorted schedule above one wavefront
+    if (ctx->cfg.lane_sort >= 0 && M > 64) {
+        PlanArgs pa{};
+        pa.actions = actions; pa.act_f64 = act_f64; pa.N = M; pa.ids = env_ids; pa.n_state = ctx->N;
+        pa.max_current = ctx->cfg.max_current; pa.max_duration = ctx->cfg.max_duration;
+        pa.state = ctx->s.rec; pa.skip_done = (ctx->cfg.skip_done && !autoreset) ? 1 : 0;
+        pa.perm = ws.perm; pa.act_sorted = ws.act_sorted;
+        pa.cls = ctx->cls; pa.ctab = ctx->ctab;
+        pa.env_type = ctx->per_env ? ctx->env_type : nullptr;
+        pa.by_kind = (ctx->cfg.torque_model == 1 && ((ctx->ncls > 1 && ctx->cls) || ctx->per_env)) ? 1 : 0;
+        pa.regroup = (pa.by_kind && !ctx->per_env) ? 1 : 0;
+        hipLaunchKernelGGL(stg_plan_tile_kernel<true>, dim3((unsigned)((M + TILE_ENVS - 1) / TILE_ENVS)), dim3(PLAN_THREADS), 0, st, pa);
+        a.perm = ws.perm;
+        a.act_sorted = ws.act_sorted;
+    }
+    a.actions = actions; a.K = 1; a.out_every = 1; a.autoreset = autoreset ? 1 : 0;
+    a.records = records ? 1 : 0;
+    a.obs = obs; a.final_obs = final_obs; a.reward = reward; a.reward64 = reward_f64; a.energy = energy; a.term = terminated; a.trunc = truncated; a.status = status;
+    const bool thermal = ctx->cfg.thermal && ctx->cfg.temperature > 0;
+    const int multi = ctx->per_env ? 2 : (ctx->ncls > 1 ? 1 : 0);
+    const bool devphys = ctx->cfg.torque_model == 1;
+    const bool pc = ctx->cfg.wave_spec > 0 || (ctx->cfg.wave_spec == 0 && M <= STG_WAVE_SPEC_MAX_ENVS);
+    a.hybrid = 0;                                                      // (not measured for id launches)
+    a.refill = 0; a.refill_check = STG_REFILL_CHECK_DEFAULT; a.refill_nw = 0;
+    if (ctx->cfg.solver == STG_SOLVER_RK45 && !ctx->per_env) {
+        const int64_t nblk = ((M + TILE_ENVS - 1) / TILE_ENVS) * TILE_WAVES;
+        int r = 0, chk = STG_REFILL_CHECK_DEFAULT;
+        int64_t nw = 0;
+        if (ctx->cfg.lane_refill == 0) {
+            refill_auto(M, ctx->cfg.thermal != 0, r, nw);
+            if (nw >= 2048) chk = 16;
+        }
+        else if (ctx->cfg.lane_refill > 0) { r = ctx->cfg.lane_refill; nw = (nblk + r - 1) / r; }
+        if (r >= 2 && nw >= 1 && !(ctx->cfg.thermal && ctx->cfg.wave_spec > 0)) {
+            if (nw > 0x7FFFFFFFll) return fail(STG_E_INVALID, "lane refill: too many wavefronts");
+            a.refill = r; a.refill_check = chk; a.refill_nw = (int32_t)nw;
+            // the launch's own cursors, zeroed on its stream (no context-owned cursor: launches on other streams may overlap, and a captured
+            // graph replays the memset with the kernel)
+            HIP_TRY(hipMemsetAsync(ws.cursor, 0, ws.cursor_bytes, st));
+            a.refill_cursor = ws.cursor;
+            a.refill_cursor_next = ws.cursor_next;
+            stg_dispatch_step_rk45_refill(a, ctx->cfg.thermal != 0, multi != 0, ctx->axis_z_llgs, act_f64, st);
+            HIP_TRY(hipGetLastError());
+            return STG_OK;
+        }
+    }
+    switch (ctx->cfg.solver) {
+        case STG_SOLVER_RK4: stg_dispatch_step_rk4(a, thermal, multi, ctx->axis_z, devphys, act_f64, pc, st); break;
+        case STG_SOLVER_EULER: stg_dispatch_step_euler(a, thermal, multi, ctx->axis_z, devphys, act_f64, pc, st); break;
+        default: stg_dispatch_step_rk45(a, ctx->cfg.thermal != 0, multi, ctx->axis_z_llgs, act_f64, pc, st); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return STG_OK;
 }
 
 extern "C++" {

@@ -91,6 +91,11 @@ struct StepArgs {
     float* reward;                // [K or 1][N]
     double *reward64, *energy;
     uint8_t *term, *trunc, *status;
+    // stg_step_ids (kernels instantiated with IDS = true): N above is then the LIST length M -- the launch's slots, and the stride and
+    // index of its outputs, which are in list order --, and the env of list position j is ids[j]: its state record, Philox counter,
+    // class row and parameter record.  An id >= n_state is never dereferenced (its outputs: write_bad_id).
+    const uint32_t* ids;
+    int64_t n_state;
 };
 
 struct SolveArgs {
@@ -314,6 +319,24 @@ __device__ __forceinline__ void write_record_obs(void* base, int64_t i, const V3
     float2* rec = (float2*)((char*)base + i * STG_RECORD_BYTES);
 #pragma unroll
     for (int k = 0; k < 6; ++k) rec[k] = make_float2(o[2 * k], o[2 * k + 1]);
+}
+
+// stg_step_ids: the outputs of a list position whose id is beyond the context (STG_STATUS_BAD_ID, everything else zero; final_obs untouched)
+__device__ __forceinline__ void write_bad_id(const StepArgs& a, int64_t o) {
+    const int64_t M = a.N;
+    if (a.records) {
+        float2* rec = (float2*)((char*)a.obs + o * STG_RECORD_BYTES);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) rec[k] = make_float2(0.0f, 0.0f);
+        rec[6] = make_float2(0.0f, __uint_as_float((uint32_t)STG_STATUS_BAD_ID << 16));
+    } else {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) a.obs[k * M + o] = 0.0f;
+        a.reward[o] = 0.0f; a.term[o] = 0; a.trunc[o] = 0;
+    }
+    if (a.reward64) a.reward64[o] = 0.0;
+    if (a.energy) a.energy[o] = 0.0;
+    if (a.status) a.status[o] = STG_STATUS_BAD_ID;
 }
 
 // Where the dispatcher put this launch's wavefronts (stg_get_placement).  The schedules above lean on observed dispatcher behaviour
@@ -588,7 +611,7 @@ constexpr int REFILL_CURSOR_STRIDE = 16;      // u64 between two cursors (a 128-
 // The refill loop of ONE persistent wavefront (see stg_step_refill_kernel below, which is this loop for every wavefront of a launch).  The
 // queue holds the blocks [blk0, blk0 + nblk_q) of the rank-major order; this is wavefront w of the nw that share it.  (A device function
 // of its own since round 4's experiment of running it in the non-pair workgroups of the hybrid launch: profiles/EXPERIMENTS.md.)
-template <bool THERMAL, bool MULTI, bool AXIS_Z, typename AT>
+template <bool THERMAL, bool MULTI, bool AXIS_Z, typename AT, bool IDS>
 __device__ __forceinline__ void refill_wave(const StepArgs& a, int64_t w, int64_t nw, int64_t blk0, int64_t nblk_q, int lane, const double* s_tab,
                                             unsigned long long& c_steps, unsigned long long& c_sub, unsigned long long& c_noop) {
     const int64_t N = a.N;
@@ -601,8 +624,8 @@ __device__ __forceinline__ void refill_wave(const StepArgs& a, int64_t w, int64_
     const Dp5Tab tb = make_dp5_tab();
     InlineNormals ns;
 
-    // the lane's env in flight
-    int64_t i = 0;
+    // the lane's env in flight (IDS: i is the env, o its list position = output index)
+    int64_t i = 0, o = 0;
     bool has_env = false;
     double J = 0.0, T = 0.0;
     V3 e_tgt{0.0, 0.0, 1.0};                                    // the env's record as loaded (target, energy, step count, stream position)
@@ -625,7 +648,14 @@ __device__ __forceinline__ void refill_wave(const StepArgs& a, int64_t w, int64_
         const int64_t slot = (valid_blk ? refill_slot_base(idx, tiles) : 0) + (p & 63);
         const bool valid = valid_blk && slot < N;
         if (!valid) return;
-        i = a.perm ? (int64_t)a.perm[slot] : slot;
+        if constexpr (IDS) {
+            o = a.perm ? (int64_t)a.perm[slot] : slot;
+            const uint32_t id = a.ids[o];
+            if ((int64_t)id >= a.n_state) { write_bad_id(a, o); return; }   // (the lane draws again at the next refill point)
+            i = (int64_t)id;
+        } else {
+            i = a.perm ? (int64_t)a.perm[slot] : slot;
+        }
         V3 m;
         bool done;
         load_state(a.s, i, m, e_tgt, e_etot, e_step, e_rng, done);           // (kept for the tail of the env-step: no second read)
@@ -635,7 +665,8 @@ __device__ __forceinline__ void refill_wave(const StepArgs& a, int64_t w, int64_
             const AT2 aa = ((const AT2*)a.act_sorted)[slot];
             parse_action<AT>(aa.x, aa.y, a.c.max_current, a.c.max_duration, J, T);
         } else {
-            parse_action<AT>(act[i], act[N + i], a.c.max_current, a.c.max_duration, J, T);
+            const int64_t p = IDS ? o : i;                      // (actions are in list order)
+            parse_action<AT>(act[p], act[N + p], a.c.max_current, a.c.max_duration, J, T);
         }
         if (MULTI) {
             const int c = (int)a.cls[i];
@@ -657,7 +688,7 @@ __device__ __forceinline__ void refill_wave(const StepArgs& a, int64_t w, int64_
         int32_t step = e_step;
         uint32_t rng = e_rng;
         bool done = e_skip;                                      // (a stepped env's flag is recomputed by the tail)
-        env_step_tail(a, i, 0, true, true, !e_skip, row, (uint64_t)(a.env_id0 + i), m, tgt, etot, step, rng, done, J, T, so, c_steps, c_sub, c_noop);
+        env_step_tail(a, IDS ? o : i, 0, true, true, !e_skip, row, (uint64_t)(a.env_id0 + i), m, tgt, etot, step, rng, done, J, T, so, c_steps, c_sub, c_noop);
         store_state(a.s, i, m, tgt, etot, step, rng, done);
         has_env = false;
         L.active = false;
@@ -767,7 +798,8 @@ __device__ __forceinline__ void refill_wave(const StepArgs& a, int64_t w, int64_
 // kernel never reads cost nothing).  Rounds 2-3 derived them into a 64-row LDS block -- 23.5 KB per 64-lane workgroup, which held a CU
 // to six wavefronts (1.5 per SIMD) and forced one-wavefront workgroups, which the dispatcher spreads unevenly (1 ... 6 per SIMD): the
 // per-env cfg4 row ran at a SIMD busy share of 0.78 (profiles/r04_simd_timeline.txt).
-template <int SOLVER, bool THERMAL, int MULTI, bool AXIS_Z, bool DEVPHYS, typename AT, bool PC, int WGW>
+// IDS: a stg_step_ids launch (StepArgs::ids); false compiles to the full-N kernel.
+template <int SOLVER, bool THERMAL, int MULTI, bool AXIS_Z, bool DEVPHYS, typename AT, bool PC, int WGW, bool IDS>
 #ifndef STG_STEP_ATTR
 #define STG_STEP_ATTR
 #endif
@@ -815,10 +847,17 @@ stg_step_kernel(const StepArgs a) {
     const int64_t lane_slot = ((PC && a.hybrid) ? hyb_slot
                                                 : stg_slot_block<WGW>(blockIdx.x, (uint32_t)((a.N + WGW * 64 - 1) / (WGW * 64)), a.perm != nullptr, cw, PC,
                                                                       (uint32_t)a.snake_rounds) * 64) + lane;
-    const bool live = lane_slot < a.N;
+    const bool in_list = lane_slot < a.N;
     // duration-sorted schedule: slot j of the launch integrates env perm[j], so the 64 lanes of a wavefront have
     // (nearly) equal trip counts; all state and outputs stay at the env's own index
-    const int64_t i = live ? (a.perm ? (int64_t)a.perm[lane_slot] : lane_slot) : 0;
+    // (IDS: perm[j] is a list position o -- the index of the outputs -- and the env is ids[o]; an id beyond the context is reported and
+    // its lane has no env)
+    const int64_t o = in_list ? (a.perm ? (int64_t)a.perm[lane_slot] : lane_slot) : 0;
+    const uint32_t id = (IDS && in_list) ? a.ids[o] : 0u;
+    const bool bad = IDS && in_list && (int64_t)id >= a.n_state;
+    if (bad && !producer) write_bad_id(a, o);
+    const bool live = in_list && !bad;
+    const int64_t i = IDS ? (live ? (int64_t)id : 0) : o;
     constexpr int ENV_LAYOUT = SOLVER == STG_SOLVER_RK45 ? ENV_LAYOUT_LLGS : (DEVPHYS ? ENV_LAYOUT_DEV : ENV_LAYOUT_CORE);
     double own_row[MULTI == 2 ? C_COUNT : 1];
     const double* row;
@@ -874,7 +913,7 @@ stg_step_kernel(const StepArgs a) {
             const AT2 aa = ((const AT2*)a.act_sorted)[live ? lane_slot : 0];
             parse_action<AT>(aa.x, aa.y, a.c.max_current, a.c.max_duration, J, T);
         } else {
-            parse_action<AT>(act[((int64_t)k * 2 + 0) * N + i], act[((int64_t)k * 2 + 1) * N + i], a.c.max_current,
+            parse_action<AT>(act[((int64_t)k * 2 + 0) * N + o], act[((int64_t)k * 2 + 1) * N + o], a.c.max_current,
                              a.c.max_duration, J, T);
         }
         const bool last = (k == a.K - 1);
@@ -904,7 +943,7 @@ stg_step_kernel(const StepArgs a) {
             InlineNormals inl;
             so = run_solver<SOLVER, THERMAL, false, AXIS_Z, DEVPHYS>(m, J, T, row, a.c, rk, norec, inl, true);
         }
-        env_step_tail(a, i, ko, wr, live, lane_solves, row, env_id, m, tgt, etot, step, rng, done, J, T, so, c_steps, c_sub, c_noop);
+        env_step_tail(a, o, ko, wr, live, lane_solves, row, env_id, m, tgt, etot, step, rng, done, J, T, so, c_steps, c_sub, c_noop);
     }
     if (live) store_state(a.s, i, m, tgt, etot, step, rng, done);
     record_retired(a.placement, wave, lane, c_sub);
@@ -939,7 +978,7 @@ stg_step_kernel(const StepArgs a) {
 //    integrating.  A lane that draws an empty slot (a ragged tile's slots beyond N sit among the others) draws again next time.
 //  * Two wavefronts per SIMD: the SIMD serves the older one first (arbitration is by priority, then age:
 //    tools/probes/simd_fairness.hip), which with a shared queue only means that it takes more entries.
-template <bool THERMAL, bool MULTI, bool AXIS_Z, typename AT, int WGW>
+template <bool THERMAL, bool MULTI, bool AXIS_Z, typename AT, int WGW, bool IDS>
 __global__ void __launch_bounds__(WGW * 64) stg_step_refill_kernel(const StepArgs a) {
     extern __shared__ double s_tab[];
     __shared__ unsigned long long s_cnt[WGW * 3];
@@ -954,7 +993,7 @@ __global__ void __launch_bounds__(WGW * 64) stg_step_refill_kernel(const StepArg
     record_placement(a.placement, wave, lane, false);
     if (w >= nw) return;
     unsigned long long c_steps = 0, c_sub = 0, c_noop = 0;
-    refill_wave<THERMAL, MULTI, AXIS_Z, AT>(a, w, nw, 0, nblk, lane, s_tab, c_steps, c_sub, c_noop);
+    refill_wave<THERMAL, MULTI, AXIS_Z, AT, IDS>(a, w, nw, 0, nblk, lane, s_tab, c_steps, c_sub, c_noop);
     record_retired(a.placement, wave, lane, c_sub);
     wave_add3(a.counters + (size_t)((blockIdx.x * WGW + wave) % COUNTER_STRIPES) * COUNTER_STRIDE, s_cnt + wave * 3, c_steps, c_sub, c_noop);
 }
@@ -1007,7 +1046,7 @@ static int32_t snake_rounds_of(const StepArgs& a, const void* kernel, int wgw, s
     return (n_q > 32u && nb >= 2 && n_q <= 32u * (unsigned)nb + 16u) ? nb : 0;
 }
 
-template <int SOLVER, bool THERMAL, int MULTI, bool AXIS_Z, bool DEVPHYS, int WGW>
+template <int SOLVER, bool THERMAL, int MULTI, bool AXIS_Z, bool DEVPHYS, int WGW, bool IDS>
 static void launch_step_w(const StepArgs& a, int act_f64, bool pc, hipStream_t st) {
     const dim3 grid(step_grid(a, WGW));
     const size_t lds = step_dyn_lds<MULTI>(a);
@@ -1015,15 +1054,15 @@ static void launch_step_w(const StepArgs& a, int act_f64, bool pc, hipStream_t s
     // (launched by name, not through a function-pointer variable: a host build with -fsanitize=address was seen to push the call
     // configuration and then NOT launch through the pointer -- no error, no kernel; the pointer only serves the occupancy query)
     if (act_f64) {
-        b.snake_rounds = snake_rounds_of(a, (const void*)&stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, double, false, WGW>, WGW, lds);
-        hipLaunchKernelGGL((stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, double, false, WGW>), grid, dim3(WGW * 64), lds, st, b);
+        b.snake_rounds = snake_rounds_of(a, (const void*)&stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, double, false, WGW, IDS>, WGW, lds);
+        hipLaunchKernelGGL((stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, double, false, WGW, IDS>), grid, dim3(WGW * 64), lds, st, b);
     } else {
-        b.snake_rounds = snake_rounds_of(a, (const void*)&stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, float, false, WGW>, WGW, lds);
-        hipLaunchKernelGGL((stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, float, false, WGW>), grid, dim3(WGW * 64), lds, st, b);
+        b.snake_rounds = snake_rounds_of(a, (const void*)&stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, float, false, WGW, IDS>, WGW, lds);
+        hipLaunchKernelGGL((stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, float, false, WGW, IDS>), grid, dim3(WGW * 64), lds, st, b);
     }
 }
 
-template <int SOLVER, bool THERMAL, int MULTI, bool AXIS_Z, bool DEVPHYS>
+template <int SOLVER, bool THERMAL, int MULTI, bool AXIS_Z, bool DEVPHYS, bool IDS>
 static void launch_step(const StepArgs& a, int act_f64, bool pc, hipStream_t st) {
     if (THERMAL && !DEVPHYS && pc) {
         // wave-specialised variant: one integrating + one producing wavefront per workgroup; not built for the
@@ -1035,64 +1074,65 @@ static void launch_step(const StepArgs& a, int act_f64, bool pc, hipStream_t st)
         StepArgs b = a;
         b.snake_rounds = (a.perm && step_grid(a, 1) / 8u <= 64u) ? 2 : 0;
         if (act_f64)
-            hipLaunchKernelGGL((stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, double, PC, 1>), grid, dim3(128), step_dyn_lds<MULTI>(a), st, b);
+            hipLaunchKernelGGL((stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, double, PC, 1, IDS>), grid, dim3(128), step_dyn_lds<MULTI>(a), st, b);
         else
-            hipLaunchKernelGGL((stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, float, PC, 1>), grid, dim3(128), step_dyn_lds<MULTI>(a), st, b);
+            hipLaunchKernelGGL((stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, float, PC, 1, IDS>), grid, dim3(128), step_dyn_lds<MULTI>(a), st, b);
         return;
     }
     // workgroups of 4 integrating wavefronts once there is one per CU, of 1 below that
-    if (a.N >= STG_WG4_MIN_ENVS) launch_step_w<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, 4>(a, act_f64, pc, st);
-    else launch_step_w<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, 1>(a, act_f64, pc, st);
+    if (a.N >= STG_WG4_MIN_ENVS) launch_step_w<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, 4, IDS>(a, act_f64, pc, st);
+    else launch_step_w<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, 1, IDS>(a, act_f64, pc, st);
 }
-template <int SOLVER, bool AXIS_Z, bool DEVPHYS>
+template <int SOLVER, bool AXIS_Z, bool DEVPHYS, bool IDS>
 static void dispatch_step2(const StepArgs& a, bool thermal, int multi, int act_f64, bool pc, hipStream_t st) {
     if (thermal) {
-        if (multi == 2) launch_step<SOLVER, true, 2, AXIS_Z, DEVPHYS>(a, act_f64, pc, st);
-        else if (multi) launch_step<SOLVER, true, 1, AXIS_Z, DEVPHYS>(a, act_f64, pc, st);
-        else launch_step<SOLVER, true, 0, AXIS_Z, DEVPHYS>(a, act_f64, pc, st);
+        if (multi == 2) launch_step<SOLVER, true, 2, AXIS_Z, DEVPHYS, IDS>(a, act_f64, pc, st);
+        else if (multi) launch_step<SOLVER, true, 1, AXIS_Z, DEVPHYS, IDS>(a, act_f64, pc, st);
+        else launch_step<SOLVER, true, 0, AXIS_Z, DEVPHYS, IDS>(a, act_f64, pc, st);
     } else {
-        if (multi == 2) launch_step<SOLVER, false, 2, AXIS_Z, DEVPHYS>(a, act_f64, false, st);
-        else if (multi) launch_step<SOLVER, false, 1, AXIS_Z, DEVPHYS>(a, act_f64, false, st);
-        else launch_step<SOLVER, false, 0, AXIS_Z, DEVPHYS>(a, act_f64, false, st);
+        if (multi == 2) launch_step<SOLVER, false, 2, AXIS_Z, DEVPHYS, IDS>(a, act_f64, false, st);
+        else if (multi) launch_step<SOLVER, false, 1, AXIS_Z, DEVPHYS, IDS>(a, act_f64, false, st);
+        else launch_step<SOLVER, false, 0, AXIS_Z, DEVPHYS, IDS>(a, act_f64, false, st);
     }
 }
 // axis_z selects the easy-axis = z specialisation of the RHS (Simple: e = +z; LLGS: raw axis and demag along z);
 // devphys the opt-in device-physics torque model (fixed-step solvers only)
-template <int SOLVER>
+template <int SOLVER, bool IDS>
 static void dispatch_step(const StepArgs& a, bool thermal, int multi, bool axis_z, bool devphys, int act_f64, bool pc, hipStream_t st) {
     if constexpr (SOLVER != STG_SOLVER_RK45) {          // (the device-physics torque model exists for the fixed-step solvers only)
         if (devphys) {
-            if (axis_z) dispatch_step2<SOLVER, true, true>(a, thermal, multi, act_f64, pc, st);
-            else dispatch_step2<SOLVER, false, true>(a, thermal, multi, act_f64, pc, st);
+            if (axis_z) dispatch_step2<SOLVER, true, true, IDS>(a, thermal, multi, act_f64, pc, st);
+            else dispatch_step2<SOLVER, false, true, IDS>(a, thermal, multi, act_f64, pc, st);
             return;
         }
     }
-    if (axis_z) dispatch_step2<SOLVER, true, false>(a, thermal, multi, act_f64, pc, st);
-    else dispatch_step2<SOLVER, false, false>(a, thermal, multi, act_f64, pc, st);
+    if (axis_z) dispatch_step2<SOLVER, true, false, IDS>(a, thermal, multi, act_f64, pc, st);
+    else dispatch_step2<SOLVER, false, false, IDS>(a, thermal, multi, act_f64, pc, st);
 }
 
 // lane-refill launch of the RK45 step (a.refill = envs per lane >= 2): ceil(ceil(N / 64) / refill) wavefronts
-template <bool THERMAL, bool MULTI, bool AXIS_Z>
+template <bool THERMAL, bool MULTI, bool AXIS_Z, bool IDS>
 static void launch_refill(const StepArgs& a, int act_f64, hipStream_t st) {
     constexpr int WGW = 4;
     const int64_t nw = a.refill_nw;
     const dim3 grid((unsigned)((nw + WGW - 1) / WGW));
     const size_t lds = MULTI ? (size_t)a.ncls * C_COUNT * sizeof(double) : 0;
-    if (act_f64) hipLaunchKernelGGL((stg_step_refill_kernel<THERMAL, MULTI, AXIS_Z, double, WGW>), grid, dim3(WGW * 64), lds, st, a);
-    else hipLaunchKernelGGL((stg_step_refill_kernel<THERMAL, MULTI, AXIS_Z, float, WGW>), grid, dim3(WGW * 64), lds, st, a);
+    if (act_f64) hipLaunchKernelGGL((stg_step_refill_kernel<THERMAL, MULTI, AXIS_Z, double, WGW, IDS>), grid, dim3(WGW * 64), lds, st, a);
+    else hipLaunchKernelGGL((stg_step_refill_kernel<THERMAL, MULTI, AXIS_Z, float, WGW, IDS>), grid, dim3(WGW * 64), lds, st, a);
 }
+template <bool IDS>
 static void dispatch_refill(const StepArgs& a, bool thermal, bool multi, bool axis_z, int act_f64, hipStream_t st) {
     if (thermal) {
-        if (multi) { if (axis_z) launch_refill<true, true, true>(a, act_f64, st); else launch_refill<true, true, false>(a, act_f64, st); }
-        else { if (axis_z) launch_refill<true, false, true>(a, act_f64, st); else launch_refill<true, false, false>(a, act_f64, st); }
+        if (multi) { if (axis_z) launch_refill<true, true, true, IDS>(a, act_f64, st); else launch_refill<true, true, false, IDS>(a, act_f64, st); }
+        else { if (axis_z) launch_refill<true, false, true, IDS>(a, act_f64, st); else launch_refill<true, false, false, IDS>(a, act_f64, st); }
     } else {
-        if (multi) { if (axis_z) launch_refill<false, true, true>(a, act_f64, st); else launch_refill<false, true, false>(a, act_f64, st); }
-        else { if (axis_z) launch_refill<false, false, true>(a, act_f64, st); else launch_refill<false, false, false>(a, act_f64, st); }
+        if (multi) { if (axis_z) launch_refill<false, true, true, IDS>(a, act_f64, st); else launch_refill<false, true, false, IDS>(a, act_f64, st); }
+        else { if (axis_z) launch_refill<false, false, true, IDS>(a, act_f64, st); else launch_refill<false, false, false, IDS>(a, act_f64, st); }
     }
 }
 
 // defined in stg_step_{rk4,euler,rk45}.hip
-// (multi: 0 one class, 1 class table, 2 per-env parameter records)
+// (multi: 0 one class, 1 class table, 2 per-env parameter records; a.ids != nullptr selects the IDS kernels of stg_step_ids)
 void stg_dispatch_step_rk4(const StepArgs& a, bool thermal, int multi, bool axis_z, bool devphys, int act_f64, bool pc, hipStream_t st);
 void stg_dispatch_step_euler(const StepArgs& a, bool thermal, int multi, bool axis_z, bool devphys, int act_f64, bool pc, hipStream_t st);
 void stg_dispatch_step_rk45(const StepArgs& a, bool thermal, int multi, bool axis_z, int act_f64, bool pc, hipStream_t st);

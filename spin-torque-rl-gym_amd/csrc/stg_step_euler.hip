@@ -2,5 +2,6 @@
 #include "stg_kernels.hpp"
 
 void stg_dispatch_step_euler(const StepArgs& a, bool thermal, int multi, bool axis_z, bool devphys, int act_f64, bool pc, hipStream_t st) {
-    dispatch_step<STG_SOLVER_EULER>(a, thermal, multi, axis_z, devphys, act_f64, pc, st);
+    if (a.ids) dispatch_step<STG_SOLVER_EULER, true>(a, thermal, multi, axis_z, devphys, act_f64, pc, st);      // stg_step_ids
+    else dispatch_step<STG_SOLVER_EULER, false>(a, thermal, multi, axis_z, devphys, act_f64, pc, st);
 }

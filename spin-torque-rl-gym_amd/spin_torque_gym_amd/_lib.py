@@ -13,13 +13,13 @@ LIB_PATH = os.environ.get("STG_HIP_LIBRARY") or os.path.join(_HERE, "libspintorq
 
 STG_MAX_TARGETS = 8
 STG_MAX_CLASSES = 64
-ABI_VERSION = 4          # STG_ABI_VERSION of include/spintorque_hip.h this binding was written against
+ABI_VERSION = 5          # STG_ABI_VERSION of include/spintorque_hip.h this binding was written against
 STG_NPARAM = 30          # double-valued fields of stg_device_params, in declaration order
 SOLVERS = {"rk4": 0, "euler": 1, "rk45": 2}
 DEV_TYPES = {"stt_mram": 0, "sot_mram": 1, "vcma_mram": 2}
 OUT_LAYOUTS = {"soa": 0, "records": 1}
 RECORD_BYTES = 56        # STG_RECORD_BYTES
-STATUS_OK, STATUS_NOOP, STATUS_RESET, STATUS_INACTIVE = 0, 1, 2, 3
+STATUS_OK, STATUS_NOOP, STATUS_RESET, STATUS_INACTIVE, STATUS_BAD_ID = 0, 1, 2, 3, 4
 STG_OK, STG_E_INVALID, STG_E_HIP, STG_E_NOMEM, STG_E_STATE = 0, -1, -2, -3, -4
 
 
@@ -66,6 +66,8 @@ SYMBOLS = {
     "stg_reset": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP]),
     "stg_step": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "stg_step_many": (C.c_int, [_VP, C.c_int32, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "stg_step_ids_workspace_bytes": (C.c_size_t, [_VP, C.c_int64]),
+    "stg_step_ids": (C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "stg_get_state": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "stg_set_state": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "stg_device_terms": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),

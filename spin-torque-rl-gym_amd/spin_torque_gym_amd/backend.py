@@ -313,6 +313,80 @@ class HipBackend:
         self._keep = (a,)
         return obs, reward, reward64, term, trunc, status
 
+    # -- subset stepping (stg_step_ids) and what the send/recv pool needs of a backend -----------------------------------
+    def ids_workspace(self, m):
+        """A workspace for stg_step_ids launches of up to m ids (uint8 device tensor, stg_step_ids_workspace_bytes)."""
+        nb = int(self.lib.stg_step_ids_workspace_bytes(self._ctx, int(m)))
+        if nb <= 0:
+            raise ValueError("m must be >= 1")
+        return torch.empty(nb, dtype=torch.uint8, device=self.device)
+
+    def alloc_ids_outputs(self, m, autoreset=False):
+        """Output arrays of one stg_step_ids launch of m ids, compact and in list order: dict(buf (what the kernel writes),
+        obs [12,m] view, reward, terminated, truncated, status, reward64, energy, final_buf, final_obs [12,m] view)."""
+        dev = self.device
+        buf, obs, reward, term, trunc = alloc_step_outputs(m, dev, self.cfg.out_layout)
+        out = dict(buf=buf, obs=obs, reward=reward, terminated=term, truncated=trunc, reward64=None, energy=None, final_buf=None,
+                   final_obs=None, status=record_views(buf)[4] if self.records_layout else None)
+        if self.diagnostics:
+            out.update(reward64=torch.empty(m, dtype=torch.float64, device=dev), energy=torch.empty(m, dtype=torch.float64, device=dev),
+                       status=torch.empty(m, dtype=torch.uint8, device=dev))
+        if autoreset:
+            if self.records_layout:
+                out["final_buf"] = torch.zeros((m, 12), dtype=torch.float32, device=dev)
+                out["final_obs"] = out["final_buf"].t()
+            else:
+                out["final_buf"] = out["final_obs"] = torch.zeros((12, m), dtype=torch.float32, device=dev)
+        return out
+
+    def step_ids(self, actions, env_ids, autoreset=False, workspace=None, out=None, stream=None):
+        """stg_step_ids: one env step of the envs env_ids ([M] integers, host or device) only, with actions [2,M] in list order.
+        Outputs are compact, in list order (output j belongs to env_ids[j]): the dict of alloc_ids_outputs (`out`, or new arrays).
+        No range or duplicate checks here: an id >= N reports STATUS_BAD_ID (SpinTorqueVecEnv checks on the host).
+        workspace: from ids_workspace(M' >= M), or None for a new one.  stream: a torch.cuda.Stream to launch on -- it first waits for
+        the current stream (which produced the inputs) and the new arrays belong to it -- or None for the current stream.  Launches
+        on different streams may overlap only under the header's concurrency contract (own workspace, pair-closed disjoint id sets)."""
+        cur = torch.cuda.current_stream(self.device)
+        s = cur if stream is None else stream
+        if s is not cur:
+            s.wait_stream(cur)
+        with torch.cuda.stream(s):
+            a = torch.as_tensor(actions)
+            f64 = a.dtype == torch.float64
+            m = int(a.shape[-1])
+            a = self._dev(a, torch.float64 if f64 else torch.float32, (2, m))
+            ids = self._dev(env_ids, torch.int32, (m,))        # (the kernel reads uint32: same bits for ids < 2^31)
+            if s is not cur:
+                a.record_stream(s)
+                ids.record_stream(s)
+            ws = self.ids_workspace(m) if workspace is None else workspace
+            if out is None:
+                out = self.alloc_ids_outputs(m, autoreset)
+            rec = self.records_layout
+            diag = self.diagnostics
+            _lib.check(self.lib.stg_step_ids(self._ctx, m, _ptr(ids), _ptr(a), int(f64), int(bool(autoreset)), _ptr(ws), _ptr(out["buf"]),
+                                             _ptr(out["final_buf"]) if autoreset else None, None if rec else _ptr(out["reward"]),
+                                             _ptr(out["reward64"]), _ptr(out["energy"]), None if rec else _ptr(out["terminated"]),
+                                             None if rec else _ptr(out["truncated"]), _ptr(out["status"]) if diag else None,
+                                             C.c_void_p(s.cuda_stream)))
+        out["_keep"] = (a, ids, ws)           # inputs stay alive while the launch may still read them
+        return out
+
+    def make_streams(self, k):
+        return [torch.cuda.Stream(self.device) for _ in range(int(k))]
+
+    def record_event(self, stream):
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        return ev
+
+    def hand_over(self, out):
+        """The arrays of a completed id launch are read on the current stream from now on (caching-allocator bookkeeping)."""
+        cur = torch.cuda.current_stream(self.device)
+        for k, t in out.items():
+            if torch.is_tensor(t) and t.is_cuda:
+                t.record_stream(cur)
+
     def get_state(self):
         n, dev = self.n, self.device
         st = dict(m=torch.empty((3, n), dtype=torch.float64, device=dev),

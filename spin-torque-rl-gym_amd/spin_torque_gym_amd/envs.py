@@ -125,6 +125,8 @@ class SpinTorqueVecEnv:
     ``info['reward_f64']`` (the reward before rounding to fp32) and ``info['energy']`` (the reference's
     info['energy_consumed'], spin_torque_env.py:474-480); by default a step writes the RL-facing outputs only
     (``info['status']`` is then the records' status byte).
+    Subsets and asynchronous stepping: ``step_ids(actions, env_ids)`` steps the listed envs only (outputs compact, in list order);
+    ``async_reset`` / ``recv`` / ``send`` are the EnvPool contract on top of it (in-flight batches on a small pool of streams).
     """
 
     def __init__(self, num_envs: int, device_type: Union[str, Sequence[str]] = "stt_mram",
@@ -179,6 +181,8 @@ class SpinTorqueVecEnv:
         self.single_action_space = _box([-max_current, 0.0], [max_current, max_duration], dtype=np.float32)
         self.single_observation_space = _box(-np.inf, np.inf, shape=(12,), dtype=np.float32)
         self._needs_reset = True
+        self._pool = None                     # the send/recv pool while in async mode (async_reset ... reset)
+        self._ids_ws = None                   # workspace of synchronous step_ids calls (sized for num_envs)
 
     # batched spaces of gymnasium.vector.VectorEnv, built on first use (N x 2 / N x 12 bounds)
     @property
@@ -214,6 +218,7 @@ class SpinTorqueVecEnv:
         """options: 'initial_state' / 'target_state' as [N,3] (or [3], broadcast) arrays, 'mask' (bool [N]) to
         reset a subset.  Without them states are drawn on the device from Philox(seed, env_id, ...)."""
         options = options or {}
+        self._end_async()
         if seed is not None:
             self._rng, self._seed = _np_random(seed)
         dev_seed = int(self._rng.integers(0, 2**63 - 1))
@@ -233,6 +238,7 @@ class SpinTorqueVecEnv:
         env's own (double buffering; the multi-GPU env passes its slice of the global record array)."""
         if self._needs_reset:
             raise RuntimeError("Environment must be reset before calling step")
+        self._no_pool("step")
         a = torch.as_tensor(actions)
         if not actions_soa:
             a = a.t()
@@ -257,6 +263,7 @@ class SpinTorqueVecEnv:
 
     def step_many(self, actions, out_every: bool = True, actions_soa: bool = False):
         """K env steps in one launch.  actions [K,N,2] (or [K,2,N] with actions_soa)."""
+        self._no_pool("step_many")
         a = torch.as_tensor(actions)
         if not actions_soa:
             a = a.transpose(1, 2)
@@ -289,6 +296,7 @@ class SpinTorqueVecEnv:
     def state_dict(self):
         """Device state + everything the random streams hang on: the host PCG64 state (reset seeds), `cfg.seed` (the
         Philox key of the thermal field and of device-side auto-resets) and `env_id0` (its counter offset)."""
+        self._no_pool("state_dict")
         st = {k: v.cpu() for k, v in self.backend.get_state().items()}
         st["host_rng"] = self._rng.bit_generator.state
         st["cfg_seed"] = int(self.cfg.seed)
@@ -298,6 +306,7 @@ class SpinTorqueVecEnv:
     def load_state_dict(self, st):
         """Resumes bit-for-bit: an env built with another stream key (e.g. seed=None in a new process) or env_id0 gets
         its context rebuilt with the checkpoint's before the state is restored."""
+        self._end_async()
         seed, id0 = int(st.get("cfg_seed", self.cfg.seed)), int(st.get("env_id0", self.env_id0))
         if seed != int(self.cfg.seed) or id0 != self.env_id0:
             self.backend.close()
@@ -325,7 +334,176 @@ class SpinTorqueVecEnv:
         return health_report(self)
 
     def close(self):
+        self._end_async()
         self.backend.close()
+
+    # -- subset stepping and the EnvPool-style send/recv pool ------------------------------------------------
+    def _check_ids(self, env_ids) -> np.ndarray:
+        """env_ids (host or device integer tensor, array or sequence) -> host int64 [M].  Range and duplicate checks run on the host:
+        device ids cost one small device-to-host copy."""
+        if torch.is_tensor(env_ids):
+            if env_ids.is_floating_point() or env_ids.is_complex() or env_ids.dtype == torch.bool:
+                raise TypeError("env_ids must be integers")
+            ids = env_ids.detach().to("cpu", torch.int64).numpy().reshape(-1)
+        else:
+            ids = np.asarray(env_ids)
+            if ids.size and ids.dtype.kind not in "iu":
+                raise TypeError("env_ids must be integers")
+            ids = ids.astype(np.int64).reshape(-1)
+        if ids.size == 0:
+            raise ValueError("env_ids is empty")
+        if int(ids.min()) < 0 or int(ids.max()) >= self.num_envs:
+            raise ValueError(f"env ids must be in [0, {self.num_envs})")
+        seen = np.zeros(self.num_envs, dtype=bool)        # (O(N) instead of a sort: the pool checks every send)
+        seen[ids] = True
+        if int(np.count_nonzero(seen)) != ids.size:
+            raise ValueError("env_ids holds duplicate ids")
+        return ids
+
+    def _ids_actions(self, actions, m):
+        a = torch.as_tensor(actions)
+        if a.dim() != 2 or tuple(a.shape) != (m, 2):
+            raise ValueError(f"actions must be [M, 2] = [{m}, 2], got {tuple(a.shape)}")
+        return a.t()
+
+    def _ids_result(self, out, env_id):
+        info = {"env_id": env_id}
+        if out.get("status") is not None:
+            info["status"] = out["status"]
+        if self.autoreset:
+            info["final_obs"] = out["final_obs"].t()
+        if self.diagnostics:
+            info.update(reward_f64=out["reward64"], energy=out["energy"])
+        return out["obs"].t(), out["reward"], out["terminated"].bool(), out["truncated"].bool(), info
+
+    def step_ids(self, actions, env_ids):
+        """One env step of the envs `env_ids` only (every other env is left exactly as it is).  actions [M,2], row j for env_ids[j].
+        Returns obs [M,12], reward [M], terminated [M], truncated [M], info -- all in list order -- with info['env_id'] (int64 [M]) and
+        'status', plus 'final_obs' with autoreset and 'reward_f64' / 'energy' with diagnostics.  An env's results are those a full
+        step() would give it with the same action."""
+        if self._needs_reset:
+            raise RuntimeError("Environment must be reset before calling step_ids")
+        self._no_pool("step_ids")
+        ids = self._check_ids(env_ids)
+        a = self._ids_actions(actions, ids.size)
+        if self._ids_ws is None:
+            self._ids_ws = self.backend.ids_workspace(self.num_envs)
+        env_id = torch.as_tensor(ids).to(self.backend.device)
+        t0 = time.perf_counter()
+        out = self.backend.step_ids(a, env_id, autoreset=self.autoreset, workspace=self._ids_ws)
+        self.profiler.add("step_ids", time.perf_counter() - t0)
+        return self._ids_result(out, env_id)
+
+    def async_reset(self, batch_size: int, seed: Optional[int] = None, num_streams: int = 4):
+        """Resets every env and enters async mode (EnvPool's contract): batch k = envs [kB, (k+1)B) is then ready for recv() with its
+        reset observation.  batch_size B must be even (envs 2k and 2k+1 share a 128-byte line of state and are always sent together,
+        see send).  num_streams (<= 4 by default, the HIP runtime's default hardware-queue count): streams of the pool."""
+        B, N = int(batch_size), self.num_envs
+        if B < 2 or B % 2:
+            raise ValueError("batch_size must be even (>= 2): envs 2k and 2k+1 are stepped together")
+        if B > N:
+            raise ValueError(f"batch_size must be <= num_envs ({N})")
+        if not 1 <= int(num_streams) <= 32:
+            raise ValueError("num_streams must be in [1, 32]")
+        obs, _ = self.reset(seed=seed)
+        self._pool = _AsyncPool(self, B, int(num_streams), obs)
+
+    def recv(self):
+        """Outputs of a completed in-flight batch, the oldest completed first (spin-polls the batches' events): (obs, reward,
+        terminated, truncated, info) as step_ids returns them, info['env_id'] naming the envs.  The tensors stay valid until those ids are
+        sent again."""
+        if self._pool is None:
+            raise RuntimeError("recv: not in async mode (call async_reset first)")
+        return self._pool.recv()
+
+    def send(self, actions, env_ids):
+        """Steps env_ids with actions [M,2] asynchronously, on the next stream of the pool.  The ids must have been received and not sent
+        since, and be pair-closed: with env 2k or 2k+1 the set holds its partner too (the last env of an odd num_envs has none) -- the
+        two share a 128-byte line of state, which two launches in flight at once must not (include/spintorque_hip.h, stg_step_ids).
+        A send may merge received batches or split one along pairs."""
+        if self._pool is None:
+            raise RuntimeError("send: not in async mode (call async_reset first)")
+        self._pool.send(actions, env_ids)
+
+    def _no_pool(self, what):
+        if self._pool is not None:
+            raise RuntimeError(f"{what}: the send/recv pool is active (async_reset); call reset() to end async mode first")
+
+    def _end_async(self):
+        if self._pool is not None:
+            self._pool.drain()
+            self._pool = None
+
+
+class _AsyncPool:
+    """Bookkeeping of SpinTorqueVecEnv's async mode: which envs are in flight, which are received and held by the caller, and the
+    in-flight launches (oldest first) with their completion events.  Each stream has its own stg_step_ids workspace; the output arrays of
+    a launch are its own (they stay valid for as long as the caller holds them)."""
+
+    def __init__(self, env, batch_size, num_streams, reset_obs):
+        self.env = env
+        b = env.backend
+        n = env.num_envs
+        self.streams = b.make_streams(num_streams)
+        self.workspaces = [b.ids_workspace(n) for _ in self.streams]
+        self.next_stream = 0
+        self.held = np.zeros(n, dtype=bool)           # received, not sent since
+        self.inflight = []                            # [(ids host int64, event or None, result or None, outputs, env_id)], in send order
+        dev = b.device
+        for lo in range(0, n, batch_size):            # the reset batches: complete from the start
+            hi = min(lo + batch_size, n)
+            m = hi - lo
+            env_id = torch.arange(lo, hi, dtype=torch.int64, device=dev)
+            info = {"env_id": env_id, "status": torch.zeros(m, dtype=torch.uint8, device=dev)}
+            if env.autoreset:
+                info["final_obs"] = torch.zeros((m, 12), dtype=torch.float32, device=dev)
+            if env.diagnostics:
+                info.update(reward_f64=torch.zeros(m, dtype=torch.float64, device=dev), energy=torch.zeros(m, dtype=torch.float64, device=dev))
+            res = (reset_obs[lo:hi].clone(), torch.zeros(m, dtype=torch.float32, device=dev), torch.zeros(m, dtype=torch.bool, device=dev),
+                   torch.zeros(m, dtype=torch.bool, device=dev), info)
+            self.inflight.append((np.arange(lo, hi, dtype=np.int64), None, res, None, env_id))
+
+    def recv(self):
+        if not self.inflight:
+            raise RuntimeError("recv: nothing is in flight (send received envs first)")
+        while True:
+            for k, (ids, ev, res, out, env_id) in enumerate(self.inflight):
+                if ev is None or ev.query():
+                    del self.inflight[k]
+                    if out is not None:           # (complete: from here on the arrays are read on the current stream)
+                        self.env.backend.hand_over(out)
+                        res = self.env._ids_result(out, env_id)
+                    self.held[ids] = True
+                    return res
+            time.sleep(0)
+
+    def send(self, actions, env_ids):
+        env = self.env
+        ids = env._check_ids(env_ids)
+        if not self.held[ids].all():
+            raise ValueError("send: every id must have been received (recv) and not sent since")
+        n = env.num_envs
+        in_set = np.zeros(n, dtype=bool)
+        in_set[ids] = True
+        partner = ids ^ 1
+        partner = partner[partner < n]
+        if not in_set[partner].all():
+            raise ValueError("send: the id set splits a pair (2k, 2k+1); send both envs of a pair together")
+        a = env._ids_actions(actions, ids.size)
+        k = self.next_stream
+        self.next_stream = (k + 1) % len(self.streams)
+        b = env.backend
+        env_id = torch.as_tensor(ids).to(b.device)
+        out = b.step_ids(a, env_id, autoreset=env.autoreset, workspace=self.workspaces[k], stream=self.streams[k])
+        ev = b.record_event(self.streams[k])
+        self.held[ids] = False
+        self.inflight.append((ids, ev, None, out, env_id))
+
+    def drain(self):
+        for _, ev, _, _, _ in self.inflight:
+            if ev is not None:
+                ev.synchronize()
+        self.inflight = []
 
 
 class SpinTorqueEnv(_EnvBase):
