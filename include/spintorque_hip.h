@@ -88,7 +88,7 @@ typedef struct {
     double energy_penalty_weight;   /* 0.1 */
     double targets[STG_MAX_TARGETS][3]; /* target_states, unit vectors (default +z, -z) */
     uint64_t seed;                  /* key of the in-kernel Philox4x32-10 (thermal field, device-side resets) */
-    int64_t max_attempts;           /* RK45 attempt budget per solve; exceeded -> STG_STATUS_NOOP.  The reference has
+    int64_t max_attempts;           /* RK45 attempt budget per solve, 1 ... 2^31 - 1; exceeded -> STG_STATUS_NOOP.  The reference has
                                        no such guard (its stiff cases simply never return, SURVEY.md headline 3). */
     int32_t skip_done;              /* 1: lanes whose episode already ended are not integrated (wavefront-level
                                        early-out) and report STG_STATUS_INACTIVE; 0: reference behaviour (step anyway) */

@@ -427,7 +427,8 @@ static int check_cfg(const stg_config* c) {
     if (c->noise_model != 0 && c->noise_model != 1) return fail(STG_E_INVALID, "cfg.noise_model must be 0 (white) or 1 (Ornstein-Uhlenbeck)");
     if (c->noise_model == 1 && c->solver == STG_SOLVER_RK45) return fail(STG_E_INVALID, "cfg.noise_model = 1 needs a fixed-step solver (RK4 or Euler)");
     if (c->noise_model == 1 && !(c->noise_corr_time > 0)) return fail(STG_E_INVALID, "cfg.noise_corr_time must be positive");
-    if (c->solver == STG_SOLVER_RK45 && c->max_attempts < 1) return fail(STG_E_INVALID, "cfg.max_attempts must be >= 1");
+    // (the kernels count attempts in 32 bits)
+    if (c->solver == STG_SOLVER_RK45 && (c->max_attempts < 1 || c->max_attempts > INT32_MAX)) return fail(STG_E_INVALID, "cfg.max_attempts must be in 1 ... 2^31 - 1");
     if (c->torque_model < 0 || c->torque_model > 1) return fail(STG_E_INVALID, "cfg.torque_model must be 0 or 1");
     if (c->out_layout != STG_OUT_SOA && c->out_layout != STG_OUT_RECORDS) return fail(STG_E_INVALID, "cfg.out_layout must be STG_OUT_SOA or STG_OUT_RECORDS");
     if (c->lane_refill < -1 || c->lane_refill == 1 || c->lane_refill > 1024) return fail(STG_E_INVALID, "cfg.lane_refill must be -1 (never), 0 (automatic) or the number of envs per lane (2..1024)");

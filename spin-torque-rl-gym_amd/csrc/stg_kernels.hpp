@@ -636,7 +636,7 @@ __device__ __forceinline__ void refill_wave(const StepArgs& a, int64_t w, int64_
     const double* row = a.ctab;
     LlgsK k = load_llgs(row);
     LlgsLane L;
-    L.active = false; L.ok = true; L.rejected = false; L.attempts = 0; L.npts = 0;
+    L.active = false; L.idle = true; L.rejected = false; L.attempts = 0; L.npts = 0;
     L.y = L.f = L.m0 = V3{0.0, 0.0, 1.0};
     L.t = L.T = L.h_abs = L.min_step = L.bJ = L.bpJ = 0.0;
     V3 out_m{0.0, 0.0, 1.0};
@@ -713,12 +713,15 @@ __device__ __forceinline__ void refill_wave(const StepArgs& a, int64_t w, int64_
     const int check = a.refill_check > 0 ? a.refill_check : 1;
     for (;;) {
         // up to `check` attempts of the whole wavefront (lanes that are through walk along, frozen) ...
+        // (lanes are refilled between these runs, so each keeps an attempt counter of its own; the flags travel as lane masks)
+        LlgsMasks M = llgs_masks_open(L);
         for (int c = 0; c < check; ++c) {
-            llgs_lane_gate(L, a.c.max_attempts);
-            if (__ballot(L.active) == 0ull) break;
+            llgs_lane_gate<false>(L, M, (int32_t)a.c.max_attempts);
+            if (M.active == 0ull) break;
             V3 z2{0.0, 0.0, 0.0}, z3{0.0, 0.0, 0.0};
-            llgs_lane_attempt<THERMAL, false, AXIS_Z>(L, out_m, k, tb, a.c.rtol, a.c.atol, a.c.max_step, norec, noek, ns, z2, z3);
+            llgs_lane_attempt<THERMAL, false, AXIS_Z, false>(L, M, 0, out_m, k, tb, a.c.rtol, a.c.atol, a.c.max_step, norec, noek, ns, z2, z3);
         }
+        llgs_masks_close(L, M);
         // ... then a refill point: finished lanes write their env; every lane without an env -- finished just now, or one that drew an
         // empty slot earlier -- takes the next entries in lane order: first what the wavefront has reserved, then a new reservation from
         // its current stripe (ONE atomic)

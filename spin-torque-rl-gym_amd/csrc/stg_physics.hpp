@@ -24,6 +24,8 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "stg_minstep.hpp"
+
 namespace stg {
 
 // ---- per-class derived constants (host-computed in fp64, staged in LDS by the kernels) ----------
@@ -153,14 +155,18 @@ __device__ __forceinline__ double fmax_abs(double a, double b) {
     return r;
 }
 
-// dst_i = src_i in the lanes of `mask` (a ballot), seven doubles at once: seven v_mov_b64 under EXEC = mask instead of fourteen
-// v_cndmask_b32 -- the commit of an accepted attempt (state, f(state), time).
-__device__ __forceinline__ void commit7(unsigned long long mask, double& d0, double s0, double& d1, double s1, double& d2, double s2,
-                                        double& d3, double s3, double& d4, double s4, double& d5, double s5, double& d6, double s6) {
-    // (EXEC and the mask change places by three XORs, so that no further SGPR pair is needed: the kernels sit at the SGPR limit)
-    asm("s_xor_b64 exec, exec, %[m]\n\t"
-        "s_xor_b64 %[m], exec, %[m]\n\t"
-        "s_xor_b64 exec, exec, %[m]\n\t"
+// The commit of an accepted RK45 attempt, in the lanes of `mask` (a ballot) and nowhere else, under EXEC = mask:
+//  * dst_i = src_i, seven doubles (time, state, f(state)): seven v_mov_b64 instead of fourteen v_cndmask_b32;
+//  * min_step = 10 ulp(t_new), from the exponent (stg_minstep.hpp: min_step_pos -- t_new > 0 in an accepting lane, it is at least the
+//    step just taken; `unit` = MIN_STEP_UNIT): an unchanged t leaves min_step unchanged, so the other lanes keep theirs;
+//  * h = max(h, min_step): the next step()'s lower clamp (rk.py:121-126), which applies after an accepted attempt only.
+// (s0 is the new time.  The old EXEC waits in an SGPR pair of its own.)
+__device__ __forceinline__ void commit_step(unsigned long long mask, double& d0, double s0, double& d1, double s1, double& d2, double s2,
+                                            double& d3, double s3, double& d4, double s4, double& d5, double s5, double& d6, double s6,
+                                            double& min_step, double& h, double unit) {
+    unsigned long long saved;
+    int e;
+    asm("s_and_saveexec_b64 %[sv], %[m]\n\t"
         "v_mov_b64 %[d0], %[s0]\n\t"
         "v_mov_b64 %[d1], %[s1]\n\t"
         "v_mov_b64 %[d2], %[s2]\n\t"
@@ -168,9 +174,15 @@ __device__ __forceinline__ void commit7(unsigned long long mask, double& d0, dou
         "v_mov_b64 %[d4], %[s4]\n\t"
         "v_mov_b64 %[d5], %[s5]\n\t"
         "v_mov_b64 %[d6], %[s6]\n\t"
-        "s_mov_b64 exec, %[m]"
-        : [d0] "+v"(d0), [d1] "+v"(d1), [d2] "+v"(d2), [d3] "+v"(d3), [d4] "+v"(d4), [d5] "+v"(d5), [d6] "+v"(d6), [m] "+s"(mask)
-        : [s0] "v"(s0), [s1] "v"(s1), [s2] "v"(s2), [s3] "v"(s3), [s4] "v"(s4), [s5] "v"(s5), [s6] "v"(s6)
+        "v_frexp_exp_i32_f64 %[e], %[s0]\n\t"
+        "v_max_i32 %[e], %[fl], %[e]\n\t"
+        "v_ldexp_f64 %[ms], %[u], %[e]\n\t"
+        "v_max_f64 %[h], %[h], %[ms]\n\t"
+        "s_mov_b64 exec, %[sv]"
+        : [d0] "+v"(d0), [d1] "+v"(d1), [d2] "+v"(d2), [d3] "+v"(d3), [d4] "+v"(d4), [d5] "+v"(d5), [d6] "+v"(d6), [ms] "+v"(min_step),
+          [h] "+v"(h), [e] "=&v"(e), [sv] "=&s"(saved)
+        : [s0] "v"(s0), [s1] "v"(s1), [s2] "v"(s2), [s3] "v"(s3), [s4] "v"(s4), [s5] "v"(s5), [s6] "v"(s6), [u] "v"(unit), [m] "s"(mask),
+          [fl] "n"(MIN_STEP_EXP_FLOOR)
         : "scc");
 }
 
@@ -339,6 +351,7 @@ struct InlineNormals {
     static constexpr bool broken = false;
     __device__ __forceinline__ void peek() {}
     __device__ __forceinline__ bool chunk_end(bool lane_continues) { return lane_continues; }
+    __device__ __forceinline__ bool chunk_end_wave(bool mine) { return mine; }
 };
 
 // A chunk of the shared stream (one rendezvous of an integrating wavefront with its producer): an RK45 attempt (18 normals; the
@@ -386,9 +399,20 @@ struct SharedNormalsT {
     int* hs;                // LDS: the handshake words / BARRIER: the integrator's "continues" flag, two alternating copies
     int lane, it, idx, seen;   // seen: the producer's count as last read (a lane-uniform value in a VGPR)
     bool broken;               // the poll budget ran out (never, unless the protocol is broken): the solve reports failure
-    __device__ __forceinline__ void begin(const RngKey&) { it = 0; idx = 0; seen = 1; broken = false; }    // chunk 0 is there (H2)
+    // The RK45 ring (a barrier per attempt, two slots): where the current slot starts and which flag copy is next are per-lane values that
+    // TOGGLE -- one v_xor_b32 each per attempt -- instead of being rebuilt from `it` (s_bitcmp1 / s_cselect / v_or and s_and / s_lshl / v_mov)
+    static constexpr bool kToggle = BARRIER && SCALED;
+    int slot_el, flag_el;      // kToggle: element offset of this lane in the current slot (lane, or CHUNK * 64 + lane); 0 / 1
+    __device__ __forceinline__ void begin(const RngKey&) {
+        it = 0; idx = 0; seen = 1; broken = false;                                                         // chunk 0 is there (H2)
+        if (kToggle) {
+            static_assert(((CHUNK * 64) & 63) == 0, "the slot bit and the lane bits are disjoint");
+            slot_el = lane; flag_el = 0;
+            asm volatile("" : "+v"(slot_el), "+v"(flag_el));      // (kept in VGPRs)
+        }
+    }
     __device__ __forceinline__ V3 draw(bool) {
-        const T* b = buf + ((it & (DEPTH - 1)) * CHUNK + idx) * 64 + lane;
+        const T* b = kToggle ? buf + slot_el + idx * 64 : buf + ((it & (DEPTH - 1)) * CHUNK + idx) * 64 + lane;
         idx += 3;
         return V3{(double)b[0], (double)b[64], (double)b[128]};
     }
@@ -399,10 +423,12 @@ struct SharedNormalsT {
     }
     // end of a chunk: publishes that the slot is free and whether this (wave-uniform) wavefront continues; returns
     // that, once the next chunk is in LDS.  Straight-line when the producer is ahead (the normal case).
-    __device__ __forceinline__ bool chunk_end(bool lane_continues) {
-        const bool mine = __ballot(lane_continues) != 0ull;
+    __device__ __forceinline__ bool chunk_end(bool lane_continues) { return chunk_end_wave(__ballot(lane_continues) != 0ull); }
+    // (the same for a caller that holds the wave-uniform answer already)
+    __device__ __forceinline__ bool chunk_end_wave(bool mine) {
         if (BARRIER) {
-            lds_flag(hs)[it & 1] = mine ? 1 : 0;
+            lds_flag(hs)[kToggle ? flag_el : (it & 1)] = mine ? 1 : 0;
+            if (kToggle) { flag_el ^= 1; slot_el ^= CHUNK * 64; }
             __syncthreads();
             ++it;
             idx = 0;
@@ -866,6 +892,7 @@ __device__ __forceinline__ double rms3(const V3& a) { return sqrt(dot(a, a)) / 1
 // (stage nodes C = 1/5, 3/10, 4/5, 8/9, 1, 1: the RHS is autonomous but for the pulse gate, see llgs_lane_attempt)
 struct Dp5Tab {
     double A51, A52, A53, A54, A61, A62, A63, A64, A65, E1, E3, E4, E5, E6, E7;
+    double ms_unit;          // MIN_STEP_UNIT (commit_step)
 };
 __device__ __forceinline__ Dp5Tab make_dp5_tab() {
     Dp5Tab t;
@@ -874,6 +901,7 @@ __device__ __forceinline__ Dp5Tab make_dp5_tab() {
     t.A65 = vgpr_const(-5103.0 / 18656);
     t.E1 = vgpr_const(-71.0 / 57600); t.E3 = vgpr_const(71.0 / 16695); t.E4 = vgpr_const(-71.0 / 1920); t.E5 = vgpr_const(17253.0 / 339200);
     t.E6 = vgpr_const(-22.0 / 525); t.E7 = vgpr_const(1.0 / 40);
+    t.ms_unit = vgpr_const(MIN_STEP_UNIT);
     return t;
 }
 
@@ -883,13 +911,25 @@ struct LlgsLane {
     V3 m0;                   // the input row (returned when the solve fails)
     double t, T, h_abs, min_step;
     double bJ, bpJ;          // beta J, beta' J (0 when |J| < 1e-12)
-    int64_t attempts;
+    int32_t attempts;        // (the host rejects a budget beyond 32 bits: stg_create)
     int32_t npts;
-    bool ok, rejected, active;
+    bool idle;               // nothing to integrate (a disabled lane, or t0 == T): the solve counts as ok
+    bool rejected, active;
 };
 
-__device__ __forceinline__ double llgs_min_step_at(double tt) {   // 10 * |nextafter(t, inf) - t|, t >= 0                      rk.py:119
-    return 10.0 * (__longlong_as_double(__double_as_longlong(tt) + 1) - tt);
+// The flags an attempt loop updates, as 64-bit lane masks (wave-uniform values: SGPR pairs, combined by scalar instructions; the
+// per-lane booleans of LlgsLane cost a 0/1 VGPR each, with a v_cndmask / v_cmp round trip per update, once they are carried around a loop).
+//  active: the lane integrates.  pacc: the lane's previous attempt was accepted (rk.py's `step_rejected`, inverted); only a lane that
+//  is active reads it, so for the others it holds anything.
+typedef unsigned long long lanemask;
+struct LlgsMasks {
+    lanemask active, pacc;
+};
+__device__ __forceinline__ bool lane_in(lanemask m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+__device__ __forceinline__ LlgsMasks llgs_masks_open(const LlgsLane& L) { return LlgsMasks{__ballot(L.active), __ballot(!L.rejected)}; }
+__device__ __forceinline__ void llgs_masks_close(LlgsLane& L, const LlgsMasks& M) {
+    L.active = lane_in(M.active);
+    L.rejected = !lane_in(M.pacc);
 }
 
 // every accepted point is renormalised on output (llgs_solver.py:152-153); without a recorder only the last one is ever
@@ -956,20 +996,24 @@ __device__ __forceinline__ void llgs_lane_begin(LlgsLane& L, V3& out_m, const V3
         const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : fifth_root(0.01 * rcp_fast(fmax(d1, d2)));
         h_abs = fmin(fmin(100.0 * h0, h1), fmin(T, max_step));
     }
-    L.ok = true;
     L.rejected = false;
     L.attempts = 0;
-    L.min_step = llgs_min_step_at(L.t);
+    L.min_step = min_step_at(L.t);
     L.h_abs = h_abs > max_step ? max_step : (h_abs < L.min_step ? L.min_step : h_abs);          // rk.py:121-126
     L.active = enabled && (L.t != T);       // (a disabled lane only walks the workgroup's chunk loop)
+    // A lane that starts stops for one of three reasons: it arrived (t == T), its step fell below min_step, or the attempt budget ran
+    // out.  So "ok" needs no flag of its own inside the loop: it is `idle || t == T` afterwards (llgs_lane_finish).
+    L.idle = !L.active;
 }
 
-// The budget / minimum-step test that opens an attempt (rk.py:132-133 + the attempt budget); a lane that fails it stops.
-__device__ __forceinline__ void llgs_lane_gate(LlgsLane& L, int64_t max_attempts) {
-    // (bitwise on purpose: no short-circuit control flow inside the wave-uniform attempt loop)
-    const bool fail_now = L.active & ((L.h_abs < L.min_step) | (L.attempts >= max_attempts));
-    L.ok = L.ok & !fail_now;
-    L.active = L.active & !fail_now;
+// The minimum-step test that opens an attempt (rk.py:132-133); a lane that fails it stops.  UNIFORM_IT: every lane of the wavefront
+// started at iteration 0 of the loop (one env per lane), so the attempt budget is a test of the loop's scalar counter, made by the
+// loop itself; otherwise (lane refill) a lane has a counter of its own and the budget is tested here.
+template <bool UNIFORM_IT>
+__device__ __forceinline__ void llgs_lane_gate(const LlgsLane& L, LlgsMasks& M, int32_t max_attempts) {
+    lanemask stop = __ballot(L.h_abs < L.min_step);
+    if (!UNIFORM_IT) stop |= __ballot(L.attempts >= max_attempts);
+    M.active &= ~stop;
 }
 
 // ONE attempted step (rk.py:111-181) of a lane; the body has no lane-divergent control flow: a lane that is through (or
@@ -978,9 +1022,10 @@ __device__ __forceinline__ void llgs_lane_gate(LlgsLane& L, int64_t max_attempts
 // bookkeeping itself: same sequence of attempts per lane, but a wavefront needs max-over-lanes(total attempts) iterations
 // instead of sum-over-steps(max-over-lanes(attempts of that step)).
 // z2, z3: the thermal fields of the first two RHS calls of the attempt (fetched by the caller, see llgs_draw).
-template <bool THERMAL, bool RECORD, bool AXIS_Z, class NSRC>
-__device__ __forceinline__ void llgs_lane_attempt(LlgsLane& L, V3& out_m, const LlgsK& k, const Dp5Tab& tb, double rtol, double atol,
-                                                  double max_step, const Recorder& rec, const LlgsEnergyK& ek, NSRC& ns, V3 z2, V3 z3) {
+// M: the loop's flags; `it`: attempts the wavefront's loop has behind it (UNIFORM_IT: a still-active lane has made exactly these).
+template <bool THERMAL, bool RECORD, bool AXIS_Z, bool UNIFORM_IT, class NSRC>
+__device__ __forceinline__ void llgs_lane_attempt(LlgsLane& L, LlgsMasks& M, int32_t it, V3& out_m, const LlgsK& k, const Dp5Tab& tb, double rtol,
+                                                  double atol, double max_step, const Recorder& rec, const LlgsEnergyK& ek, NSRC& ns, V3 z2, V3 z3) {
     constexpr double A21 = 1.0 / 5;
     constexpr double A31 = 3.0 / 40, A32 = 9.0 / 40;
     constexpr double A41 = 44.0 / 45, A42 = -56.0 / 15, A43 = 32.0 / 9;
@@ -988,12 +1033,13 @@ __device__ __forceinline__ void llgs_lane_attempt(LlgsLane& L, V3& out_m, const 
     const double A51 = tb.A51, A52 = tb.A52, A53 = tb.A53, A54 = tb.A54, A61 = tb.A61, A62 = tb.A62, A63 = tb.A63, A64 = tb.A64, A65 = tb.A65;
     const double E1 = tb.E1, E3 = tb.E3, E4 = tb.E4, E5 = tb.E5, E6 = tb.E6, E7 = tb.E7;
     const double T = L.T;
-    const bool active = L.active;
+    const bool active = lane_in(M.active);
     const V3 y = L.y;
     const double t = L.t;
     auto fun = [&](const V3& yy, const V3& ht, bool on) -> V3 { return llgs_fun<THERMAL, AXIS_Z, false>(L, k, yy, ht, on); };
     auto draw = [&](bool even) -> V3 { return llgs_draw<THERMAL>(ns, k, even); };
-    L.attempts += active ? 1 : 0;
+    // (one masked 32-bit move; the counter of a lane that is through stays)
+    if (UNIFORM_IT) L.attempts = active ? it + 1 : L.attempts; else L.attempts += active ? 1 : 0;
     const double t_new = fmin(add_x(t, L.h_abs), T);                       // rk.py:135-138: if t_new - T > 0: t_new = T
     const double h = sub_x(t_new, t);
     const double h_try = fabs(h);
@@ -1034,24 +1080,27 @@ __device__ __forceinline__ void llgs_lane_attempt(LlgsLane& L, V3& out_m, const 
     // Controller (rk.py:158-181), branch-free: both outcomes share err^-0.2 and differ in a handful of selects.
     // 0.9 * err^-0.2 saturates at MAX_FACTOR = 10 for err <= 0.09^5 and at MIN_FACTOR = 0.2 for err >= 4.5^5 (err is
     // the SQUARED norm here); NaN error norms reject (nan < 1 is False) with fmax(0.2, NaN) = 0.2, as in SciPy.
-    const bool acc = active && err < 1.0;
+    const lanemask accm = M.active & __ballot(err < 1.0);
+    const bool acc = lane_in(accm);
     const double r9 = 0.9 * inv_tenth_root(err);
     // (the clamps also cover the ends of the range: err -> 0 makes r9 huge, inf or -- at exactly 0 -- NaN, and
     // fmin/fmax return their other operand for a NaN; err -> inf makes it 0 or NaN)
-    double fa = fmin(10.0, r9);
-    fa = L.rejected ? fmin(1.0, fa) : fa;
+    // after a rejected attempt the factor is capped at 1 instead of MAX_FACTOR: min(1, min(10, r9)) = min(1, r9) for every r9, NaN
+    // included (both give 1), so the cap is selected and ONE minimum taken
+    const double fa = fmin(lane_in(M.pacc) ? 10.0 : 1.0, r9);
     const double fr = fmax(0.2, r9);
-    // h_abs of a lane that is through (or never started) is dead: nothing reads it before llgs_lane_begin writes it again
-    const double h_next = h_try * (acc ? fa : fr);
+    // h_abs of a lane that is through (or never started) is dead: nothing reads it before llgs_lane_begin writes it again.
+    // The next step()'s clamp of h_abs to [min_step, max_step] (rk.py:121-126) applies after an accepted attempt only; a rejected one has
+    // shrunk h_try <= max_step, so the upper clamp is a no-op there and runs unconditionally.  It never returns a NaN (max_step is none) nor
+    // anything below +0, so the lower clamp against 0 that a rejecting lane would get is the identity and is left out (commit_step).
+    double h_next = fmin(h_try * (acc ? fa : fr), max_step);
     // an accepted attempt advances, records, and does the next step()'s prologue
-    commit7(__ballot(acc), L.t, t_new, L.y.x, y_new.x, L.y.y, y_new.y, L.y.z, y_new.z, L.f.x, f_new.x, L.f.y, f_new.y, L.f.z, f_new.z);
+    commit_step(accm, L.t, t_new, L.y.x, y_new.x, L.y.y, y_new.y, L.y.z, y_new.z, L.f.x, f_new.x, L.f.y, f_new.y, L.f.z, f_new.z,
+                L.min_step, h_next, tb.ms_unit);
+    L.h_abs = h_next;
     if (RECORD) { if (acc) llgs_lane_emit<RECORD>(L, out_m, rec, ek); } else L.npts += acc ? 1 : 0;
-    L.rejected = active ? !acc : L.rejected;
-    L.min_step = llgs_min_step_at(L.t);                                                  // unchanged t -> unchanged value
-    // the next step()'s clamp of h_abs to [min_step, max_step] (rk.py:121-126) applies after an accepted attempt only; a rejected
-    // one has shrunk h_try <= max_step, so the upper clamp is a no-op there and runs unconditionally
-    L.h_abs = fmax(fmin(h_next, max_step), acc ? L.min_step : 0.0);
-    L.active = active && (L.t != T);
+    M.pacc = accm;
+    M.active &= __ballot(L.t != T);
 }
 
 // end of a solve: the final row (the input row when the solve failed), accepted points, attempts
@@ -1062,8 +1111,9 @@ __device__ __forceinline__ SolveOut llgs_lane_finish(LlgsLane& L, V3& out_m, con
     o.m = out_m;
     o.n = L.npts - 1;
     o.work = L.attempts;
-    o.ok = L.ok && !ns.broken;
-    if (!L.ok) o.m = L.m0;
+    const bool ok = L.idle || L.t == L.T;
+    o.ok = ok && !ns.broken;
+    if (!ok) o.m = L.m0;
     return o;
 }
 
@@ -1080,8 +1130,13 @@ __device__ __forceinline__ SolveOut llgs_solve(const V3& m0, double J, double T,
     llgs_lane_begin<THERMAL, RECORD, AXIS_Z>(L, out_m, m0, J, T, k, beta, betap, rtol, atol, max_step, rk, rec, ek, ns, enabled);
     // SharedNormals: the prologue's two RHS calls were chunk 0; every attempt is one further chunk and the loop is
     // wave-uniform (a finished lane idles until the wavefront's last lane is through)
+    LlgsMasks M = llgs_masks_open(L);
+    atol = vgpr_const(atol);        // (read next to rtol in one instruction, which takes a single scalar operand: no copy per attempt)
+    // the attempt budget as the loop's own bound: whoever is still active when it runs out has failed (t != T: llgs_lane_finish)
+    const int32_t budget = (int32_t)max_attempts;
+    int32_t it = 0;
     bool wave_go = true;
-    if (NSRC::kShared) wave_go = ns.chunk_end(L.active);
+    if (NSRC::kShared) wave_go = ns.chunk_end_wave(M.active != 0ull);
     if (wave_go)
     for (;;) {
       // The loop is wave-uniform and its body has no lane-divergent control flow (see llgs_lane_attempt).  (The
@@ -1091,11 +1146,15 @@ __device__ __forceinline__ SolveOut llgs_solve(const V3& m0, double J, double T,
       // under the step-size bookkeeping)
       V3 z2 = zero, z3 = zero;
       if (THERMAL && NSRC::kShared) { z2 = llgs_draw<THERMAL>(ns, k, true); z3 = llgs_draw<THERMAL>(ns, k, false); }
-      llgs_lane_gate(L, max_attempts);
-      if (!NSRC::kShared && __ballot(L.active) == 0ull) break;
-      llgs_lane_attempt<THERMAL, RECORD, AXIS_Z>(L, out_m, k, tb, rtol, atol, max_step, rec, ek, ns, z2, z3);
-      if (NSRC::kShared && !ns.chunk_end(L.active)) break;
+      llgs_lane_gate<true>(L, M, budget);
+      if (!NSRC::kShared && M.active == 0ull) break;
+      llgs_lane_attempt<THERMAL, RECORD, AXIS_Z, true>(L, M, it, out_m, k, tb, rtol, atol, max_step, rec, ek, ns, z2, z3);
+      ++it;
+      const bool go = it < budget;
+      if (NSRC::kShared) { if (!ns.chunk_end_wave(go && M.active != 0ull)) break; }
+      else if (!go) break;
     }
+    llgs_masks_close(L, M);
     return llgs_lane_finish<RECORD>(L, out_m, rec, ek, ns);
 }
 
