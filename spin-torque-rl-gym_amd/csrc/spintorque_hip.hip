@@ -9,8 +9,8 @@
 // One lane per env; the step kernel's workgroups hold one integrating wavefront (launches below 65 536 envs: small
 // batches spread over as many CUs as they have wavefronts) or four (one per SIMD of a CU), plus, in the wave-specialised
 // thermal form, one producer wavefront each; the hot loops live entirely in registers.  With one device class the
-// constants are read through scalar loads (SGPRs); with several (or per-env parameters) each lane reads its row of
-// derived constants from LDS.
+// constants are read through scalar loads (SGPRs); with several each lane reads its row of derived constants from LDS;
+// with per-env parameters each lane derives its constants from its env's record into registers (step kernel, MULTI == 2).
 #include "stg_kernels.hpp"
 
 #include <cmath>
@@ -28,7 +28,7 @@ __global__ void __launch_bounds__(64) stg_solve_kernel(const SolveArgs a) {
     __shared__ double s_tab[MULTI ? STG_MAX_CLASSES * C_COUNT : 1];
     const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const bool in_range = i < a.N;
-    const double* row = class_row<MULTI>(a.ctab, a.cls, a.ncls, i, in_range, s_tab, EnvParams{}, a.N);
+    const double* row = class_row<MULTI>(a.ctab, a.cls, a.ncls, i, in_range, s_tab, EnvParams{});
     if (!in_range) return;
     const int64_t N = a.N;
     const V3 m0{a.m0[i], a.m0[N + i], a.m0[2 * N + i]};
@@ -63,7 +63,7 @@ __global__ void __launch_bounds__(64) stg_reset_kernel(const ResetArgs a) {
     __shared__ double s_tab[STG_MAX_CLASSES * C_COUNT];
     const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const bool in_range = i < a.N;
-    const double* row = (a.ncls > 1 || a.ep.soa) ? class_row<true>(a.ctab, a.cls, a.ncls, i, in_range, s_tab, a.ep, a.N, a.ep.layout) : a.ctab;
+    const double* row = (a.ncls > 1 || a.ep.rec) ? class_row<true>(a.ctab, a.cls, a.ncls, i, in_range, s_tab, a.ep, a.ep.layout) : a.ctab;
     if (!in_range) return;
     const int64_t N = a.N;
     V3 m0, t0;
@@ -349,25 +349,6 @@ static int fail(int code, const std::string& msg) {
             return fail(STG_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                  \
     } while (0)
 
-// automatic lane refill of the RK45 step (stg_step_refill_kernel: persistent wavefronts sharing one global queue; measured on 81 921 ...
-// 1 048 576 envs, profiles/r04_refill_global_ab.txt): 1024 wavefronts -- one per SIMD -- while that leaves at most 8 envs per lane (up
-// to 524 288 envs), 2048 beyond.  From 131 073 envs at T = 0 K (up to there the one-env-per-lane launch with its two wavefronts per SIMD
-// is as fast: 131 072 envs 1.96 against 1.94 ms, 98 304 envs 1.81 against 1.87) and from 98 305 envs with the thermal field (just
-// above the hybrid wave-specialised launch: 98 304 envs hybrid 2.81 against 2.90 ms, 106 496 envs 3.08 against 2.93; up to 131 072 envs
-// 3.1-3.2 -> 2.9-3.0 ms against one env per lane: there the launch is bound by its longest env at the inline-normal loop's
-// lone-wavefront speed either way).  Attempts between refill points: 32 (16 with 2048 wavefronts).
-constexpr int64_t STG_REFILL_AUTO_ENVS = 131073, STG_REFILL_AUTO_ENVS_THERMAL = 98305;
-constexpr int32_t STG_REFILL_CHECK_DEFAULT = 32;
-static inline void refill_auto(int64_t n, bool thermal, int& r, int64_t& nw) {
-    r = 0; nw = 0;
-    if (n < (thermal ? STG_REFILL_AUTO_ENVS_THERMAL : STG_REFILL_AUTO_ENVS)) return;
-    const int64_t nblk = ((n + TILE_ENVS - 1) / TILE_ENVS) * TILE_WAVES;      // blocks of whole tiles (a ragged tile's empty blocks included)
-    nw = 1024;
-    int64_t rr = (nblk + nw - 1) / nw;
-    if (rr > 8) { nw = 2048; rr = (nblk + nw - 1) / nw; }
-    r = (int)(rr < 2 ? 2 : (rr > 0x7FFFFFFF ? 0x7FFFFFFF : rr));              // (envs per lane on average; only != 0 matters to the launch)
-}
-
 struct stg_ctx {
     int device;
     int64_t N, env_id0;
@@ -397,7 +378,7 @@ struct stg_ctx {
 
 static EnvParams env_params_of(const stg_ctx* ctx) {
     EnvParams e{};
-    if (ctx->per_env) e.soa = ctx->env_soa;
+    if (ctx->per_env) e.rec = ctx->env_soa;
     e.layout = ctx->env_layout;
     e.gamma = ctx->cfg.gamma; e.temperature = ctx->cfg.temperature;
     return e;
@@ -525,8 +506,6 @@ int stg_set_params(stg_ctx* ctx, const stg_device_params* table, int32_t n_class
     return STG_OK;
 }
 
-// axis flags of a per-env parameter block: flag[0] = some env's easy axis is not exactly +z after normalisation,
-// flag[1] = some env's raw axis or demag factors have x/y components (LLGS specialisation)
 // rows of the caller's structure of arrays -> the library's per-env records (once per stg_set_params_per_env)
 __global__ void stg_env_pack_kernel(const double* soa, const uint8_t* type, const uint8_t* valid, int64_t N, double* rec, int layout) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -544,6 +523,8 @@ __global__ void stg_env_pack_kernel(const double* soa, const uint8_t* type, cons
     if (layout == ENV_LAYOUT_DEV) for (int k = 0; k < 8; ++k) r[16 + k] = soa[(int64_t)dev[k] * N + i];
 }
 
+// axis flags of a per-env parameter block: flag[0] = some env's easy axis is not exactly +z after normalisation,
+// flag[1] = some env's raw axis or demag factors have x/y components (LLGS specialisation)
 __global__ void stg_env_axis_kernel(const double* soa, int64_t N, int32_t* flag) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
@@ -603,10 +584,6 @@ int stg_thermal_strength(stg_ctx* ctx, int32_t cls, double* out) {
     return STG_OK;
 }
 
-// largest launch the automatic wave specialisation applies to: one integrating wavefront per SIMD (256 CUs x 4 SIMDs x
-// 64 lanes); beyond that the launch is throughput-bound and the rendezvous costs more than it gives
-constexpr int64_t STG_WAVE_SPEC_MAX_ENVS = 65536;
-
 static inline dim3 grid_for(int64_t N) { return dim3((unsigned)((N + 63) / 64)); }
 
 int stg_reset(stg_ctx* ctx, const uint8_t* mask, const double* init_m, const double* target, uint64_t seed,
@@ -625,116 +602,6 @@ int stg_reset(stg_ctx* ctx, const uint8_t* mask, const double* init_m, const dou
     HIP_TRY(hipGetLastError());
     ctx->have_state = true;
     return STG_OK;
-}
-
-int stg_step_many(stg_ctx* ctx, int32_t K, const void* actions, int32_t act_f64, int32_t out_every, int32_t autoreset,
-                  float* obs, float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated,
-                  uint8_t* truncated, uint8_t* status, void* stream) {
-    if (!ctx) return fail(STG_E_INVALID, "ctx is NULL");
-    if (!ctx->have_params || !ctx->have_state) return fail(STG_E_STATE, "stg_set_params and stg_reset must precede stg_step");
-    if (K < 1) return fail(STG_E_INVALID, "K must be >= 1");
-    const bool records = ctx->cfg.out_layout == STG_OUT_RECORDS;
-    if (!actions || !obs) return fail(STG_E_INVALID, "actions/obs must not be NULL");
-    if (!records && (!reward || !terminated || !truncated)) return fail(STG_E_INVALID, "reward/terminated/truncated must not be NULL (cfg.out_layout = STG_OUT_SOA)");
-    if (records && ((uintptr_t)obs & 7u)) return fail(STG_E_INVALID, "the record array must be 8-byte aligned");
-    if (records && ((uintptr_t)final_obs & 7u)) return fail(STG_E_INVALID, "final_obs must be 8-byte aligned (cfg.out_layout = STG_OUT_RECORDS)");
-    HIP_TRY(hipSetDevice(ctx->device));
-    StepArgs a{};
-    a.s = ctx->s; a.c = cfg_view(ctx->cfg); a.N = ctx->N; a.env_id0 = ctx->env_id0;
-    a.ctab = ctx->ctab; a.cls = ctx->cls; a.ncls = ctx->ncls; a.ep = env_params_of(ctx);
-    a.counters = ctx->counters;
-    a.placement = ctx->placement + (size_t)(ctx->launch_seq % PLACEMENT_RING) * PLACEMENT_WORDS;
-    ctx->launch_seq += 1;
-    hipStream_t st = (hipStream_t)stream;
-    a.perm = nullptr;
-    // lane_sort: 0 = automatic (on: the single LDS-only plan kernel costs ~5 us and the sorted schedule is never slower
-    // once there is more than one wavefront), 1 = always, -1 = never (identity schedule)
-    const bool want_sort = ctx->cfg.lane_sort >= 0;
-    if (want_sort && ctx->N > 64) {
-        if (ctx->N > 0xFFFFFFFFll) return fail(STG_E_INVALID, "lane sort supports up to 2^32 envs per context");
-        PlanArgs pa{};
-        pa.actions = actions; pa.act_f64 = act_f64; pa.N = ctx->N;
-        pa.max_current = ctx->cfg.max_current; pa.max_duration = ctx->cfg.max_duration;
-        pa.state = ctx->s.rec; pa.skip_done = (ctx->cfg.skip_done && !autoreset) ? 1 : 0;
-        pa.perm = ctx->perm; pa.act_sorted = ctx->act_sorted;
-        pa.cls = ctx->cls; pa.ctab = ctx->ctab;
-        pa.env_type = ctx->per_env ? ctx->env_type : nullptr;
-        pa.by_kind = (ctx->cfg.torque_model == 1 && ((ctx->ncls > 1 && ctx->cls) || ctx->per_env)) ? 1 : 0;
-        // device-physics model with a class table: kind-pure groups of four blocks (= whole workgroups of the step launch), dealt by the
-        // estimated cost of their longest block (round 4, profiles/r04_devphys_order_ab.txt: 1.08-1.37x at 98 304 ... 1 048 576 envs;
-        // 65 537 ... 98 303 envs not measured; there the rounds 2-3 grouping, keyed by a group's first env, lost to kind-major at 70 000
-        // envs: 0.39 -> 0.60 ms).  Per-env parameter records keep the kind-major order, measured ahead when their launches were
-        // one-wavefront workgroups (see stg_plan_tile_kernel) and not re-measured since they use 4-wavefront ones from 65 536 envs on.
-        pa.regroup = (pa.by_kind && !ctx->per_env) ? 1 : 0;
-        const dim3 g((unsigned)((ctx->N + TILE_ENVS - 1) / TILE_ENVS));
-        hipLaunchKernelGGL(stg_plan_tile_kernel<false>, g, dim3(PLAN_THREADS), 0, st, pa);
-        a.perm = ctx->perm;
-        a.act_sorted = ctx->act_sorted;
-    }
-    a.actions = actions; a.K = K; a.out_every = out_every ? 1 : 0; a.autoreset = autoreset ? 1 : 0;
-    a.records = records ? 1 : 0;
-    a.obs = obs; a.final_obs = final_obs; a.reward = reward; a.reward64 = reward_f64; a.energy = energy; a.term = terminated; a.trunc = truncated; a.status = status;
-    // the Simple solver only draws a thermal field when temperature > 0 (simple_solver.py:321,378)
-    const bool thermal = ctx->cfg.thermal && ctx->cfg.temperature > 0;
-    const int multi = ctx->per_env ? 2 : (ctx->ncls > 1 ? 1 : 0);      // (2: every lane derives its constants from its env's record, in registers)
-    const bool devphys = ctx->cfg.torque_model == 1;
-    // wave_spec: 0 = automatic (thermal launches of at most STG_WAVE_SPEC_MAX_ENVS envs, i.e. latency-bound ones),
-    // 1 = always, -1 = never.  Results do not depend on it.
-    bool pc = ctx->cfg.wave_spec > 0 || (ctx->cfg.wave_spec == 0 && ctx->N <= STG_WAVE_SPEC_MAX_ENVS);
-    // hybrid (RK45 / RK4 + thermal, sorted schedule, 65 536 < N <= 131 072, automatic mode): 1024 two-wavefront workgroups -- producer /
-    // consumer pairs for the 2048 - nblk longest blocks, two blocks with inline normals in each of the others (stg_kernels.hpp:
-    // stg_hybrid_block)
-    a.hybrid = 0;
-    if ((ctx->cfg.solver == STG_SOLVER_RK45 || (ctx->cfg.solver == STG_SOLVER_RK4 && thermal && !devphys)) &&
-        ctx->cfg.thermal && ctx->cfg.wave_spec == 0 && a.perm && !ctx->per_env &&
-        ctx->N > STG_WAVE_SPEC_MAX_ENVS) {
-        const int64_t nblk = ((ctx->N + TILE_ENVS - 1) / TILE_ENVS) * TILE_WAVES;      // blocks of whole tiles
-        // (a) up to 131 072 envs: pairs for the 2048 - nblk longest blocks, two fixed blocks in each other workgroup -- measured
-        // (profiles/r04_hybrid_range_ab.txt) ahead of the alternatives down to 512 pairs (RK45, 98 304 envs) / 640 pairs (RK4, 90 112 envs)
-        const int64_t n_pair = 2048 - nblk;
-        const int64_t min_pairs = ctx->cfg.solver == STG_SOLVER_RK45 ? 512 : 640;
-        if (ctx->N <= 2 * STG_WAVE_SPEC_MAX_ENVS && n_pair >= min_pairs) { pc = true; a.hybrid = (int32_t)n_pair + 1; }
-    }
-    // lane refill (RK45 throughput launches, see stg_step_refill_kernel).  cfg.lane_refill: 0 = automatic, -1 never, >= 2 forced
-    a.refill = 0; a.refill_check = STG_REFILL_CHECK_DEFAULT; a.refill_nw = 0;
-    if (ctx->cfg.solver == STG_SOLVER_RK45 && K == 1 && !ctx->per_env) {
-        const int64_t nblk = ((ctx->N + TILE_ENVS - 1) / TILE_ENVS) * TILE_WAVES;
-        int r = 0, chk = STG_REFILL_CHECK_DEFAULT;
-        int64_t nw = 0;
-        if (ctx->cfg.lane_refill == 0) {
-            refill_auto(ctx->N, ctx->cfg.thermal != 0, r, nw);
-            // (two wavefronts per SIMD: a refill point every 16 attempts -- 1 048 576 envs 13.3 against 13.6 ms; with one per SIMD 16 ... 64
-            // are alike, 8 and 128 worse)
-            if (nw >= 2048) chk = 16;
-        }
-        else if (ctx->cfg.lane_refill > 0) { r = ctx->cfg.lane_refill; nw = (nblk + r - 1) / r; }
-        // (not combined with the wave-specialised launch: a forced wave_spec = 1 keeps the one-env-per-lane kernel)
-        if (r >= 2 && nw >= 1 && !(ctx->cfg.thermal && ctx->cfg.wave_spec > 0)) {
-            if (nw > 0x7FFFFFFFll) return fail(STG_E_INVALID, "lane refill: too many wavefronts");
-            a.refill = r; a.refill_check = chk; a.refill_nw = (int32_t)nw;
-            // two cursors alternate: this launch finds its own at 0 (zeroed by the previous refill launch, or by stg_create) and
-            // zeroes the next one's -- launches of a context are ordered on their stream
-            a.refill_cursor = ctx->refill_cursor + (ctx->refill_seq & 1) * (REFILL_STRIPES * REFILL_CURSOR_STRIDE);
-            a.refill_cursor_next = ctx->refill_cursor + ((ctx->refill_seq + 1) & 1) * (REFILL_STRIPES * REFILL_CURSOR_STRIDE);
-            ctx->refill_seq += 1;
-            stg_dispatch_step_rk45_refill(a, ctx->cfg.thermal != 0, multi != 0, ctx->axis_z_llgs, act_f64, st);
-            HIP_TRY(hipGetLastError());
-            return STG_OK;
-        }
-    }
-    switch (ctx->cfg.solver) {
-        case STG_SOLVER_RK4: stg_dispatch_step_rk4(a, thermal, multi, ctx->axis_z, devphys, act_f64, pc, st); break;
-        case STG_SOLVER_EULER: stg_dispatch_step_euler(a, thermal, multi, ctx->axis_z, devphys, act_f64, pc, st); break;
-        default: stg_dispatch_step_rk45(a, ctx->cfg.thermal != 0, multi, ctx->axis_z_llgs, act_f64, pc, st); break;
-    }
-    HIP_TRY(hipGetLastError());
-    return STG_OK;
-}
-
-int stg_step(stg_ctx* ctx, const void* actions, int32_t act_f64, float* obs, float* reward, double* reward_f64,
-             double* energy, uint8_t* terminated, uint8_t* truncated, uint8_t* status, void* stream) {
-    return stg_step_many(ctx, 1, actions, act_f64, 1, 0, obs, nullptr, reward, reward_f64, energy, terminated, truncated,
-                         status, stream);
 }
 
 // stg_step_ids's workspace (caller-owned, one per launch in flight): slot -> list position, the slot-order actions, the refill launch's
@@ -760,100 +627,121 @@ static IdsWorkspace ids_workspace(void* base, int64_t M) {
     return w;
 }
 
+// the output pointers of a step launch: the NULL / alignment rules of the context's output layout, then into the kernel's arguments
+static int step_outputs(const stg_ctx* ctx, StepArgs& a, float* obs, float* final_obs, float* reward, double* reward_f64, double* energy,
+                        uint8_t* terminated, uint8_t* truncated, uint8_t* status) {
+    const bool records = ctx->cfg.out_layout == STG_OUT_RECORDS;
+    if (!records && (!reward || !terminated || !truncated)) return fail(STG_E_INVALID, "reward/terminated/truncated must not be NULL (cfg.out_layout = STG_OUT_SOA)");
+    if (records && ((uintptr_t)obs & 7u)) return fail(STG_E_INVALID, "the record array must be 8-byte aligned");
+    if (records && ((uintptr_t)final_obs & 7u)) return fail(STG_E_INVALID, "final_obs must be 8-byte aligned (cfg.out_layout = STG_OUT_RECORDS)");
+    a.records = records ? 1 : 0;
+    a.obs = obs; a.final_obs = final_obs; a.reward = reward; a.reward64 = reward_f64; a.energy = energy; a.term = terminated; a.trunc = truncated; a.status = status;
+    return STG_OK;
+}
+
+// Enqueues one step launch.  `a` arrives with what the entry point decides (N = the launch's slots, K, out_every, autoreset, actions,
+// outputs, ids / n_state); the rest comes from the context and from the launch plan (stg_launch_plan.hpp).  ws: the workspace of an
+// id launch, nullptr for the full step, which uses the context's own buffers.
+static int enqueue_step(stg_ctx* ctx, StepArgs& a, int32_t act_f64, const IdsWorkspace* ws, hipStream_t st) {
+    a.s = ctx->s; a.c = cfg_view(ctx->cfg); a.env_id0 = ctx->env_id0;
+    a.ctab = ctx->ctab; a.cls = ctx->cls; a.ncls = ctx->ncls; a.ep = env_params_of(ctx);
+    a.counters = ctx->counters;
+    a.placement = ctx->placement + (size_t)(ctx->launch_seq % PLACEMENT_RING) * PLACEMENT_WORDS;
+    ctx->launch_seq += 1;
+    StepPlan p;
+    const char* err = "";
+    if (int rc = plan_step(ctx->cfg, a.N, a.K, a.autoreset != 0, ws != nullptr, ctx->per_env, ctx->ncls, ctx->cls != nullptr, &p, &err)) return fail(rc, err);
+    if (p.sort) {
+        PlanArgs pa{};
+        pa.actions = a.actions; pa.act_f64 = act_f64; pa.N = a.N; pa.ids = a.ids; pa.n_state = a.n_state;
+        pa.max_current = ctx->cfg.max_current; pa.max_duration = ctx->cfg.max_duration;
+        pa.state = ctx->s.rec; pa.skip_done = p.skip_done;
+        pa.perm = ws ? ws->perm : ctx->perm; pa.act_sorted = ws ? ws->act_sorted : ctx->act_sorted;
+        pa.cls = ctx->cls; pa.ctab = ctx->ctab;
+        pa.env_type = ctx->per_env ? ctx->env_type : nullptr;
+        pa.by_kind = p.by_kind; pa.regroup = p.regroup;
+        const dim3 g((unsigned)((a.N + TILE_ENVS - 1) / TILE_ENVS));
+        with_flag(ws != nullptr, [&](auto IDS) { hipLaunchKernelGGL(stg_plan_tile_kernel<IDS.value>, g, dim3(PLAN_THREADS), 0, st, pa); });
+        a.perm = pa.perm;
+        a.act_sorted = pa.act_sorted;
+    }
+    a.hybrid = p.hybrid;
+    a.refill = p.refill; a.refill_check = p.refill_check; a.refill_nw = p.refill_nw;
+    if (p.refill) {
+        if (ws) {
+            // the launch's own cursors, zeroed on its stream (no context-owned cursor: launches on other streams may overlap, and a captured
+            // graph replays the memset with the kernel)
+            HIP_TRY(hipMemsetAsync(ws->cursor, 0, ws->cursor_bytes, st));
+            a.refill_cursor = ws->cursor;
+            a.refill_cursor_next = ws->cursor_next;
+        } else {
+            // two cursors alternate: this launch finds its own at 0 (zeroed by the previous refill launch, or by stg_create) and
+            // zeroes the next one's -- launches of a context are ordered on their stream
+            a.refill_cursor = ctx->refill_cursor + (ctx->refill_seq & 1) * (REFILL_STRIPES * REFILL_CURSOR_STRIDE);
+            a.refill_cursor_next = ctx->refill_cursor + ((ctx->refill_seq + 1) & 1) * (REFILL_STRIPES * REFILL_CURSOR_STRIDE);
+            ctx->refill_seq += 1;
+        }
+        stg_dispatch_step_rk45_refill(a, p.thermal, p.multi != 0, ctx->axis_z_llgs, act_f64, st);
+    } else {
+        switch (ctx->cfg.solver) {
+            case STG_SOLVER_RK4: stg_dispatch_step_rk4(a, p.thermal, p.multi, ctx->axis_z, p.devphys, act_f64, p.pc, st); break;
+            case STG_SOLVER_EULER: stg_dispatch_step_euler(a, p.thermal, p.multi, ctx->axis_z, p.devphys, act_f64, p.pc, st); break;
+            default: stg_dispatch_step_rk45(a, p.thermal, p.multi, ctx->axis_z_llgs, act_f64, p.pc, st); break;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return STG_OK;
+}
+
+int stg_step_many(stg_ctx* ctx, int32_t K, const void* actions, int32_t act_f64, int32_t out_every, int32_t autoreset,
+                  float* obs, float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated,
+                  uint8_t* truncated, uint8_t* status, void* stream) {
+    if (!ctx) return fail(STG_E_INVALID, "ctx is NULL");
+    if (!ctx->have_params || !ctx->have_state) return fail(STG_E_STATE, "stg_set_params and stg_reset must precede stg_step");
+    if (K < 1) return fail(STG_E_INVALID, "K must be >= 1");
+    if (!actions || !obs) return fail(STG_E_INVALID, "actions/obs must not be NULL");
+    StepArgs a{};
+    if (int rc = step_outputs(ctx, a, obs, final_obs, reward, reward_f64, energy, terminated, truncated, status)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    a.N = ctx->N; a.actions = actions; a.K = K; a.out_every = out_every ? 1 : 0; a.autoreset = autoreset ? 1 : 0;
+    return enqueue_step(ctx, a, act_f64, nullptr, (hipStream_t)stream);
+}
+
+int stg_step(stg_ctx* ctx, const void* actions, int32_t act_f64, float* obs, float* reward, double* reward_f64,
+             double* energy, uint8_t* terminated, uint8_t* truncated, uint8_t* status, void* stream) {
+    return stg_step_many(ctx, 1, actions, act_f64, 1, 0, obs, nullptr, reward, reward_f64, energy, terminated, truncated,
+                         status, stream);
+}
+
 size_t stg_step_ids_workspace_bytes(const stg_ctx* ctx, int64_t M) {
     if (!ctx || M < 1) return 0;
     return ids_workspace(nullptr, M).bytes;
 }
 
+// One env-step of the M envs env_ids: the schedule is decided by M as stg_step_many decides it by N (results do not depend on it)
 int stg_step_ids(stg_ctx* ctx, int64_t M, const uint32_t* env_ids, const void* actions, int32_t act_f64, int32_t autoreset,
                  void* workspace, float* obs, float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated,
                  uint8_t* truncated, uint8_t* status, void* stream) {
     if (!ctx) return fail(STG_E_INVALID, "ctx is NULL");
     if (!ctx->have_params || !ctx->have_state) return fail(STG_E_STATE, "stg_set_params and stg_reset must precede stg_step_ids");
     if (M < 1 || M > 0xFFFFFFFFll) return fail(STG_E_INVALID, "M must be in [1, 2^32)");
-    const bool records = ctx->cfg.out_layout == STG_OUT_RECORDS;
     if (!env_ids || !actions || !obs || !workspace) return fail(STG_E_INVALID, "env_ids/actions/obs/workspace must not be NULL");
     if ((uintptr_t)workspace & 15u) return fail(STG_E_INVALID, "the workspace must be 16-byte aligned");
-    if (!records && (!reward || !terminated || !truncated)) return fail(STG_E_INVALID, "reward/terminated/truncated must not be NULL (cfg.out_layout = STG_OUT_SOA)");
-    if (records && ((uintptr_t)obs & 7u)) return fail(STG_E_INVALID, "the record array must be 8-byte aligned");
-    if (records && ((uintptr_t)final_obs & 7u)) return fail(STG_E_INVALID, "final_obs must be 8-byte aligned (cfg.out_layout = STG_OUT_RECORDS)");
+    StepArgs a{};
+    if (int rc = step_outputs(ctx, a, obs, final_obs, reward, reward_f64, energy, terminated, truncated, status)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     const IdsWorkspace ws = ids_workspace(workspace, M);
-    hipStream_t st = (hipStream_t)stream;
-    StepArgs a{};
-    a.s = ctx->s; a.c = cfg_view(ctx->cfg); a.N = M; a.env_id0 = ctx->env_id0;
-    a.ids = env_ids; a.n_state = ctx->N;
-    a.ctab = ctx->ctab; a.cls = ctx->cls; a.ncls = ctx->ncls; a.ep = env_params_of(ctx);
-    a.counters = ctx->counters;
-    a.placement = ctx->placement + (size_t)(ctx->launch_seq % PLACEMENT_RING) * PLACEMENT_WORDS;
-    ctx->launch_seq += 1;
-    a.perm = nullptr;
-    // schedules decided by M, as stg_step_many decides them by N (results do not depend on them): the sorted schedule above one wavefront
-    if (ctx->cfg.lane_sort >= 0 && M > 64) {
-        PlanArgs pa{};
-        pa.actions = actions; pa.act_f64 = act_f64; pa.N = M; pa.ids = env_ids; pa.n_state = ctx->N;
-        pa.max_current = ctx->cfg.max_current; pa.max_duration = ctx->cfg.max_duration;
-        pa.state = ctx->s.rec; pa.skip_done = (ctx->cfg.skip_done && !autoreset) ? 1 : 0;
-        pa.perm = ws.perm; pa.act_sorted = ws.act_sorted;
-        pa.cls = ctx->cls; pa.ctab = ctx->ctab;
-        pa.env_type = ctx->per_env ? ctx->env_type : nullptr;
-        pa.by_kind = (ctx->cfg.torque_model == 1 && ((ctx->ncls > 1 && ctx->cls) || ctx->per_env)) ? 1 : 0;
-        pa.regroup = (pa.by_kind && !ctx->per_env) ? 1 : 0;
-        hipLaunchKernelGGL(stg_plan_tile_kernel<true>, dim3((unsigned)((M + TILE_ENVS - 1) / TILE_ENVS)), dim3(PLAN_THREADS), 0, st, pa);
-        a.perm = ws.perm;
-        a.act_sorted = ws.act_sorted;
-    }
+    a.N = M; a.ids = env_ids; a.n_state = ctx->N;
     a.actions = actions; a.K = 1; a.out_every = 1; a.autoreset = autoreset ? 1 : 0;
-    a.records = records ? 1 : 0;
-    a.obs = obs; a.final_obs = final_obs; a.reward = reward; a.reward64 = reward_f64; a.energy = energy; a.term = terminated; a.trunc = truncated; a.status = status;
-    const bool thermal = ctx->cfg.thermal && ctx->cfg.temperature > 0;
-    const int multi = ctx->per_env ? 2 : (ctx->ncls > 1 ? 1 : 0);
-    const bool devphys = ctx->cfg.torque_model == 1;
-    const bool pc = ctx->cfg.wave_spec > 0 || (ctx->cfg.wave_spec == 0 && M <= STG_WAVE_SPEC_MAX_ENVS);
-    a.hybrid = 0;                                                      // (not measured for id launches)
-    a.refill = 0; a.refill_check = STG_REFILL_CHECK_DEFAULT; a.refill_nw = 0;
-    if (ctx->cfg.solver == STG_SOLVER_RK45 && !ctx->per_env) {
-        const int64_t nblk = ((M + TILE_ENVS - 1) / TILE_ENVS) * TILE_WAVES;
-        int r = 0, chk = STG_REFILL_CHECK_DEFAULT;
-        int64_t nw = 0;
-        if (ctx->cfg.lane_refill == 0) {
-            refill_auto(M, ctx->cfg.thermal != 0, r, nw);
-            if (nw >= 2048) chk = 16;
-        }
-        else if (ctx->cfg.lane_refill > 0) { r = ctx->cfg.lane_refill; nw = (nblk + r - 1) / r; }
-        if (r >= 2 && nw >= 1 && !(ctx->cfg.thermal && ctx->cfg.wave_spec > 0)) {
-            if (nw > 0x7FFFFFFFll) return fail(STG_E_INVALID, "lane refill: too many wavefronts");
-            a.refill = r; a.refill_check = chk; a.refill_nw = (int32_t)nw;
-            // the launch's own cursors, zeroed on its stream (no context-owned cursor: launches on other streams may overlap, and a captured
-            // graph replays the memset with the kernel)
-            HIP_TRY(hipMemsetAsync(ws.cursor, 0, ws.cursor_bytes, st));
-            a.refill_cursor = ws.cursor;
-            a.refill_cursor_next = ws.cursor_next;
-            stg_dispatch_step_rk45_refill(a, ctx->cfg.thermal != 0, multi != 0, ctx->axis_z_llgs, act_f64, st);
-            HIP_TRY(hipGetLastError());
-            return STG_OK;
-        }
-    }
-    switch (ctx->cfg.solver) {
-        case STG_SOLVER_RK4: stg_dispatch_step_rk4(a, thermal, multi, ctx->axis_z, devphys, act_f64, pc, st); break;
-        case STG_SOLVER_EULER: stg_dispatch_step_euler(a, thermal, multi, ctx->axis_z, devphys, act_f64, pc, st); break;
-        default: stg_dispatch_step_rk45(a, ctx->cfg.thermal != 0, multi, ctx->axis_z_llgs, act_f64, pc, st); break;
-    }
-    HIP_TRY(hipGetLastError());
-    return STG_OK;
+    return enqueue_step(ctx, a, act_f64, &ws, (hipStream_t)stream);
 }
 
 extern "C++" {
-template <int SOLVER, bool RECORD>
-static void dispatch_solve(const SolveArgs& a, bool thermal, bool multi, hipStream_t st) {
-    const dim3 g = grid_for(a.N), b(64);
-    if (thermal) {
-        if (multi) hipLaunchKernelGGL((stg_solve_kernel<SOLVER, true, true, RECORD>), g, b, 0, st, a);
-        else hipLaunchKernelGGL((stg_solve_kernel<SOLVER, true, false, RECORD>), g, b, 0, st, a);
-    } else {
-        if (multi) hipLaunchKernelGGL((stg_solve_kernel<SOLVER, false, true, RECORD>), g, b, 0, st, a);
-        else hipLaunchKernelGGL((stg_solve_kernel<SOLVER, false, false, RECORD>), g, b, 0, st, a);
-    }
+template <int SOLVER>
+static void dispatch_solve(const SolveArgs& a, bool thermal, bool multi, bool record, hipStream_t st) {
+    with_flag(thermal, [&](auto THERMAL) { with_flag(multi, [&](auto MULTI) { with_flag(record, [&](auto RECORD) {
+        hipLaunchKernelGGL((stg_solve_kernel<SOLVER, THERMAL.value, MULTI.value, RECORD.value>), grid_for(a.N), dim3(64), 0, st, a);
+    }); }); });
 }
 }  // extern "C++"
 
@@ -875,15 +763,9 @@ static int solve_common(stg_ctx* ctx, const double* m0, const double* J, const d
     hipStream_t st = (hipStream_t)stream;
     const bool th_simple = ctx->cfg.thermal && ctx->cfg.temperature > 0, th_llgs = ctx->cfg.thermal != 0;
     switch (ctx->cfg.solver) {
-        case STG_SOLVER_RK4:
-            if (record) dispatch_solve<STG_SOLVER_RK4, true>(a, th_simple, multi, st); else dispatch_solve<STG_SOLVER_RK4, false>(a, th_simple, multi, st);
-            break;
-        case STG_SOLVER_EULER:
-            if (record) dispatch_solve<STG_SOLVER_EULER, true>(a, th_simple, multi, st); else dispatch_solve<STG_SOLVER_EULER, false>(a, th_simple, multi, st);
-            break;
-        default:
-            if (record) dispatch_solve<STG_SOLVER_RK45, true>(a, th_llgs, multi, st); else dispatch_solve<STG_SOLVER_RK45, false>(a, th_llgs, multi, st);
-            break;
+        case STG_SOLVER_RK4: dispatch_solve<STG_SOLVER_RK4>(a, th_simple, multi, record, st); break;
+        case STG_SOLVER_EULER: dispatch_solve<STG_SOLVER_EULER>(a, th_simple, multi, record, st); break;
+        default: dispatch_solve<STG_SOLVER_RK45>(a, th_llgs, multi, record, st); break;
     }
     HIP_TRY(hipGetLastError());
     return STG_OK;

@@ -4,6 +4,7 @@
 // spintorque_hip.hip holds the C-ABI, the other kernels and the host logic.
 #pragma once
 #include "../../include/spintorque_hip.h"
+#include "stg_launch_plan.hpp"
 #include "stg_physics.hpp"
 
 #include <hip/hip_runtime.h>
@@ -58,7 +59,7 @@ struct CfgView {
 enum : int { ENV_LAYOUT_CORE = 0, ENV_LAYOUT_LLGS = 1, ENV_LAYOUT_DEV = 2 };
 __host__ __device__ constexpr int env_layout_doubles(int layout) { return layout == ENV_LAYOUT_CORE ? 16 : (layout == ENV_LAYOUT_LLGS ? 20 : 24); }
 struct EnvParams {
-    const double* soa;        // records [N][env_layout_doubles(layout)] or nullptr (the name is historical: "per-env parameters present")
+    const double* rec;        // records [N][env_layout_doubles(layout)], or nullptr: no per-env parameters (class table)
     double gamma, temperature;
     int32_t layout;           // ENV_LAYOUT_* the records were packed in (= what the context's solver / torque model select)
 };
@@ -70,7 +71,7 @@ struct StepArgs {
     const double* ctab;
     const uint8_t* cls;
     int32_t ncls;
-    EnvParams ep;                 // per-env parameters (soa == nullptr: class table)
+    EnvParams ep;                 // per-env parameters (rec == nullptr: class table)
     const void* actions;          // [K][2][N]
     int32_t K, out_every, autoreset;
     int32_t snake_rounds;         // sorted schedule: leading rounds of workgroups dealt in boustrophedon order, 0 = none (stg_slot_block)
@@ -145,7 +146,7 @@ template <int LAYOUT>
 __device__ __forceinline__ void load_env_params(const EnvParams& e, int64_t i, stg_device_params& p) {
     constexpr int ND = env_layout_doubles(LAYOUT);
     double q[ND];
-    const double2* src = reinterpret_cast<const double2*>(e.soa + i * ND);
+    const double2* src = reinterpret_cast<const double2*>(e.rec + i * ND);
 #pragma unroll
     for (int k = 0; k < ND / 2; ++k) { const double2 v = src[k]; q[2 * k] = v.x; q[2 * k + 1] = v.y; }
     p.damping = q[0]; p.ms = q[1]; p.ku = q[2]; p.volume = q[3]; p.polarization = q[4];
@@ -179,9 +180,9 @@ __device__ __forceinline__ void load_env_params(const EnvParams& e, int64_t i, s
 // context's value in the reset kernel.
 template <bool MULTI>
 __device__ __forceinline__ const double* class_row(const double* ctab, const uint8_t* cls, int32_t ncls, int64_t i,
-                                                   bool in_range, double* lds, const EnvParams& ep, int64_t N, int layout = ENV_LAYOUT_CORE) {
+                                                   bool in_range, double* lds, const EnvParams& ep, int layout = ENV_LAYOUT_CORE) {
     if (MULTI) {
-        if (ep.soa) {
+        if (ep.rec) {
             const int lane = (int)(threadIdx.x & 63u);
             if (threadIdx.x < 64 && in_range) {
                 stg_device_params p;
@@ -403,13 +404,7 @@ __device__ __forceinline__ void wave_add3(unsigned long long* dst, unsigned long
     }
 }
 
-constexpr int PLAN_DUR = 256;         // 20 ps of pulse duration per bucket at the default 5 ns maximum
-constexpr int PLAN_BUCKETS = 3 * PLAN_DUR;   // x device kind (device-physics torque model: type-uniform wavefronts)
-constexpr int PLAN_THREADS = 1024;
-constexpr int PLAN_ITEMS = 4;
-constexpr int TILE_ENVS = PLAN_THREADS * PLAN_ITEMS;   // 4096 envs sorted together (one plan workgroup)
-constexpr int TILE_WAVES = TILE_ENVS / 64;             // = 64 wavefronts of the step launch
-
+// (PLAN_*, TILE_ENVS, TILE_WAVES: stg_launch_plan.hpp)
 // Which 64-slot block of the schedule integrating wavefront `cw` of workgroup `b` takes; a workgroup holds WGW = 1 or 4
 // integrating wavefronts.
 //  * WGW = 4 (launches of at least one such workgroup per CU): the dispatcher puts the wavefronts of a 256-thread
@@ -807,10 +802,11 @@ template <int SOLVER, bool THERMAL, int MULTI, bool AXIS_Z, bool DEVPHYS, typena
 #define STG_STEP_ATTR
 #endif
 // (second bound = minimum wavefronts per SIMD: the fixed-step T = 0 K kernels with the reference RHS and the easy axis along z -- every
-// factory default -- sit at 127-129 VGPRs: one
-// register decides between three and four resident wavefronts per SIMD, so they are held to four: 127 VGPRs, no spills (cfg4 class
-// table 0.516 -> 0.505 ms, RK4 at T = 0 K 262 144 envs 0.513 -> 0.497 ms).  Not the class-table kernel with 64-thread workgroups (per-env
-// parameter records: its 23.5 KB LDS block per workgroup bounds the occupancy anyway, and the tighter allocation cost it 6 %).)
+// factory default -- sit at 127-129 VGPRs: one register decides between three and four resident wavefronts per SIMD, so they are held
+// to four: 127 VGPRs, no spills (cfg4 class table 0.516 -> 0.505 ms, RK4 at T = 0 K 262 144 envs 0.513 -> 0.497 ms).  Excluded:
+// the per-env kernels (MULTI == 2: a lane's derived constants live in registers) and the class-table kernel with 64-thread workgroups
+// -- that exclusion dates from when per-env parameters were this kernel with a 64-row LDS block, which the tighter allocation cost 6 %;
+// it has not been re-measured for the class table alone.)
 __global__ void __launch_bounds__(PC ? 2 * WGW * 64 : WGW * 64, (SOLVER != STG_SOLVER_RK45 && !THERMAL && !DEVPHYS && AXIS_Z && MULTI != 2 && !(MULTI && WGW == 1)) ? 4 : 1) STG_STEP_ATTR
 stg_step_kernel(const StepArgs a) {
     // the env-step arithmetic around the solver (energy, reward, flags) has no contraction: same roundings in every
@@ -870,7 +866,7 @@ stg_step_kernel(const StepArgs a) {
         derive_row(p, a.ep.gamma, a.ep.temperature, own_row);
         row = own_row;
     } else {
-        row = class_row<MULTI != 0>(a.ctab, a.cls, a.ncls, i, live, s_tab, a.ep, a.N, ENV_LAYOUT);
+        row = class_row<MULTI != 0>(a.ctab, a.cls, a.ncls, i, live, s_tab, a.ep, ENV_LAYOUT);
     }
     // Lanes without an env: the one-wavefront form has no rendezvous after this point and lets them go; in the
     // wave-specialised form they stay (inert) because every wavefront of the workgroup takes part in every s_barrier.
@@ -1006,6 +1002,18 @@ __global__ void __launch_bounds__(WGW * 64) stg_step_refill_kernel(const StepArg
 // ------------------------------------------------------------------------------------------------
 constexpr int64_t STG_WG4_MIN_ENVS = 65536;       // 256 CUs x 4 SIMDs x 64 lanes
 
+// run-time flag -> compile-time constant: f is a generic lambda and receives std::true_type / std::false_type (multi: 0, 1 or 2)
+template <class F>
+static inline void with_flag(bool v, F&& f) {
+    if (v) f(std::true_type{}); else f(std::false_type{});
+}
+template <class F>
+static inline void with_multi(int multi, F&& f) {
+    if (multi == 2) f(std::integral_constant<int, 2>{});
+    else if (multi) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 0>{});
+}
+
 // dynamic LDS of a launch: the class table of a MULTI kernel (see stg_step_kernel)
 template <int MULTI>
 static size_t step_dyn_lds(const StepArgs& a) {
@@ -1049,89 +1057,55 @@ static int32_t snake_rounds_of(const StepArgs& a, const void* kernel, int wgw, s
     return (n_q > 32u && nb >= 2 && n_q <= 32u * (unsigned)nb + 16u) ? nb : 0;
 }
 
-template <int SOLVER, bool THERMAL, int MULTI, bool AXIS_Z, bool DEVPHYS, int WGW, bool IDS>
-static void launch_step_w(const StepArgs& a, int act_f64, bool pc, hipStream_t st) {
-    const dim3 grid(step_grid(a, WGW));
-    const size_t lds = step_dyn_lds<MULTI>(a);
-    StepArgs b = a;
-    // (launched by name, not through a function-pointer variable: a host build with -fsanitize=address was seen to push the call
-    // configuration and then NOT launch through the pointer -- no error, no kernel; the pointer only serves the occupancy query)
-    if (act_f64) {
-        b.snake_rounds = snake_rounds_of(a, (const void*)&stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, double, false, WGW, IDS>, WGW, lds);
-        hipLaunchKernelGGL((stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, double, false, WGW, IDS>), grid, dim3(WGW * 64), lds, st, b);
-    } else {
-        b.snake_rounds = snake_rounds_of(a, (const void*)&stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, float, false, WGW, IDS>, WGW, lds);
-        hipLaunchKernelGGL((stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, float, false, WGW, IDS>), grid, dim3(WGW * 64), lds, st, b);
+// One step launch.  PC: the wave-specialised variant, one integrating + one producing wavefront per workgroup (WGW = 1); it exists
+// for the thermal kernels without the device-physics model, and that model for the fixed-step solvers only -- dispatch_step never
+// asks for another combination, and none is instantiated.
+template <int SOLVER, bool THERMAL, int MULTI, bool AXIS_Z, bool DEVPHYS, typename AT, bool PC, int WGW, bool IDS>
+static void launch_step(const StepArgs& a, hipStream_t st) {
+    if constexpr ((PC && (!THERMAL || DEVPHYS || WGW != 1)) || (DEVPHYS && SOLVER == STG_SOLVER_RK45)) return;
+    else {
+        const size_t lds = step_dyn_lds<MULTI>(a);
+        StepArgs b = a;
+        dim3 grid(step_grid(a, WGW));
+        if constexpr (PC) {
+            if (a.hybrid) grid = dim3(1024u);                         // (hybrid: always 1024 workgroups, see stg_hybrid_block)
+            // boustrophedon order over every round while the launch is at most two rounds (n_q <= 64 workgroups per XCD group), i.e.
+            // resident from the start; 32 768 < N <= 65 536 envs take the pair placement instead (stg_slot_block)
+            b.snake_rounds = (a.perm && step_grid(a, 1) / 8u <= 64u) ? 2 : 0;
+        } else {
+            b.snake_rounds = snake_rounds_of(a, (const void*)&stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, AT, PC, WGW, IDS>, WGW, lds);
+        }
+        // (launched by name, not through a function-pointer variable: a host build with -fsanitize=address was seen to push the call
+        // configuration and then NOT launch through the pointer -- no error, no kernel; the pointer only serves the occupancy query)
+        hipLaunchKernelGGL((stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, AT, PC, WGW, IDS>), grid, dim3((PC ? 2 : 1) * WGW * 64), lds, st, b);
     }
 }
 
-template <int SOLVER, bool THERMAL, int MULTI, bool AXIS_Z, bool DEVPHYS, bool IDS>
-static void launch_step(const StepArgs& a, int act_f64, bool pc, hipStream_t st) {
-    if (THERMAL && !DEVPHYS && pc) {
-        // wave-specialised variant: one integrating + one producing wavefront per workgroup; not built for the
-        // device-physics model
-        constexpr bool PC = THERMAL && !DEVPHYS;
-        const dim3 grid(a.hybrid ? 1024u : step_grid(a, 1));          // (hybrid: always 1024 workgroups, see stg_hybrid_block)
-        // boustrophedon order over every round while the launch is at most two rounds (n_q <= 64 workgroups per XCD group), i.e.
-        // resident from the start; 32 768 < N <= 65 536 envs take the pair placement instead (stg_slot_block)
-        StepArgs b = a;
-        b.snake_rounds = (a.perm && step_grid(a, 1) / 8u <= 64u) ? 2 : 0;
-        if (act_f64)
-            hipLaunchKernelGGL((stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, double, PC, 1, IDS>), grid, dim3(128), step_dyn_lds<MULTI>(a), st, b);
-        else
-            hipLaunchKernelGGL((stg_step_kernel<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, float, PC, 1, IDS>), grid, dim3(128), step_dyn_lds<MULTI>(a), st, b);
-        return;
-    }
-    // workgroups of 4 integrating wavefronts once there is one per CU, of 1 below that
-    if (a.N >= STG_WG4_MIN_ENVS) launch_step_w<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, 4, IDS>(a, act_f64, pc, st);
-    else launch_step_w<SOLVER, THERMAL, MULTI, AXIS_Z, DEVPHYS, 1, IDS>(a, act_f64, pc, st);
-}
-template <int SOLVER, bool AXIS_Z, bool DEVPHYS, bool IDS>
-static void dispatch_step2(const StepArgs& a, bool thermal, int multi, int act_f64, bool pc, hipStream_t st) {
-    if (thermal) {
-        if (multi == 2) launch_step<SOLVER, true, 2, AXIS_Z, DEVPHYS, IDS>(a, act_f64, pc, st);
-        else if (multi) launch_step<SOLVER, true, 1, AXIS_Z, DEVPHYS, IDS>(a, act_f64, pc, st);
-        else launch_step<SOLVER, true, 0, AXIS_Z, DEVPHYS, IDS>(a, act_f64, pc, st);
-    } else {
-        if (multi == 2) launch_step<SOLVER, false, 2, AXIS_Z, DEVPHYS, IDS>(a, act_f64, false, st);
-        else if (multi) launch_step<SOLVER, false, 1, AXIS_Z, DEVPHYS, IDS>(a, act_f64, false, st);
-        else launch_step<SOLVER, false, 0, AXIS_Z, DEVPHYS, IDS>(a, act_f64, false, st);
-    }
-}
 // axis_z selects the easy-axis = z specialisation of the RHS (Simple: e = +z; LLGS: raw axis and demag along z);
-// devphys the opt-in device-physics torque model (fixed-step solvers only)
+// devphys the opt-in device-physics torque model (fixed-step solvers only); pc the wave-specialised kernel (thermal, not device-physics)
 template <int SOLVER, bool IDS>
 static void dispatch_step(const StepArgs& a, bool thermal, int multi, bool axis_z, bool devphys, int act_f64, bool pc, hipStream_t st) {
-    if constexpr (SOLVER != STG_SOLVER_RK45) {          // (the device-physics torque model exists for the fixed-step solvers only)
-        if (devphys) {
-            if (axis_z) dispatch_step2<SOLVER, true, true, IDS>(a, thermal, multi, act_f64, pc, st);
-            else dispatch_step2<SOLVER, false, true, IDS>(a, thermal, multi, act_f64, pc, st);
-            return;
-        }
-    }
-    if (axis_z) dispatch_step2<SOLVER, true, false, IDS>(a, thermal, multi, act_f64, pc, st);
-    else dispatch_step2<SOLVER, false, false, IDS>(a, thermal, multi, act_f64, pc, st);
+    devphys = devphys && SOLVER != STG_SOLVER_RK45;
+    pc = pc && thermal && !devphys;
+    // workgroups of 4 integrating wavefronts once there is one per CU, of 1 below that (and in the wave-specialised form)
+    const bool wg4 = !pc && a.N >= STG_WG4_MIN_ENVS;
+    with_flag(thermal, [&](auto THERMAL) { with_multi(multi, [&](auto MULTI) { with_flag(axis_z, [&](auto AXIS_Z) {
+    with_flag(devphys, [&](auto DEVPHYS) { with_flag(act_f64 != 0, [&](auto F64) { with_flag(pc, [&](auto PC) { with_flag(wg4, [&](auto WG4) {
+        using AT = std::conditional_t<F64.value, double, float>;
+        launch_step<SOLVER, THERMAL.value, MULTI.value, AXIS_Z.value, DEVPHYS.value, AT, PC.value, WG4.value ? 4 : 1, IDS>(a, st);
+    }); }); }); }); }); }); });
 }
 
-// lane-refill launch of the RK45 step (a.refill = envs per lane >= 2): ceil(ceil(N / 64) / refill) wavefronts
-template <bool THERMAL, bool MULTI, bool AXIS_Z, bool IDS>
-static void launch_refill(const StepArgs& a, int act_f64, hipStream_t st) {
-    constexpr int WGW = 4;
-    const int64_t nw = a.refill_nw;
-    const dim3 grid((unsigned)((nw + WGW - 1) / WGW));
-    const size_t lds = MULTI ? (size_t)a.ncls * C_COUNT * sizeof(double) : 0;
-    if (act_f64) hipLaunchKernelGGL((stg_step_refill_kernel<THERMAL, MULTI, AXIS_Z, double, WGW, IDS>), grid, dim3(WGW * 64), lds, st, a);
-    else hipLaunchKernelGGL((stg_step_refill_kernel<THERMAL, MULTI, AXIS_Z, float, WGW, IDS>), grid, dim3(WGW * 64), lds, st, a);
-}
+// lane-refill launch of the RK45 step (a.refill = envs per lane >= 2): a.refill_nw wavefronts in workgroups of four
 template <bool IDS>
 static void dispatch_refill(const StepArgs& a, bool thermal, bool multi, bool axis_z, int act_f64, hipStream_t st) {
-    if (thermal) {
-        if (multi) { if (axis_z) launch_refill<true, true, true, IDS>(a, act_f64, st); else launch_refill<true, true, false, IDS>(a, act_f64, st); }
-        else { if (axis_z) launch_refill<true, false, true, IDS>(a, act_f64, st); else launch_refill<true, false, false, IDS>(a, act_f64, st); }
-    } else {
-        if (multi) { if (axis_z) launch_refill<false, true, true, IDS>(a, act_f64, st); else launch_refill<false, true, false, IDS>(a, act_f64, st); }
-        else { if (axis_z) launch_refill<false, false, true, IDS>(a, act_f64, st); else launch_refill<false, false, false, IDS>(a, act_f64, st); }
-    }
+    constexpr int WGW = 4;
+    const dim3 grid((unsigned)(((int64_t)a.refill_nw + WGW - 1) / WGW));
+    with_flag(thermal, [&](auto THERMAL) { with_flag(multi, [&](auto MULTI) { with_flag(axis_z, [&](auto AXIS_Z) { with_flag(act_f64 != 0, [&](auto F64) {
+        using AT = std::conditional_t<F64.value, double, float>;
+        hipLaunchKernelGGL((stg_step_refill_kernel<THERMAL.value, MULTI.value, AXIS_Z.value, AT, WGW, IDS>), grid, dim3(WGW * 64),
+                           step_dyn_lds<MULTI.value ? 1 : 0>(a), st, a);
+    }); }); }); });
 }
 
 // defined in stg_step_{rk4,euler,rk45}.hip

@@ -135,6 +135,16 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def alloc_final_obs(lead, m: int, device, layout: str):
+    """Terminal-observation buffer of an auto-resetting step, shape `lead` + per-step: (what the kernel writes, its [.., 12, m] view).
+    'records': env-major [.., m, 12] like the records (one 48-byte block per env) and the transposed view; else [.., 12, m] itself."""
+    if layout == "records":
+        buf = torch.zeros((*lead, m, 12), dtype=torch.float32, device=device)
+        return buf, buf.transpose(-1, -2)
+    buf = torch.zeros((*lead, 12, m), dtype=torch.float32, device=device)
+    return buf, buf
+
+
 class HipBackend:
     """Owns one stg_ctx.  All tensors are on ``cuda:<device_index>``; per-env arrays are component-major
     ([3,N], [12,N], [2,N]) as the C-ABI defines them."""
@@ -185,6 +195,14 @@ class HipBackend:
         if shape is not None and tuple(t.shape) != tuple(shape):
             raise ValueError(f"expected shape {tuple(shape)}, got {tuple(t.shape)}")
         return t
+
+    def _out_ptrs(self, out, final, reward, reward64, energy, term, trunc, status):
+        """The eight output-pointer arguments of stg_step_many / stg_step_ids in ABI order.  `out` is the record array or the obs
+        array; in the records layout reward / terminated / truncated live in the records (NULL), and the status array is only
+        written with diagnostics (without them `status` is at most a view of the records)."""
+        rec = self.records_layout
+        return (_ptr(out), _ptr(final), None if rec else _ptr(reward), _ptr(reward64), _ptr(energy), None if rec else _ptr(term),
+                None if rec else _ptr(trunc), _ptr(status) if self.diagnostics else None)
 
     def close(self):
         if self._ctx:
@@ -248,33 +266,21 @@ class HipBackend:
         f64 = a.dtype == torch.float64
         a = self._dev(a, torch.float64 if f64 else torch.float32, (2, self.n))
         if autoreset and self.final_obs is None:
-            if self.records_layout:           # env-major like the records: one 48-byte block per env
-                self._final_buf = torch.zeros((self.n, 12), dtype=torch.float32, device=self.device)
-                self.final_obs = self._final_buf.t()
-            else:
-                self._final_buf = self.final_obs = torch.zeros((12, self.n), dtype=torch.float32, device=self.device)
-        if self.records_layout:
-            rec = self.packed if out is None else out
-            if rec.dtype != torch.uint8 or tuple(rec.shape) != (self.n, RECORD_BYTES) or not rec.is_contiguous() or rec.device != self.device:
-                raise ValueError(f"out must be a contiguous uint8 [{self.n}, {RECORD_BYTES}] tensor on {self.device}")
-            diag = self.diagnostics
-            _lib.check(self.lib.stg_step_many(self._ctx, 1, _ptr(a), int(f64), 1, int(bool(autoreset)), _ptr(rec),
-                                              _ptr(self._final_buf) if autoreset else None, None, _ptr(self.reward64),
-                                              _ptr(self.energy), None, None, _ptr(self.status) if diag else None, self._stream()))
-            self._keep = (a,)
-            if out is None:
-                return self.obs, self.reward, self.reward64, self.terminated, self.truncated, self.status
-            obs, reward, term, trunc, st = record_views(rec)
-            return obs.t(), reward, self.reward64, term, trunc, (self.status if diag else st)
-        if out is not None:
+            self._final_buf, self.final_obs = alloc_final_obs((), self.n, self.device, self.cfg.out_layout)
+        if out is not None and not self.records_layout:
             raise ValueError("out= needs out_layout='records'")
-        _lib.check(self.lib.stg_step_many(self._ctx, 1, _ptr(a), int(f64), 1, int(bool(autoreset)), _ptr(self.obs),
-                                          _ptr(self.final_obs) if autoreset else None,
-                                          _ptr(self.reward), _ptr(self.reward64), _ptr(self.energy),
-                                          _ptr(self.terminated), _ptr(self.truncated), _ptr(self.status),
-                                          self._stream()))
+        dst = (self.packed if out is None else out) if self.records_layout else self.obs
+        if self.records_layout and (dst.dtype != torch.uint8 or tuple(dst.shape) != (self.n, RECORD_BYTES) or not dst.is_contiguous()
+                                    or dst.device != self.device):
+            raise ValueError(f"out must be a contiguous uint8 [{self.n}, {RECORD_BYTES}] tensor on {self.device}")
+        _lib.check(self.lib.stg_step_many(self._ctx, 1, _ptr(a), int(f64), 1, int(bool(autoreset)),
+                                          *self._out_ptrs(dst, self._final_buf if autoreset else None, self.reward, self.reward64,
+                                                          self.energy, self.terminated, self.truncated, self.status), self._stream()))
         self._keep = (a,)
-        return self.obs, self.reward, self.reward64, self.terminated, self.truncated, self.status
+        if out is None:
+            return self.obs, self.reward, self.reward64, self.terminated, self.truncated, self.status
+        obs, reward, term, trunc, st = record_views(out)
+        return obs.t(), reward, self.reward64, term, trunc, (self.status if self.diagnostics else st)
 
     def step_many(self, actions, out_every=True, autoreset=False):
         """actions: [K,2,N]; returns tensors with a leading K (out_every) or 1 dimension."""
@@ -298,18 +304,10 @@ class HipBackend:
         reward64 = torch.empty((ko, n), dtype=torch.float64, device=dev) if diag else None
         status = torch.empty((ko, n), dtype=torch.uint8, device=dev) if diag else (record_views(rec)[4] if self.records_layout else None)
         self.energy_many = torch.empty((ko, n), dtype=torch.float64, device=dev) if diag else None
-        fbuf = None
-        self.final_obs_many = None
-        if autoreset:
-            if self.records_layout:
-                fbuf = torch.zeros((ko, n, 12), dtype=torch.float32, device=dev)
-                self.final_obs_many = fbuf.transpose(1, 2)
-            else:
-                fbuf = self.final_obs_many = torch.zeros((ko, 12, n), dtype=torch.float32, device=dev)
+        fbuf, self.final_obs_many = alloc_final_obs((ko,), n, dev, self.cfg.out_layout) if autoreset else (None, None)
         _lib.check(self.lib.stg_step_many(self._ctx, K, _ptr(a), int(f64), int(bool(out_every)), int(bool(autoreset)),
-                                          _ptr(out_ptr), _ptr(fbuf), None if self.records_layout else _ptr(reward),
-                                          _ptr(reward64), _ptr(self.energy_many), None if self.records_layout else _ptr(term),
-                                          None if self.records_layout else _ptr(trunc), _ptr(status) if diag else None, self._stream()))
+                                          *self._out_ptrs(out_ptr, fbuf, reward, reward64, self.energy_many, term, trunc, status),
+                                          self._stream()))
         self._keep = (a,)
         return obs, reward, reward64, term, trunc, status
 
@@ -332,11 +330,7 @@ class HipBackend:
             out.update(reward64=torch.empty(m, dtype=torch.float64, device=dev), energy=torch.empty(m, dtype=torch.float64, device=dev),
                        status=torch.empty(m, dtype=torch.uint8, device=dev))
         if autoreset:
-            if self.records_layout:
-                out["final_buf"] = torch.zeros((m, 12), dtype=torch.float32, device=dev)
-                out["final_obs"] = out["final_buf"].t()
-            else:
-                out["final_buf"] = out["final_obs"] = torch.zeros((12, m), dtype=torch.float32, device=dev)
+            out["final_buf"], out["final_obs"] = alloc_final_obs((), m, dev, self.cfg.out_layout)
         return out
 
     def step_ids(self, actions, env_ids, autoreset=False, workspace=None, out=None, stream=None):
@@ -362,13 +356,10 @@ class HipBackend:
             ws = self.ids_workspace(m) if workspace is None else workspace
             if out is None:
                 out = self.alloc_ids_outputs(m, autoreset)
-            rec = self.records_layout
-            diag = self.diagnostics
-            _lib.check(self.lib.stg_step_ids(self._ctx, m, _ptr(ids), _ptr(a), int(f64), int(bool(autoreset)), _ptr(ws), _ptr(out["buf"]),
-                                             _ptr(out["final_buf"]) if autoreset else None, None if rec else _ptr(out["reward"]),
-                                             _ptr(out["reward64"]), _ptr(out["energy"]), None if rec else _ptr(out["terminated"]),
-                                             None if rec else _ptr(out["truncated"]), _ptr(out["status"]) if diag else None,
-                                             C.c_void_p(s.cuda_stream)))
+            _lib.check(self.lib.stg_step_ids(self._ctx, m, _ptr(ids), _ptr(a), int(f64), int(bool(autoreset)), _ptr(ws),
+                                             *self._out_ptrs(out["buf"], out["final_buf"] if autoreset else None, out["reward"],
+                                                             out["reward64"], out["energy"], out["terminated"], out["truncated"],
+                                                             out["status"]), C.c_void_p(s.cuda_stream)))
         out["_keep"] = (a, ids, ws)           # inputs stay alive while the launch may still read them
         return out
 
