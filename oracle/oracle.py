@@ -16,7 +16,7 @@ _SO = os.path.join(_HERE, "_build", "libstg_oracle.so")
 __all__ = ["Params", "Config", "EnvState", "StepOut", "lib", "build", "make_params", "make_config",
            "simple_solve", "llgs_solve", "resistance", "thermal_strength", "env_step", "env_step_batch",
            "thermal_normals", "parse_action", "simple_dmdt", "llgs_rhs", "DEV_TYPES", "sot_torque", "vcma_keff",
-           "ArrayConfig", "make_array_config", "array_coupling", "ArrayEnvState", "array_step", "array_observation",
+           "ArrayConfig", "make_array_config", "array_coupling", "ArrayEnvState", "array_step", "array_observation", "array_reset_draw",
            "device_field", "ou_update"]
 
 DEV_TYPES = {"stt_mram": 0, "sot_mram": 1, "vcma_mram": 2}
@@ -116,6 +116,8 @@ def lib():
                                       C.POINTER(C.c_uint8), dp]
         L.stgo_array_observation.restype = None
         L.stgo_array_observation.argtypes = [C.POINTER(ArrayConfig), dp, dp, C.c_double, C.c_int32, C.POINTER(C.c_float)]
+        L.stgo_array_reset_draw.restype = None
+        L.stgo_array_reset_draw.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, dp, dp]
         L.stgo_device_field.restype = None
         L.stgo_device_field.argtypes = [dp, C.POINTER(Params), dp]
         L.stgo_ou_update.restype = None
@@ -365,6 +367,13 @@ def array_observation(state, c):
     lib().stgo_array_observation(C.byref(c), _dp(state.pattern), _dp(state.target), state.total_energy.value,
                                  state.step_count.value, obs.ctypes.data_as(C.POINTER(C.c_float)))
     return obs
+
+
+def array_reset_draw(seed, env_id, resets, n_dev):
+    """The array env's device-side random reset of one array: (pattern [n_dev, 3] of unit vectors, |z| [n_dev] before normalising)."""
+    out, norms = np.zeros((n_dev, 3)), np.zeros(n_dev)
+    lib().stgo_array_reset_draw(int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_id), int(resets) & 0xFFFFFFFF, int(n_dev), _dp(out), _dp(norms))
+    return out, norms
 
 
 def device_field(m, p):

@@ -113,6 +113,20 @@ void stgo_reset_draw(uint64_t seed, uint64_t env_id, uint32_t rng_step, int n_ta
     *target_idx = (int)(((uint64_t)r * (uint64_t)n_targets) >> 32);
 }
 
+/* device-side random reset of one array (csrc/stg_array.hip: stg_array_reset_kernel), restated: one stream per (array, reset
+ * count), tag 0xFFFFFFFD, one draw3 per cell (even / odd calls alternate), each normalised; norms[d] = |z_d| before that */
+void stgo_array_reset_draw(uint64_t seed, uint64_t env_id, uint32_t resets, int n_dev, double* out, double* norms) {
+    nstream g;
+    ns_init(&g, seed ^ 0x9E3779B97F4A7C15ull, env_id, resets, 0xFFFFFFFDu);
+    for (int d = 0; d < n_dev; ++d) {
+        double z[3];
+        ns_draw3(&g, z);
+        const double nn = norm3(z);
+        for (int k = 0; k < 3; ++k) out[3 * d + k] = z[k] / nn;
+        if (norms) norms[d] = nn;
+    }
+}
+
 double stgo_thermal_strength(const stgo_params* p, double gamma, double temperature, int which) {
     if (which == 0) {
         /* simple_solver.py:382-383: sqrt(2*alpha*kb*T / (mu_0*ms*volume*gamma)) */
@@ -524,6 +538,9 @@ int64_t stgo_llgs_solve(const double m0[3], double T, const stgo_params* p, cons
 /* ------------------------------------------------------------------------------------------------
  * A9  compute_resistance
  * ------------------------------------------------------------------------------------------------ */
+/* Python's max(r, floor): r unless floor > r, so a NaN r stays NaN (C's fmax would return the floor) */
+static inline double pymax(double r, double floor_) { return floor_ > r ? floor_ : r; }
+
 double stgo_resistance(const double m_in[3], const stgo_params* p) {
     double rn = norm3(p->ref_m);
     double ref[3] = {p->ref_m[0] / rn, p->ref_m[1] / rn, p->ref_m[2] / rn};
@@ -534,7 +551,7 @@ double stgo_resistance(const double m_in[3], const stgo_params* p) {
         double tmr = (p->r_ap - p->r_p) / p->r_p;
         double ct = dot3(m, ref);
         double r = p->r_p * (1 + tmr * (1 - ct) / 2);
-        return fmax(r, p->r_p * 0.5);
+        return pymax(r, p->r_p * 0.5);
     }
     double ct = dot3(m_in, ref);
     double r = p->r_p + (p->r_ap - p->r_p) * (1 - ct) / 2;
@@ -543,7 +560,7 @@ double stgo_resistance(const double m_in[3], const stgo_params* p) {
         r = r + p->r_series;
     }
     /* devices/vcma_mram.py:236-257: floor 1 */
-    return fmax(r, 1.0);
+    return pymax(r, 1.0);
 }
 
 /* ------------------------------------------------------------------------------------------------
@@ -666,7 +683,7 @@ void stgo_array_coupling(int rows, int cols, int type, double strength, double* 
                 /* array_env.py:311-332 */
                 int ir = i / cols, ic = i % cols, jr = j / cols, jc = j % cols;
                 double dist = sqrt((double)((ir - jr) * (ir - jr) + (ic - jc) * (ic - jc)));
-                if (type == 0 && dist > 0) v = strength / (dist * dist * dist);
+                if (type == 0 && dist > 0) v = strength / pow(dist, 3.0);      /* distance**3 is pow(), not d*d*d: 1 ulp apart at e.g. sqrt(17) */
                 else if (type == 1 && dist == 1) v = strength;
                 else if (type == 2 && dist > 0) v = strength / (dist * dist);
             }
@@ -738,8 +755,9 @@ void stgo_array_step(const stgo_array_config* c, const stgo_params* p, const dou
      * (the duration) is what the reference reads as the current density and the duration defaults to 1 ns. */
     double J = n_action > 1 ? (double)action[1] : 0.0;
     double T = n_action > 2 ? (double)action[2] : 1e-9;
-    J = fmin(fmax(J, -c->max_current), c->max_current);
-    T = fmin(fmax(T, 1e-12), c->max_duration);
+    /* np.clip keeps NaN (C's fmin / fmax would return the other operand) */
+    J = isnan(J) ? J : fmin(fmax(J, -c->max_current), c->max_current);
+    T = isnan(T) ? T : fmin(fmax(T, 1e-12), c->max_duration);
     int first = 0, count = 0, stride = 1;
     if (c->action_mode == 3) { first = 0; count = n; stride = 1; }
     else {

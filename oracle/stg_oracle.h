@@ -153,6 +153,8 @@ void stgo_env_step_batch(int64_t n, stgo_env_state* s, const float* actions /*[n
  * `call_idx` (replaying the stream from call 0). */
 void stgo_thermal_normals(uint64_t seed, uint64_t env_id, uint32_t env_step, uint32_t call_idx, double z[3]);
 void stgo_reset_draw(uint64_t seed, uint64_t env_id, uint32_t rng_step, int n_targets, double z[3], int* target_idx);
+/* device-side random reset of one array env (stg_array_reset): out [n_dev][3] unit vectors, norms [n_dev] = |z| before normalising (may be NULL) */
+void stgo_array_reset_draw(uint64_t seed, uint64_t env_id, uint32_t resets, int n_dev, double* out, double* norms);
 void stgo_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
 /* ---- SpinTorqueArray-v0: envs/array_env.py:362-520 ---- */

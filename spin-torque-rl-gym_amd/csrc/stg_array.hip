@@ -65,6 +65,24 @@ __device__ __forceinline__ V3 device_field(const V3& m_in, const ArrDev& d) {
     return V3{c * d.ex - d.ms * d.nx * m_in.x, c * d.ey - d.ms * d.ny * m_in.y, c * d.ez - d.ms * d.nz * m_in.z};
 }
 
+// device.compute_resistance(m) as the array env's energy term sees it (stt_mram.py:78-94, sot_mram.py:196-228, vcma_mram.py:236-257):
+// stg::resistance with Python's max(r, floor) in place of fmax -- r unless floor > r, so the NaN of a cell that a NaN duration (or a NaN
+// neighbour, through the coupling sum) has spoilt reaches the energy as it does in the reference instead of turning into the floor value.
+// Same operations in the same order otherwise: identical for every other input.
+__device__ __forceinline__ double cell_resistance(const V3& m_in, const ArrDev& d) {
+#pragma clang fp contract(off)
+    const V3 ref{d.refx, d.refy, d.refz};
+    if (d.dev_type == STG_DEV_STT) {
+        const double inv = rsqrt_fast(dot(m_in, m_in));
+        const V3 m{m_in.x * inv, m_in.y * inv, m_in.z * inv};
+        const double r = d.r_p * (1.0 + d.tmr * (1.0 - dot(m, ref)) * 0.5);
+        return d.r_p * 0.5 > r ? d.r_p * 0.5 : r;
+    }
+    double r = d.r_p + (d.r_ap - d.r_p) * (1.0 - dot(m_in, ref)) * 0.5;
+    if (d.dev_type == STG_DEV_SOT) r = r + d.r_series;
+    return 1.0 > r ? 1.0 : r;
+}
+
 // Observation rows: 'array' mode [R,C,6] = (pattern, target) per cell; 'vector' mode = flattened pattern, flattened
 // target, then 4 global values (array_env.py:533-557).
 __device__ __forceinline__ int64_t obs_row_pattern(int obs_mode, int n, int d, int k) { return obs_mode == 0 ? d * 6 + k : d * 3 + k; }
@@ -169,8 +187,7 @@ __global__ void __launch_bounds__(64) stg_array_step_kernel(const ArrArgs a) {
             const V3 tg{a.target[(int64_t)(d * 3) * N + i], a.target[(int64_t)(d * 3 + 1) * N + i], a.target[(int64_t)(d * 3 + 2) * N + i]};
             sim_sum += dot(m, tg) - dot(m0, tg);
             // energy with the resistance of the UPDATED state (current_m is a view of the pattern, array_env.py:455-463)
-            const V3 ref{a.dev.refx, a.dev.refy, a.dev.refz};
-            const double r = resistance(m, a.dev.dev_type, a.dev.r_p, a.dev.r_ap, a.dev.tmr, ref, a.dev.r_series);
+            const double r = cell_resistance(m, a.dev);
             const double v = J * r * a.dev.area;
             e_total += (v * v) / r * T;
         }
@@ -314,8 +331,7 @@ __global__ void __launch_bounds__(256, 3) stg_array_step_global_kernel(const Arr
             const V3 tg{ldt(d * 3), ldt(d * 3 + 1), ldt(d * 3 + 2)};
             sim_sum += dot(m, tg) - dot(m0, tg);
             // energy with the resistance of the UPDATED state (current_m is a view of the pattern, array_env.py:455-463)
-            const V3 ref{a.dev.refx, a.dev.refy, a.dev.refz};
-            const double r = resistance(m, a.dev.dev_type, a.dev.r_p, a.dev.r_ap, a.dev.tmr, ref, a.dev.r_series);
+            const double r = cell_resistance(m, a.dev);
             const double v = J * r * a.dev.area;
             e_total += (v * v) / r * T;
             // rotate: cell d (updated) goes to the end, cell d+1 to the front
@@ -446,8 +462,7 @@ __global__ void __launch_bounds__(256) stg_array_step_individual_kernel(const Ar
         const double e_new = sqrt(dot(m, m)) - 1.0;
         se += e_new - e_d; se2 += e_new * e_new - e_d * e_d;
         // energy with the resistance of the UPDATED state (current_m is a view of the pattern, array_env.py:455-463)
-        const V3 ref{a.dev.refx, a.dev.refy, a.dev.refz};
-        const double r = resistance(m, a.dev.dev_type, a.dev.r_p, a.dev.r_ap, a.dev.tmr, ref, a.dev.r_series);
+        const double r = cell_resistance(m, a.dev);
         const double v = J * r * a.dev.area;
         e_total = (v * v) / r * T;
     }

@@ -642,8 +642,91 @@ def G19():
          kwargs_json=np.array([json.dumps(reg[k]["kwargs"], sort_keys=True) for k in ids]))
 
 
+def G20():
+    """array_edges: SpinTorqueArray-v0 episodes at the shapes G13 leaves out (1 x 1, single rows and columns, non-square, 5 x 5,
+    8 x 8, 2 x 32) with out-of-range, fractional, zero, sub-threshold and over-limit actions; plus NaN / infinite currents and
+    durations on 2 x 3 'individual' and 3 x 3 'global', each followed by an ordinary action."""
+    from spin_torque_gym.envs.array_env import SpinTorqueArrayEnv
+    rng = np.random.default_rng(2020)
+    fac = DeviceFactory()
+    out = {}
+    tags = []
+
+    def add(tag, kwargs, actions, seed):
+        env = SpinTorqueArrayEnv(**kwargs)
+        obs0, _ = env.reset(seed=seed)
+        k = len(tags)
+        rec = dict(obs=[obs0.reshape(-1)], reward=[], terminated=[], truncated=[], energy=[], similarity=[],
+                   pattern=[env.current_pattern.copy()])
+        for a in actions:
+            o, r, te, tr, info = env.step(np.array(a, dtype=np.float32))
+            rec["obs"].append(np.asarray(o).reshape(-1)); rec["reward"].append(r); rec["terminated"].append(te)
+            rec["truncated"].append(tr); rec["energy"].append(info["energy_consumed"])
+            rec["similarity"].append(info["pattern_similarity"]); rec["pattern"].append(env.current_pattern.copy())
+        for name, arr in rec.items():
+            out[f"ep{k}_{name}"] = np.array(arr)
+        out[f"ep{k}_actions"] = np.array(actions, dtype=np.float32)
+        out[f"ep{k}_target"] = env.target_pattern.copy()
+        if getattr(env, "include_coupling", False) and env.n_devices <= 25:      # (the 64-cell tables are 32 KB each)
+            out[f"ep{k}_coupling"] = env.coupling_matrix.copy()
+        tags.append(tag)
+        print(f"    G20 episode {k} ({tag}): {len(actions)} steps, final similarity {rec['similarity'][-1]:.4f}, "
+              f"terminated {rec['terminated']}, truncated {rec['truncated']}")
+
+    def edge_acts(lim, jmax, tmax):
+        """Index below 0, above the limit and just under an integer; J = 0, |J| = 1e-13 and beyond max_current; T below 1e-12
+        (also negative) and above max_duration."""
+        def idx(): return rng.uniform(-0.5, lim + 0.5)
+        def J(): return rng.uniform(-jmax, jmax)
+        def T(): return rng.uniform(1e-10, 0.4 * tmax)
+        return [(-0.7, J(), T()), (lim + 3.2, 1.55 * jmax, T()), (max(lim, 1) - 0.001, J(), 1e-13), (idx(), 0.0, T()),
+                (idx(), 1e-13, T()), (idx(), -1.5 * jmax, 1.8 * tmax), (idx(), -1e-13, -1e-9), (idx(), J(), T())]
+
+    def edge_acts_global(jmax):
+        # 'global' mode: action[1] is what the reference reads as the current, the duration is fixed at 1 ns
+        return [(rng.uniform(-jmax, jmax), j) for j in (rng.uniform(-jmax, jmax), 1.55 * jmax, 0.0, 1e-13, -1.5 * jmax, -1e-13,
+                                                        rng.uniform(-jmax, jmax))]
+
+    sot = fac.get_default_parameters("sot_mram"); sot.update(aspect_ratio=2.0)
+    vc = fac.get_default_parameters("vcma_mram"); vc.update(aspect_ratio=0.5, reference_magnetization=np.array([0.0, 0.2, 1.0]))
+    add("1x1_individual", dict(array_size=(1, 1), action_mode="individual", max_steps=5), edge_acts(0, 2e6, 5e-9), 0)
+    add("1x7_column", dict(array_size=(1, 7), action_mode="column", coupling_type="exchange", coupling_strength=0.3,
+                           observation_mode="vector"), edge_acts(6, 2e6, 5e-9), 1)
+    add("1x7_row", dict(array_size=(1, 7), action_mode="row", coupling_type="stray_field", success_threshold=0.004),
+        edge_acts(0, 2e6, 5e-9), 2)
+    add("7x1_row", dict(array_size=(7, 1), action_mode="row", coupling_strength=0.2, observation_mode="vector", max_steps=6,
+                        temperature=350.0), edge_acts(6, 2e6, 5e-9), 3)
+    add("7x1_column", dict(array_size=(7, 1), action_mode="column", include_coupling=False, max_current=1e6, max_duration=1e-9,
+                           energy_penalty_weight=0.3), edge_acts(0, 1e6, 1e-9), 4)
+    add("5x3_row", dict(array_size=(5, 3), action_mode="row", device_type="sot_mram", device_params=sot, max_current=5e3,
+                        observation_mode="vector"), edge_acts(4, 5e3, 5e-9), 5)
+    add("3x5_row", dict(array_size=(3, 5), action_mode="row", device_type="vcma_mram", device_params=vc, max_current=5e3,
+                        coupling_type="exchange", coupling_strength=0.3, max_steps=4), edge_acts(2, 5e3, 5e-9), 6)
+    add("5x5_global", dict(array_size=(5, 5), action_mode="global", coupling_type="stray_field", observation_mode="vector",
+                           success_threshold=-0.002), edge_acts_global(2e6), 7)
+    add("8x8_row", dict(array_size=(8, 8), action_mode="row"), edge_acts(7, 2e6, 5e-9), 8)
+    add("8x8_column", dict(array_size=(8, 8), action_mode="column", coupling_type="exchange", coupling_strength=0.3,
+                           observation_mode="vector", max_steps=3), edge_acts(7, 2e6, 5e-9), 9)
+    add("8x8_global", dict(array_size=(8, 8), action_mode="global", coupling_type="stray_field", device_type="sot_mram",
+                           device_params=sot, max_current=5e3), edge_acts_global(5e3), 10)
+    add("2x32_column", dict(array_size=(2, 32), action_mode="column", device_type="vcma_mram", device_params=vc, max_current=5e3,
+                            observation_mode="vector"), edge_acts(31, 5e3, 5e-9), 11)
+    # NaN / infinite currents and durations, each followed by an ordinary action; the NaN duration comes last because the NaN
+    # it writes into the pattern stays (and spreads through the coupling sum)
+    nan, inf = float("nan"), float("inf")
+    def ordinary(lim): return (rng.uniform(-0.5, lim + 0.5), rng.uniform(-2e6, 2e6), rng.uniform(1e-10, 2e-9))
+    add("nan_2x3_individual", dict(array_size=(2, 3), action_mode="individual", coupling_strength=0.2, observation_mode="vector"),
+        [(1.0, nan, 1e-9), ordinary(5), (2.0, inf, 1e-9), ordinary(5), (3.0, -inf, 5e-10), ordinary(5), (4.0, 1.2e6, inf), ordinary(5),
+         (0.0, 1.5e6, nan), (4.0, -1.1e6, 7e-10), (0.0, 0.9e6, 3e-10)], 3)
+    add("nan_3x3_global", dict(array_size=(3, 3), action_mode="global"),
+        [(1e6, nan), (0.3e6, rng.uniform(-2e6, 2e6)), (1e6, inf), (nan, rng.uniform(-2e6, 2e6)), (inf, -inf),
+         (-0.2e6, rng.uniform(-2e6, 2e6))], 4)
+    out["episode_tags"] = np.array(tags)
+    save("G20_array_edges", **out)
+
+
 ALL = dict(G18=G18, G17=G17, G16=G16, G15=G15, G14=G14, G1=G1, G2=G2, G3=G3, G4=G4, G5=G5, G6=G6, G7=G7, G8=G8, G9=G9, G10=G10, G11=G11, G12=G12, G13=G13,
-           G19=G19)
+           G19=G19, G20=G20)
 
 if __name__ == "__main__":
     which = sys.argv[1:] or list(ALL)

@@ -299,6 +299,8 @@ class OracleArrayBackend:
         self.coupling = np.zeros((self.n_dev, self.n_dev)) if coupling is None else np.ascontiguousarray(coupling, dtype=np.float64)
         self.states = [None] * self.n
         self.target = None
+        self.env_id0 = int(env_id0)
+        self.resets = np.zeros(self.n, dtype=np.uint32)      # per array: how many random resets it has had
         n = self.n
         self.obs = torch.zeros((self.obs_dim, n), dtype=torch.float32)
         self.reward = torch.zeros(n, dtype=torch.float32)
@@ -311,13 +313,28 @@ class OracleArrayBackend:
         pass
 
     def reset(self, mask=None, init_pattern=None, target=None, seed=0):
-        assert init_pattern is not None, "the oracle backend takes explicit initial patterns"
-        ip = torch.as_tensor(init_pattern).numpy()
+        """stg_array_reset: selected arrays take `init_pattern` or, without one, the device-side random draw of
+        (seed, env_id0 + i, this array's count of earlier random resets); `target`, else the target they have, else the
+        checkerboard; energy and step count return to zero.  The observation of EVERY array is returned."""
+        ip = None if init_pattern is None else torch.as_tensor(init_pattern).cpu().numpy()
+        tg_in = None if target is None else torch.as_tensor(target).cpu().numpy()
+        mask = None if mask is None else torch.as_tensor(mask).cpu().numpy().astype(bool)
         for i in range(self.n):
-            if mask is not None and not bool(mask[i]):
-                continue
-            tg = torch.as_tensor(target).numpy()[:, i].reshape(-1, 3) if target is not None else self.states[i].target
-            self.states[i] = oracle.ArrayEnvState(ip[:, i].reshape(-1, 3), tg)
+            if mask is None or mask[i]:
+                if ip is not None:
+                    pat = ip[:, i].reshape(-1, 3).copy()      # (a column of an N = 1 batch is contiguous: never alias the caller's array)
+                else:
+                    pat, _ = oracle.array_reset_draw(int(seed), self.env_id0 + i, int(self.resets[i]), self.n_dev)
+                    self.resets[i] += 1
+                if tg_in is not None:
+                    tg = tg_in[:, i].reshape(-1, 3).copy()
+                elif self.states[i] is not None:
+                    tg = self.states[i].target
+                else:                                  # checkerboard of +-z over (row, column)
+                    r, c = np.divmod(np.arange(self.n_dev), self.cfg.cols)
+                    tg = np.zeros((self.n_dev, 3))
+                    tg[:, 2] = np.where((r + c) % 2 == 0, 1.0, -1.0)
+                self.states[i] = oracle.ArrayEnvState(pat, tg)
             self.obs[:, i] = torch.from_numpy(oracle.array_observation(self.states[i], self.ocfg))
         return self.obs
 
