@@ -358,6 +358,31 @@ int stg_array_step(stg_array_ctx* ctx, const float* actions, float* obs, float* 
 int stg_array_get_state(stg_array_ctx* ctx, double* pattern, double* target, double* total_energy, int32_t* step_count,
                         void* stream);
 
+/* K steps of every array in ONE launch: the pattern stays on chip for all K steps, with optional same-step auto-reset (the array
+ * env's counterpart of stg_step_many).  actions [dev] float[K][A][N].  out_every = 1: obs float[K][obs_dim][N], reward float[K][N],
+ * reward_f64 / energy double[K][N] or NULL, terminated / truncated uint8[K][N]; out_every = 0: only the last step's outputs are
+ * written, with a leading dimension of 1 (reward / energy are the last step's values, not sums).
+ * autoreset = 0: exactly K calls of stg_array_step, finished arrays keep stepping as in the reference.  autoreset != 0: an array
+ * with terminated | truncated at step k reports that step's reward and flags and is then reset in the kernel as
+ * stg_array_reset(mask = that array, init_pattern = NULL, target = NULL, seed) would reset it (random pattern of the same stream,
+ * its reset counter advanced, target kept, energy and step count zero); its obs column holds the new episode's first observation
+ * and final_obs float[K or 1][obs_dim][N] (may be NULL) receives the terminal observation of such arrays ONLY -- other entries are
+ * left untouched; the next step of the launch continues the new episode.
+ * Enqueues kernels only (no host synchronisation, no scratch): may be captured in a graph.  STG_E_INVALID for K < 1, a missing
+ * mandatory pointer or an array too large for the device's LDS, STG_E_STATE before the first reset; nothing is launched then. */
+int stg_array_step_many(stg_array_ctx* ctx, int32_t K, const float* actions, int32_t out_every, int32_t autoreset, uint64_t seed,
+                        float* obs, float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated,
+                        uint8_t* truncated, void* stream);
+
+/* The inverse of stg_array_get_state plus the per-array reset counters (which key the device-side random reset draws): asynchronous
+ * copies on `stream` from [dev] buffers of stg_array_get_state's shapes, resets uint32[N]; any may be NULL.  A pattern marks the
+ * context as having state and a target as having a target, so a context restored with both can step without a reset. */
+int stg_array_set_state(stg_array_ctx* ctx, const double* pattern, const double* target, const double* total_energy,
+                        const int32_t* step_count, const uint32_t* resets, void* stream);
+
+/* resets [dev] uint32[N]: how many device-side random resets each array has had (asynchronous copy on `stream`) */
+int stg_array_get_resets(stg_array_ctx* ctx, uint32_t* resets, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

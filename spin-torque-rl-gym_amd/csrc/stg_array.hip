@@ -565,6 +565,224 @@ __global__ void __launch_bounds__(64) stg_array_reset_kernel(const ArrResetArgs 
     }
 }
 
+// ---- K fused steps with same-step auto-reset (stg_array_step_many) ------------------------------------------------------------------
+// The general kernel's layout (one array per lane, 64-lane workgroups, pattern in LDS as [cell*3+component][64], coupling matrix behind
+// it), but the pattern is loaded ONCE, stays in LDS for all K steps and is written back once; total energy and step count live in
+// registers.  After the one barrier that publishes the coupling matrix a lane touches only its own LDS column, so lanes beyond N leave
+// and the in-kernel reset needs no further barrier.  The target is NOT LDS-resident (a second 24.6 KB copy per wavefront would halve the
+// resident wavefronts of a latency-bound kernel): it is re-read once per step, in the pass that forms the similarity from scratch.
+// Forming the similarity from scratch every step (instead of carrying an incrementally updated sum) makes a step a function of the
+// state alone, so K steps in one launch equal the same steps split over several launches bit for bit.
+struct ArrManyArgs {
+    ArrArgs s;                 // actions / outputs point at step 0 / output slot 0
+    int64_t env_id0;
+    int32_t K, out_every, autoreset;
+    uint64_t seed;
+    uint32_t* resets;          // [N]
+    float* final_obs;          // [K or 1][obs_dim][N] or NULL
+};
+
+// One pass over the array: similarity sum of the LDS-resident pattern with the target (np.mean of the per-cell dot products,
+// array_env.py:523-531, same order as the general kernel's first pass), the sum of the cell norms and, when dst is not NULL, the pattern
+// and target rows of one observation.
+__device__ __forceinline__ double many_pass(const ArrArgs& a, const double* lp, int lane, int n, int64_t i, float* dst, double& norm_sum) {
+    const int64_t N = a.N;
+    double sim_sum = 0.0, ns = 0.0;
+    for (int d = 0; d < n; ++d) {
+        const double pv[3] = {lp[(d * 3) * 64 + lane], lp[(d * 3 + 1) * 64 + lane], lp[(d * 3 + 2) * 64 + lane]};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double tv = a.target[(int64_t)(d * 3 + k) * N + i];
+            sim_sum += pv[k] * tv;
+            if (dst) {
+                dst[obs_row_pattern(a.obs_mode, n, d, k) * N + i] = (float)pv[k];
+                dst[obs_row_target(a.obs_mode, n, d, k) * N + i] = (float)tv;
+            }
+        }
+        ns += sqrt(dot(V3{pv[0], pv[1], pv[2]}, V3{pv[0], pv[1], pv[2]}));
+    }
+    norm_sum = ns;
+    return sim_sum;
+}
+
+// the pattern and target rows of one observation, nothing else (the terminal observation of an array that is about to restart)
+__device__ __forceinline__ void many_copy_rows(const ArrArgs& a, const double* lp, int lane, int n, int64_t i, float* dst) {
+    const int64_t N = a.N;
+    for (int d = 0; d < n; ++d) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            dst[obs_row_pattern(a.obs_mode, n, d, k) * N + i] = (float)lp[(d * 3 + k) * 64 + lane];
+            dst[obs_row_target(a.obs_mode, n, d, k) * N + i] = (float)a.target[(int64_t)(d * 3 + k) * N + i];
+        }
+    }
+}
+
+// the four global values behind the pattern and target rows of a 'vector' observation (array_env.py:547-557)
+__device__ __forceinline__ void many_vector_rows(const ArrArgs& a, float* dst, int n, int64_t i, double sim, int32_t step, double etot) {
+    const int64_t N = a.N;
+    dst[(int64_t)(6 * n + 0) * N + i] = (float)sim;
+    dst[(int64_t)(6 * n + 1) * N + i] = (float)((double)(a.max_steps - step) / (double)a.max_steps);
+    dst[(int64_t)(6 * n + 2) * N + i] = (float)(etot / 1e-12);
+    dst[(int64_t)(6 * n + 3) * N + i] = (float)(a.temperature / 300.0);
+}
+
+// One addressed cell, in place in LDS: effective field with the coupling sum over the current pattern, ten normalised Euler sub-steps of
+// one derivative (array_env.py:478-521).  Returns the cell's energy, with the resistance of the UPDATED state (array_env.py:455-463).
+template <int NDEV>
+__device__ __forceinline__ double many_update_cell(const ArrArgs& a, double* lp, const double* lc, int lane, int n, int d, double J, double T) {
+    const V3 m0{lp[(d * 3) * 64 + lane], lp[(d * 3 + 1) * 64 + lane], lp[(d * 3 + 2) * 64 + lane]};
+    V3 h = device_field(m0, a.dev);
+    if (a.include_coupling) {                                                      // array_env.py:485-492
+        V3 hc{0.0, 0.0, 0.0};
+#pragma unroll
+        for (int j = 0; j < (NDEV > 0 ? NDEV : n); ++j) {
+            const double c = (j == d) ? 0.0 : lc[d * n + j];
+            hc = V3{hc.x + c * lp[(j * 3) * 64 + lane], hc.y + c * lp[(j * 3 + 1) * 64 + lane], hc.z + c * lp[(j * 3 + 2) * 64 + lane]};
+        }
+        h = V3{h.x + hc.x, h.y + hc.y, h.z + hc.z};
+    }
+    // _simulate_device_dynamics (array_env.py:496-521): alpha = 0.01, gamma = 2.21e5, p_hat = z
+    const V3 mxp{m0.y, -m0.x, 0.0};
+    const V3 t2 = cross(m0, mxp);
+    const double tj = 0.1 * J;
+    const V3 mxh = cross(m0, h);
+    V3 dm{-2.21e5 * mxh.x, -2.21e5 * mxh.y, -2.21e5 * mxh.z};
+    const V3 mxdm = cross(m0, dm);
+    dm = V3{dm.x + 0.01 * mxdm.x + tj * t2.x, dm.y + 0.01 * mxdm.y + tj * t2.y, dm.z + 0.01 * mxdm.z + tj * t2.z};
+    const double dt = T / 10;
+    V3 m = m0;
+#pragma unroll
+    for (int it = 0; it < 10; ++it) {
+        m = V3{m.x + dm.x * dt, m.y + dm.y * dt, m.z + dm.z * dt};
+        const double inv = rsqrt_fast(dot(m, m));               // m / |m| (array_env.py:518), <= 2 ulp per component
+        m = V3{m.x * inv, m.y * inv, m.z * inv};
+    }
+    lp[(d * 3) * 64 + lane] = m.x; lp[(d * 3 + 1) * 64 + lane] = m.y; lp[(d * 3 + 2) * 64 + lane] = m.z;
+    const double r = cell_resistance(m, a.dev);
+    const double v = J * r * a.dev.area;
+    return (v * v) / r * T;
+}
+
+// stg_array_reset_kernel's random draw for one array (same stream key, same normalisation), into the array's LDS column
+__device__ __forceinline__ void many_draw_pattern(double* lp, int lane, int n, uint64_t seed, uint64_t env_id, uint32_t resets) {
+    NormalStream ns;
+    ns.init(seed ^ 0x9E3779B97F4A7C15ull, env_id, resets, 0xFFFFFFFDu);
+    for (int d = 0; d < n; ++d) {
+        const V3 z = (d & 1) ? ns.draw3_odd() : ns.draw3_even();
+        const double inv = 1.0 / sqrt(dot(z, z));
+        lp[(d * 3) * 64 + lane] = z.x * inv;
+        lp[(d * 3 + 1) * 64 + lane] = z.y * inv;
+        lp[(d * 3 + 2) * 64 + lane] = z.z * inv;
+    }
+}
+
+template <int NDEV>
+__global__ void __launch_bounds__(64) stg_array_step_many_kernel(const ArrManyArgs b) {
+    extern __shared__ double lds[];           // pattern [n*3][64] then coupling [n*n]
+    const ArrArgs& a = b.s;
+    const int n = NDEV > 0 ? NDEV : a.rows * a.cols;
+    double* lp = lds;
+    double* lc = lds + (size_t)n * 3 * 64;
+    const int lane = threadIdx.x;
+    if (a.include_coupling) {
+        for (int q = lane; q < n * n; q += 64) lc[q] = a.coupling[q];
+    }
+    const int64_t i = (int64_t)blockIdx.x * 64 + lane;
+    const bool in_range = i < a.N;
+    const int64_t N = a.N;
+    if (in_range) {
+        for (int q = 0; q < 3 * n; ++q) lp[q * 64 + lane] = a.pattern[(int64_t)q * N + i];
+    }
+    __syncthreads();           // the only barrier: from here on a lane reads the coupling matrix and its own LDS column, nothing else
+    if (!in_range) return;
+    double etot = a.etot[i];
+    int32_t step = a.step[i];
+    const int n_act = a.mode == 3 ? 2 : 3;
+    const int64_t obs_rows = 6 * n + (a.obs_mode == 1 ? 4 : 0);
+    double norm_sum;
+    double sim_sum = many_pass(a, lp, lane, n, i, nullptr, norm_sum);
+#pragma unroll 1
+    for (int k = 0; k < b.K; ++k) {
+        const float* act = a.actions + (int64_t)k * n_act * N;
+        const bool emit = b.out_every || k == b.K - 1;
+        const int64_t slot = b.out_every ? k : 0;
+        float* obs = emit ? a.obs + slot * obs_rows * N : nullptr;
+        const double prev_sim = sim_sum / n;                                           // array_env.py:372-373
+        // _apply_action (array_env.py:411-445).  In 'global' mode the action is [current, duration]: action[1] (the duration) is what
+        // the reference reads as the current density, and the duration defaults to 1 ns -- kept as is.
+        double J = (double)act[N + i];
+        double T = n_act > 2 ? (double)act[2 * N + i] : 1e-9;
+        J = isnan(J) ? J : fmin(fmax(J, -a.max_current), a.max_current);
+        T = isnan(T) ? T : fmin(fmax(T, 1e-12), a.max_duration);
+        int first = 0, count = n, stride = 1;
+        if (a.mode != 3) {
+            const double lim = a.mode == 0 ? n - 1 : (a.mode == 1 ? a.rows - 1 : a.cols - 1);
+            const double a0 = (double)act[i];
+            // int(np.clip(action[0], 0, lim)); a NaN index raises in the reference -- here it addresses nothing
+            const int idx = isnan(a0) ? -1 : (int)fmin(fmax(a0, 0.0), lim);
+            if (a.mode == 0) { first = idx; count = 1; stride = 1; }
+            else if (a.mode == 1) { first = idx * a.cols; count = a.cols; stride = 1; }
+            else { first = idx; count = a.rows; stride = a.cols; }
+            if (idx < 0) count = 0;
+        }
+        double e_total = 0.0;
+        if (fabs(J) > 1e-12) {                                                         // array_env.py:506
+            // The addressed cells update sequentially and each sees its predecessors' new states through the coupling sum
+            // (the reference updates current_pattern in place, array_env.py:447-476).
+#pragma unroll 1
+            for (int q = 0; q < count; ++q) e_total += many_update_cell<NDEV>(a, lp, lc, lane, n, first + q * stride, J, T);
+        }
+        etot += e_total;
+        step += 1;
+        sim_sum = many_pass(a, lp, lane, n, i, obs, norm_sum);
+        const double sim = sim_sum / n;
+        const bool is_success = sim >= a.thr;
+        // uniformity: 1 - population std of the cell magnitudes (array_env.py:216-224)
+        const double mean = norm_sum / n;
+        double var = 0.0;
+        for (int d = 0; d < n; ++d) {
+            const V3 m{lp[(d * 3) * 64 + lane], lp[(d * 3 + 1) * 64 + lane], lp[(d * 3 + 2) * 64 + lane]};
+            const double dv = sqrt(dot(m, m)) - mean;
+            var += dv * dv;
+        }
+        const double uniformity = fmax(0.0, 1.0 - sqrt(var / n));
+        // default reward (array_env.py:183-224): pattern match, energy (sign as written), progress, uniformity
+        double reward = 10.0 * (is_success ? 10.0 : sim * 5.0);
+        reward += (-a.w_energy) * (-e_total / 1e-12);
+        reward += (sim - prev_sim);
+        reward += 2.0 * uniformity;
+        const bool truncated = step >= a.max_steps;
+        if (emit) {
+            if (a.obs_mode == 1) many_vector_rows(a, obs, n, i, sim, step, etot);
+            const int64_t o = slot * N + i;
+            a.reward[o] = (float)reward;
+            if (a.reward64) a.reward64[o] = reward;
+            if (a.energy) a.energy[o] = e_total;
+            a.term[o] = is_success ? 1 : 0;
+            a.trunc[o] = truncated ? 1 : 0;
+        }
+        if (b.autoreset && (is_success || truncated)) {
+            // the step above reported the finished episode; its terminal observation goes to final_obs and the array restarts as
+            // stg_array_reset(mask = this array, init_pattern = NULL, target = NULL, seed) restarts it
+            if (emit && b.final_obs) {
+                float* fo = b.final_obs + slot * obs_rows * N;
+                many_copy_rows(a, lp, lane, n, i, fo);
+                if (a.obs_mode == 1) many_vector_rows(a, fo, n, i, sim, step, etot);
+            }
+            const uint32_t rs = b.resets[i];
+            many_draw_pattern(lp, lane, n, b.seed, (uint64_t)(b.env_id0 + i), rs);
+            b.resets[i] = rs + 1;
+            etot = 0.0;
+            step = 0;
+            sim_sum = many_pass(a, lp, lane, n, i, obs, norm_sum);
+            if (emit && a.obs_mode == 1) many_vector_rows(a, obs, n, i, sim_sum / n, step, etot);
+        }
+    }
+    for (int q = 0; q < 3 * n; ++q) a.pattern[(int64_t)q * N + i] = lp[q * 64 + lane];
+    a.etot[i] = etot;
+    a.step[i] = step;
+}
+
 }  // namespace
 
 extern "C" int stg_internal_fail(int code, const char* msg);     // spintorque_hip.hip: sets stg_last_error()
@@ -586,6 +804,7 @@ struct stg_array_ctx {
     int32_t* step;
     uint32_t* resets;
     bool have_state = false, have_target = false;
+    int lds_max = 0;          // the device's LDS per workgroup, in bytes (stg_array_step_many checks its request against it)
     int variant = 1;          // experiment knob STG_ARRAY_VARIANT: 0 generic kernel for every size, 1 (default) the 4 x 4 specialisations,
                               // 2 the 4 x 4 kernel with the pattern in LDS in 'global' mode too
 };
@@ -612,6 +831,14 @@ int stg_array_create(stg_array_ctx** out, int device_id, int64_t n_arrays, int64
     if (!c) return afail(STG_E_NOMEM, "out of host memory");
     c->device = device_id; c->N = n_arrays; c->env_id0 = env_id0; c->cfg = *cfg;
     if (const char* e = std::getenv("STG_ARRAY_VARIANT")) c->variant = std::atoi(e);
+    (void)hipDeviceGetAttribute(&c->lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device_id);
+    {   // stg_array_step_many's launch above 48 KB of LDS needs the opt-in once; here, so that the call itself only enqueues
+        const size_t lds_many = sizeof(double) * ((size_t)n * 3 * 64 + (cfg->include_coupling ? (size_t)n * n : 0));
+        if (n != 16 && lds_many > 48 * 1024 && lds_many <= (size_t)c->lds_max) {
+            hipError_t ea = hipFuncSetAttribute((const void*)stg_array_step_many_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_many);
+            if (ea != hipSuccess) { delete c; return afail(STG_E_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(ea)); }
+        }
+    }
     const double mu0 = 4 * M_PI * 1e-7;
     ArrDev& d = c->dev;
     d.hk = 2 * p->ku / (mu0 * p->ms); d.ms = p->ms;                       // stt_mram.py:71, sot_mram.py:93
@@ -720,6 +947,65 @@ int stg_array_get_state(stg_array_ctx* ctx, double* pattern, double* target, dou
     if (target) AHIP_TRY(hipMemcpyAsync(target, ctx->target, N * 8 * 3 * n, hipMemcpyDeviceToDevice, st));
     if (total_energy) AHIP_TRY(hipMemcpyAsync(total_energy, ctx->etot, N * 8, hipMemcpyDeviceToDevice, st));
     if (step_count) AHIP_TRY(hipMemcpyAsync(step_count, ctx->step, N * 4, hipMemcpyDeviceToDevice, st));
+    return STG_OK;
+}
+
+int stg_array_step_many(stg_array_ctx* ctx, int32_t K, const float* actions, int32_t out_every, int32_t autoreset, uint64_t seed,
+                        float* obs, float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated,
+                        uint8_t* truncated, void* stream) {
+    if (!ctx) return afail(STG_E_INVALID, "ctx is NULL");
+    if (K < 1) return afail(STG_E_INVALID, "K must be >= 1");
+    if (!actions || !obs || !reward || !terminated || !truncated) return afail(STG_E_INVALID, "actions/obs/reward/terminated/truncated must not be NULL");
+    if (!ctx->have_state) return afail(STG_E_STATE, "stg_array_reset (or stg_array_set_state) must precede stg_array_step_many");
+    AHIP_TRY(hipSetDevice(ctx->device));
+    const stg_array_config& c = ctx->cfg;
+    const int n = c.rows * c.cols;
+    // pattern [n*3][64] and the coupling matrix: 26 KB at 4 x 4, 128 KB at 8 x 8 -- checked against the device before anything is launched
+    const size_t lds = sizeof(double) * ((size_t)n * 3 * 64 + (c.include_coupling ? (size_t)n * n : 0));
+    if (lds > (size_t)ctx->lds_max)
+        return afail(STG_E_INVALID, "stg_array_step_many: the array's pattern and coupling matrix (" + std::to_string(lds) +
+                                        " bytes per workgroup) do not fit the device's LDS (" + std::to_string(ctx->lds_max) + ")");
+    ArrManyArgs b{};
+    ArrArgs& a = b.s;
+    a.N = ctx->N; a.rows = c.rows; a.cols = c.cols; a.mode = c.action_mode; a.include_coupling = c.include_coupling;
+    a.max_steps = c.max_steps; a.obs_mode = c.obs_mode; a.max_current = c.max_current; a.max_duration = c.max_duration;
+    a.thr = c.success_threshold; a.w_energy = c.energy_penalty_weight; a.temperature = c.temperature; a.dev = ctx->dev;
+    a.coupling = ctx->coupling; a.pattern = ctx->pattern; a.target = ctx->target; a.etot = ctx->etot; a.step = ctx->step;
+    a.actions = actions; a.obs = obs; a.reward = reward; a.reward64 = reward_f64; a.energy = energy; a.term = terminated;
+    a.trunc = truncated;
+    b.env_id0 = ctx->env_id0; b.K = K; b.out_every = out_every ? 1 : 0; b.autoreset = autoreset ? 1 : 0; b.seed = seed;
+    b.resets = ctx->resets; b.final_obs = final_obs;
+    const dim3 grid((unsigned)((ctx->N + 63) / 64));
+    if (n == 16) {
+        hipLaunchKernelGGL((stg_array_step_many_kernel<16>), grid, dim3(64), lds, (hipStream_t)stream, b);
+    } else {
+        hipLaunchKernelGGL((stg_array_step_many_kernel<0>), grid, dim3(64), lds, (hipStream_t)stream, b);
+    }
+    AHIP_TRY(hipGetLastError());
+    return STG_OK;
+}
+
+int stg_array_set_state(stg_array_ctx* ctx, const double* pattern, const double* target, const double* total_energy,
+                        const int32_t* step_count, const uint32_t* resets, void* stream) {
+    if (!ctx) return afail(STG_E_INVALID, "ctx is NULL");
+    AHIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t N = (size_t)ctx->N, n = (size_t)ctx->cfg.rows * ctx->cfg.cols;
+    if (pattern) AHIP_TRY(hipMemcpyAsync(ctx->pattern, pattern, N * 8 * 3 * n, hipMemcpyDeviceToDevice, st));
+    if (target) AHIP_TRY(hipMemcpyAsync(ctx->target, target, N * 8 * 3 * n, hipMemcpyDeviceToDevice, st));
+    if (total_energy) AHIP_TRY(hipMemcpyAsync(ctx->etot, total_energy, N * 8, hipMemcpyDeviceToDevice, st));
+    if (step_count) AHIP_TRY(hipMemcpyAsync(ctx->step, step_count, N * 4, hipMemcpyDeviceToDevice, st));
+    if (resets) AHIP_TRY(hipMemcpyAsync(ctx->resets, resets, N * 4, hipMemcpyDeviceToDevice, st));
+    if (pattern) ctx->have_state = true;       // a context that never had a pattern still needs its first reset
+    if (target) ctx->have_target = true;
+    return STG_OK;
+}
+
+int stg_array_get_resets(stg_array_ctx* ctx, uint32_t* resets, void* stream) {
+    if (!ctx) return afail(STG_E_INVALID, "ctx is NULL");
+    if (!resets) return afail(STG_E_INVALID, "resets is NULL");
+    AHIP_TRY(hipSetDevice(ctx->device));
+    AHIP_TRY(hipMemcpyAsync(resets, ctx->resets, (size_t)ctx->N * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return STG_OK;
 }
 

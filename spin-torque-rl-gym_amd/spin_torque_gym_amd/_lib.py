@@ -83,6 +83,9 @@ SYMBOLS = {
     "stg_array_reset": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP]),
     "stg_array_step": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "stg_array_get_state": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
+    "stg_array_step_many": (C.c_int, [_VP, C.c_int32, _VP, C.c_int32, C.c_int32, C.c_uint64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "stg_array_set_state": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "stg_array_get_resets": (C.c_int, [_VP, _VP, _VP]),
 }
 
 _lib = None

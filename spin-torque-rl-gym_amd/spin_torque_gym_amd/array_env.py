@@ -132,6 +132,61 @@ class HipArrayBackend:
                                                 _ptr(st["step_count"]), self._stream()))
         return st
 
+    def many_outputs(self, K, out_every=True, autoreset=False):
+        """Fresh output tensors of one step_many call: leading dimension K (1 without out_every).  final_obs starts as NaN, so
+        the entries the kernel leaves untouched (arrays that did not finish at that step) read as NaN."""
+        k, n, dev = (int(K) if out_every else 1), self.n, self.device
+        out = dict(obs=torch.empty((k, self.obs_dim, n), dtype=torch.float32, device=dev),
+                   reward=torch.empty((k, n), dtype=torch.float32, device=dev),
+                   reward64=torch.empty((k, n), dtype=torch.float64, device=dev),
+                   energy=torch.empty((k, n), dtype=torch.float64, device=dev),
+                   terminated=torch.empty((k, n), dtype=torch.uint8, device=dev),
+                   truncated=torch.empty((k, n), dtype=torch.uint8, device=dev))
+        if autoreset:
+            out["final_obs"] = torch.full((k, self.obs_dim, n), float("nan"), dtype=torch.float32, device=dev)
+        return out
+
+    def step_many(self, actions, out_every=True, autoreset=False, seed=0, out=None):
+        """stg_array_step_many: actions [K, A, N]; one launch for all K steps.  `out` (optional) holds preallocated tensors of
+        many_outputs()'s shapes to write into (static buffers for graph capture); returns the dict of outputs."""
+        a_dim = 2 if self.cfg.action_mode == 3 else 3
+        a = torch.as_tensor(actions)
+        if a.dim() != 3:
+            raise ValueError(f"expected actions of shape [K, {a_dim}, {self.n}], got {tuple(a.shape)}")
+        K = int(a.shape[0])
+        a = self._dev(a, torch.float32, (K, a_dim, self.n))
+        o = dict(out) if out is not None else {}
+        names = ("obs", "reward", "reward64", "energy", "terminated", "truncated") + (("final_obs",) if autoreset else ())
+        if any(name not in o for name in names):
+            for name, t in self.many_outputs(K, out_every, autoreset).items():
+                o.setdefault(name, t)
+        k_out = K if out_every else 1
+        for name, t in o.items():
+            lead = (k_out, self.obs_dim, self.n) if name in ("obs", "final_obs") else (k_out, self.n)
+            if tuple(t.shape) != lead or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"out[{name!r}] must be a contiguous {lead} tensor on {self.device}")
+        fo = o.get("final_obs") if autoreset else None
+        _lib.check(self.lib.stg_array_step_many(self._ctx, K, _ptr(a), int(bool(out_every)), int(bool(autoreset)),
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(o["obs"]), _ptr(fo), _ptr(o["reward"]),
+                                                _ptr(o["reward64"]), _ptr(o["energy"]), _ptr(o["terminated"]), _ptr(o["truncated"]),
+                                                self._stream()))
+        self._keep = (a, o)
+        return o
+
+    def set_state(self, pattern=None, target=None, total_energy=None, step_count=None, resets=None):
+        """stg_array_set_state: any of get_state()'s tensors and the reset counters (as get_resets() returns them)."""
+        n = self.n
+        t = (self._dev(pattern, torch.float64, (self.n_dev * 3, n)), self._dev(target, torch.float64, (self.n_dev * 3, n)),
+             self._dev(total_energy, torch.float64, (n,)), self._dev(step_count, torch.int32, (n,)), self._dev(resets, torch.int32, (n,)))
+        _lib.check(self.lib.stg_array_set_state(self._ctx, *[_ptr(x) for x in t], self._stream()))
+        self._keep = t
+
+    def get_resets(self):
+        """Per array: how many device-side random resets it has had (the counter that keys the next draw), as int64."""
+        r = torch.empty(self.n, dtype=torch.int32, device=self.device)         # (the counter's 32 bits; it never gets near 2^31)
+        _lib.check(self.lib.stg_array_get_resets(self._ctx, _ptr(r), self._stream()))
+        return r.to(torch.int64)
+
 
 class SpinTorqueArrayVecEnv:
     """N parallel SpinTorqueArray-v0 environments.  Observations come back as [N, obs_dim] views ('array' mode:
@@ -174,6 +229,7 @@ class SpinTorqueArrayVecEnv:
         factory_fn = HipArrayBackend if backend is None else backend
         self.backend = factory_fn(self.num_envs, cfg, flatten_params(self.device), self.coupling_matrix, device_index, env_id0)
         self._needs_reset = True
+        self._dev_seed = 0
 
     def _soa(self, pattern):
         """[N, rows, cols, 3] or [rows, cols, 3] -> component-major [n_dev*3, N]."""
@@ -191,6 +247,7 @@ class SpinTorqueArrayVecEnv:
         if seed is not None:
             self._rng, _ = _np_random(seed)
         dev_seed = int(self._rng.integers(0, 2**63 - 1))
+        self._dev_seed = dev_seed              # keys the auto-reset draws of step_many until the next reset()
         target = options.get("target_pattern")
         if target is None and self._needs_reset:
             target = self.target_pattern
@@ -219,6 +276,89 @@ class SpinTorqueArrayVecEnv:
             raise RuntimeError("Environment must be reset before calling step")
         obs, rew, rew64, term, trunc = self.backend.step(torch.as_tensor(actions).t())
         return self._shape_obs(obs), rew, term.bool(), trunc.bool(), {"reward_f64": rew64, "energy": self.backend.energy}
+
+    def step_many(self, actions, autoreset: bool = False, out_every: bool = True, fused: Optional[bool] = None, out=None):
+        """K steps per call: actions [K, N, A].  Returns (obs [K, N, obs_dim], reward [K, N], terminated, truncated, info) -- with
+        out_every=False only the last step's outputs, leading dimension 1 (rewards are the last step's, not sums).
+
+        autoreset=False is K times step(), finished arrays stepping on as in the reference.  With autoreset=True an array that
+        terminates or truncates at step k reports that step's reward and flags, restarts from a device-side random pattern (keyed by
+        the device seed of the last reset(), its global index and its reset counter; target kept) and its obs row is the new episode's
+        first observation; info["done"] marks those entries and info["final_obs"] holds their terminal observations (the other
+        entries of final_obs are left as they were: NaN in a fresh tensor).
+
+        fused=None runs the single-launch kernel when the backend has one; fused=False (or a backend without step_many) composes the
+        same thing from step() and a masked reset() per step -- the specification of the fused path.  `out`: optional preallocated
+        backend-layout outputs (HipArrayBackend.many_outputs) to write into."""
+        if self._needs_reset:
+            raise RuntimeError("Environment must be reset before calling step_many")
+        if self.observation_mode == "dict":
+            raise ValueError("step_many returns stacked observations, which observation_mode 'dict' cannot hold: use 'array' or 'vector'")
+        a = torch.as_tensor(actions)
+        a_dim = 2 if self.action_mode == "global" else 3
+        if a.dim() != 3 or tuple(a.shape[1:]) != (self.num_envs, a_dim) or a.shape[0] < 1:
+            raise ValueError(f"expected actions of shape [K, {self.num_envs}, {a_dim}], got {tuple(a.shape)}")
+        a = a.permute(0, 2, 1)
+        if fused is None:
+            fused = hasattr(self.backend, "step_many")
+        if fused:
+            o = self.backend.step_many(a, out_every, autoreset, self._dev_seed, out)
+        else:
+            o = self._step_many_composed(a, bool(out_every), bool(autoreset), out)
+        term, trunc = o["terminated"].bool(), o["truncated"].bool()
+        info = {"reward_f64": o["reward64"], "energy": o["energy"]}
+        if autoreset:
+            info["final_obs"] = o["final_obs"].transpose(1, 2)
+            info["done"] = term | trunc
+        return o["obs"].transpose(1, 2), o["reward"], term, trunc, info
+
+    def _step_many_composed(self, a, out_every, autoreset, out):
+        """step_many from the single-step calls: per step backend.step, copy out, then -- with autoreset -- a masked random reset
+        of the finished arrays, whose observation columns replace the step's."""
+        b = self.backend
+        K = int(a.shape[0])
+        k_out = K if out_every else 1
+        dev = b.device
+        shapes = dict(obs=((b.obs_dim, self.num_envs), torch.float32), reward=((self.num_envs,), torch.float32),
+                      reward64=((self.num_envs,), torch.float64), energy=((self.num_envs,), torch.float64),
+                      terminated=((self.num_envs,), torch.uint8), truncated=((self.num_envs,), torch.uint8))
+        o = dict(out) if out is not None else {}
+        for name, (shape, dtype) in shapes.items():
+            if name not in o:
+                o[name] = torch.empty((k_out,) + shape, dtype=dtype, device=dev)
+        if autoreset and "final_obs" not in o:
+            o["final_obs"] = torch.full((k_out, b.obs_dim, self.num_envs), float("nan"), dtype=torch.float32, device=dev)
+        for k in range(K):
+            obs, rew, rew64, term, trunc = b.step(a[k])
+            emit = out_every or k == K - 1
+            slot = k if out_every else 0
+            if emit:
+                for name, t in (("obs", obs), ("reward", rew), ("reward64", rew64), ("energy", b.energy), ("terminated", term), ("truncated", trunc)):
+                    o[name][slot].copy_(t)
+            if autoreset:
+                done = (term | trunc).to(torch.uint8).clone()
+                step_obs = o["obs"][slot] if emit else None
+                new_obs = b.reset(done, None, None, self._dev_seed)
+                if emit:
+                    sel = done.bool().unsqueeze(0)
+                    o["final_obs"][slot].copy_(torch.where(sel, step_obs, o["final_obs"][slot]))
+                    o["obs"][slot].copy_(torch.where(sel, new_obs, step_obs))
+        return o
+
+    def state_dict(self):
+        """Everything a rollout needs to continue elsewhere: the device state (pattern, target, total energy, step count, reset
+        counters, as CPU tensors), the device seed of the last reset() and whether a reset is still due."""
+        st = {k: v.cpu() for k, v in self.backend.get_state().items()} if not self._needs_reset else {}
+        st["resets"] = self.backend.get_resets().cpu()
+        st["dev_seed"] = int(self._dev_seed)
+        st["needs_reset"] = bool(self._needs_reset)
+        return st
+
+    def load_state_dict(self, st):
+        """The inverse of state_dict() on an env of the same construction."""
+        self.backend.set_state(st.get("pattern"), st.get("target"), st.get("total_energy"), st.get("step_count"), st["resets"])
+        self._dev_seed = int(st["dev_seed"])
+        self._needs_reset = bool(st["needs_reset"])
 
     def get_state(self):
         return self.backend.get_state()
