@@ -88,6 +88,73 @@ __device__ __forceinline__ double cell_resistance(const V3& m_in, const ArrDev& 
 __device__ __forceinline__ int64_t obs_row_pattern(int obs_mode, int n, int d, int k) { return obs_mode == 0 ? d * 6 + k : d * 3 + k; }
 __device__ __forceinline__ int64_t obs_row_target(int obs_mode, int n, int d, int k) { return obs_mode == 0 ? d * 6 + 3 + k : 3 * n + d * 3 + k; }
 
+// ---- pieces of one step that every kernel shares, each stated once ------------------------------------------------------------------
+// Pure on values except the two that store; none holds a barrier or forms an address from a cell index.  Only uses that leave a kernel's
+// machine code as it was are taken (profiles/array_pieces_isa.txt): the action decode, the LDS coupling sum, the reset's draw and the
+// general kernel's dynamics block stay written out where they are, because sharing them changed the compiled kernels.
+
+// the four global values behind the pattern and target rows of a 'vector' observation (array_env.py:547-557): value K goes to row 6 n + K
+template <int K>
+__device__ __forceinline__ float vector_value(int32_t max_steps, double temperature, double sim, int32_t step, double etot) {
+    if (K == 0) return (float)sim;
+    if (K == 1) return (float)((double)(max_steps - step) / (double)max_steps);
+    if (K == 2) return (float)(etot / 1e-12);
+    return (float)(temperature / 300.0);
+}
+__device__ __forceinline__ void vector_rows(const ArrArgs& a, float* dst, int n, int64_t i, double sim, int32_t step, double etot) {
+    const int64_t N = a.N;
+    dst[(int64_t)(6 * n + 0) * N + i] = vector_value<0>(a.max_steps, a.temperature, sim, step, etot);
+    dst[(int64_t)(6 * n + 1) * N + i] = vector_value<1>(a.max_steps, a.temperature, sim, step, etot);
+    dst[(int64_t)(6 * n + 2) * N + i] = vector_value<2>(a.max_steps, a.temperature, sim, step, etot);
+    dst[(int64_t)(6 * n + 3) * N + i] = vector_value<3>(a.max_steps, a.temperature, sim, step, etot);
+}
+
+// _simulate_device_dynamics (array_env.py:496-521): alpha = 0.01, gamma = 2.21e5, p_hat = z; ONE derivative at m0 in the field h, then ten
+// normalised Euler sub-steps of it
+__device__ __forceinline__ V3 euler_cell(const V3& m0, const V3& h, double J, double T) {
+    const V3 mxp{m0.y, -m0.x, 0.0};
+    const V3 t2 = cross(m0, mxp);
+    const double tj = 0.1 * J;
+    const V3 mxh = cross(m0, h);
+    V3 dm{-2.21e5 * mxh.x, -2.21e5 * mxh.y, -2.21e5 * mxh.z};
+    const V3 mxdm = cross(m0, dm);
+    dm = V3{dm.x + 0.01 * mxdm.x + tj * t2.x, dm.y + 0.01 * mxdm.y + tj * t2.y, dm.z + 0.01 * mxdm.z + tj * t2.z};
+    const double dt = T / 10;
+    V3 m = m0;
+#pragma unroll
+    for (int it = 0; it < 10; ++it) {
+        m = V3{m.x + dm.x * dt, m.y + dm.y * dt, m.z + dm.z * dt};
+        const double inv = rsqrt_fast(dot(m, m));               // m / |m| (array_env.py:518), <= 2 ulp per component
+        m = V3{m.x * inv, m.y * inv, m.z * inv};
+    }
+    return m;
+}
+
+// a driven cell's energy, with the resistance of the UPDATED state m (current_m is a view of the pattern, array_env.py:455-463)
+__device__ __forceinline__ double cell_energy(const V3& m, double J, double T, const ArrDev& dev) {
+    const double r = cell_resistance(m, dev);
+    const double v = J * r * dev.area;
+    return (v * v) / r * T;
+}
+
+// default reward (array_env.py:183-224): pattern match, energy (sign as written), progress, uniformity
+__device__ __forceinline__ double default_reward(double sim, double prev_sim, bool is_success, double e_total, double uniformity, double w_energy) {
+    double reward = 10.0 * (is_success ? 10.0 : sim * 5.0);
+    reward += (-w_energy) * (-e_total / 1e-12);
+    reward += (sim - prev_sim);
+    reward += 2.0 * uniformity;
+    return reward;
+}
+
+// the per-array outputs of one step, at element o of each
+__device__ __forceinline__ void write_step_outputs(const ArrArgs& a, int64_t o, double reward, double e_total, bool is_success, bool truncated) {
+    a.reward[o] = (float)reward;
+    if (a.reward64) a.reward64[o] = reward;
+    if (a.energy) a.energy[o] = e_total;
+    a.term[o] = is_success ? 1 : 0;
+    a.trunc[o] = truncated ? 1 : 0;
+}
+
 // NDEV > 0: the number of cells is a compile-time constant and the coupling sum unrolls (4 x 4, the registered
 // SpinTorqueArray-v0: 'global' mode 0.178 -> 0.167 ms per launch at 262 144 arrays, 'row' / 'column' unchanged).
 // (Round 3, measured and rejected: a software-pipelined sweep that forms the coupling sum of the NEXT addressed cell -- all
@@ -106,6 +173,8 @@ __global__ void __launch_bounds__(64) stg_array_step_kernel(const ArrArgs a) {
     const int64_t i = (int64_t)blockIdx.x * 64 + lane;
     const bool in_range = i < a.N;
     const int64_t N = a.N;
+    // The similarity is a running sum, formed here and corrected by each updated cell's change; the fused kernel forms it from scratch
+    // every step instead.  The two differ at rounding level and each is pinned by its tests: behaviour, not duplication.
     // ONE pass over the state: pattern -> LDS, target -> its observation rows, and the similarity sum on the fly
     // (np.mean of the per-cell dot products, array_env.py:523-531); the target is not touched again except for the
     // addressed cells.
@@ -163,7 +232,7 @@ __global__ void __launch_bounds__(64) stg_array_step_kernel(const ArrArgs a) {
                 }
                 h = V3{h.x + hc.x, h.y + hc.y, h.z + hc.z};
             }
-            // _simulate_device_dynamics (array_env.py:496-521): alpha = 0.01, gamma = 2.21e5, p_hat = z
+            // euler_cell, written out: as a call it compiled with one multiply's operands swapped in the similarity update below
             const V3 mxp{m0.y, -m0.x, 0.0};
             const V3 t2 = cross(m0, mxp);
             const double tj = 0.1 * J;
@@ -187,9 +256,7 @@ __global__ void __launch_bounds__(64) stg_array_step_kernel(const ArrArgs a) {
             const V3 tg{a.target[(int64_t)(d * 3) * N + i], a.target[(int64_t)(d * 3 + 1) * N + i], a.target[(int64_t)(d * 3 + 2) * N + i]};
             sim_sum += dot(m, tg) - dot(m0, tg);
             // energy with the resistance of the UPDATED state (current_m is a view of the pattern, array_env.py:455-463)
-            const double r = cell_resistance(m, a.dev);
-            const double v = J * r * a.dev.area;
-            e_total += (v * v) / r * T;
+            e_total += cell_energy(m, J, T, a.dev);
         }
     }
     const double etot = a.etot[i] + e_total;
@@ -215,22 +282,15 @@ __global__ void __launch_bounds__(64) stg_array_step_kernel(const ArrArgs a) {
         var += dv * dv;
     }
     if (a.obs_mode == 1) {
-        a.obs[(int64_t)(6 * n + 0) * N + i] = (float)sim;
-        a.obs[(int64_t)(6 * n + 1) * N + i] = (float)((double)(a.max_steps - step) / (double)a.max_steps);
-        a.obs[(int64_t)(6 * n + 2) * N + i] = (float)(etot / 1e-12);
-        a.obs[(int64_t)(6 * n + 3) * N + i] = (float)(a.temperature / 300.0);
+        a.obs[(int64_t)(6 * n + 0) * N + i] = vector_value<0>(a.max_steps, a.temperature, sim, step, etot);
+        a.obs[(int64_t)(6 * n + 1) * N + i] = vector_value<1>(a.max_steps, a.temperature, sim, step, etot);
+        a.obs[(int64_t)(6 * n + 2) * N + i] = vector_value<2>(a.max_steps, a.temperature, sim, step, etot);
+        a.obs[(int64_t)(6 * n + 3) * N + i] = vector_value<3>(a.max_steps, a.temperature, sim, step, etot);
     }
     const double uniformity = fmax(0.0, 1.0 - sqrt(var / n));
     // default reward (array_env.py:183-224): pattern match, energy (sign as written), progress, uniformity
-    double reward = 10.0 * (is_success ? 10.0 : sim * 5.0);
-    reward += (-a.w_energy) * (-e_total / 1e-12);
-    reward += (sim - prev_sim);
-    reward += 2.0 * uniformity;
-    a.reward[i] = (float)reward;
-    if (a.reward64) a.reward64[i] = reward;
-    if (a.energy) a.energy[i] = e_total;
-    a.term[i] = is_success ? 1 : 0;
-    a.trunc[i] = step >= a.max_steps ? 1 : 0;
+    const double reward = default_reward(sim, prev_sim, is_success, e_total, uniformity, a.w_energy);
+    write_step_outputs(a, i, reward, e_total, is_success, step >= a.max_steps);
 }
 
 // 'global' action mode on NDEV cells (4 x 4, the registered SpinTorqueArray-v0): every cell is addressed, in order.  The whole pattern
@@ -308,22 +368,7 @@ __global__ void __launch_bounds__(256, 3) stg_array_step_global_kernel(const Arr
                 }
                 h = V3{h.x + hc.x, h.y + hc.y, h.z + hc.z};
             }
-            // _simulate_device_dynamics (array_env.py:496-521): alpha = 0.01, gamma = 2.21e5, p_hat = z
-            const V3 mxp{m0.y, -m0.x, 0.0};
-            const V3 t2 = cross(m0, mxp);
-            const double tj = 0.1 * J;
-            const V3 mxh = cross(m0, h);
-            V3 dm{-2.21e5 * mxh.x, -2.21e5 * mxh.y, -2.21e5 * mxh.z};
-            const V3 mxdm = cross(m0, dm);
-            dm = V3{dm.x + 0.01 * mxdm.x + tj * t2.x, dm.y + 0.01 * mxdm.y + tj * t2.y, dm.z + 0.01 * mxdm.z + tj * t2.z};
-            const double dt = T / 10;
-            V3 m = m0;
-#pragma unroll
-            for (int it = 0; it < 10; ++it) {
-                m = V3{m.x + dm.x * dt, m.y + dm.y * dt, m.z + dm.z * dt};
-                const double inv = rsqrt_fast(dot(m, m));       // m / |m| (array_env.py:518), <= 2 ulp per component
-                m = V3{m.x * inv, m.y * inv, m.z * inv};
-            }
+            const V3 m = euler_cell(m0, h, J, T);
             stp(d * 3, m.x);
             stp(d * 3 + 1, m.y);
             stp(d * 3 + 2, m.z);
@@ -331,9 +376,7 @@ __global__ void __launch_bounds__(256, 3) stg_array_step_global_kernel(const Arr
             const V3 tg{ldt(d * 3), ldt(d * 3 + 1), ldt(d * 3 + 2)};
             sim_sum += dot(m, tg) - dot(m0, tg);
             // energy with the resistance of the UPDATED state (current_m is a view of the pattern, array_env.py:455-463)
-            const double r = cell_resistance(m, a.dev);
-            const double v = J * r * a.dev.area;
-            e_total += (v * v) / r * T;
+            e_total += cell_energy(m, J, T, a.dev);
             // rotate: cell d (updated) goes to the end, cell d+1 to the front
 #pragma unroll
             for (int k = 0; k + 1 < n; ++k) pm[k] = pm[k + 1];
@@ -364,22 +407,15 @@ __global__ void __launch_bounds__(256, 3) stg_array_step_global_kernel(const Arr
         var += dv * dv;
     }
     if (a.obs_mode == 1) {
-        sto(6 * n + 0, (float)sim);
-        sto(6 * n + 1, (float)((double)(a.max_steps - step) / (double)a.max_steps));
-        sto(6 * n + 2, (float)(etot / 1e-12));
-        sto(6 * n + 3, (float)(a.temperature / 300.0));
+        sto(6 * n + 0, vector_value<0>(a.max_steps, a.temperature, sim, step, etot));
+        sto(6 * n + 1, vector_value<1>(a.max_steps, a.temperature, sim, step, etot));
+        sto(6 * n + 2, vector_value<2>(a.max_steps, a.temperature, sim, step, etot));
+        sto(6 * n + 3, vector_value<3>(a.max_steps, a.temperature, sim, step, etot));
     }
     const double uniformity = fmax(0.0, 1.0 - sqrt(var / n));
     // default reward (array_env.py:183-224): pattern match, energy (sign as written), progress, uniformity
-    double reward = 10.0 * (is_success ? 10.0 : sim * 5.0);
-    reward += (-a.w_energy) * (-e_total / 1e-12);
-    reward += (sim - prev_sim);
-    reward += 2.0 * uniformity;
-    a.reward[i] = (float)reward;
-    if (a.reward64) a.reward64[i] = reward;
-    if (a.energy) a.energy[i] = e_total;
-    a.term[i] = is_success ? 1 : 0;
-    a.trunc[i] = step >= a.max_steps ? 1 : 0;
+    const double reward = default_reward(sim, prev_sim, is_success, e_total, uniformity, a.w_energy);
+    write_step_outputs(a, i, reward, e_total, is_success, step >= a.max_steps);
 }
 
 // 'individual' action mode (one addressed cell per step): nothing but that one cell changes, so the step is ONE streaming
@@ -436,22 +472,7 @@ __global__ void __launch_bounds__(256) stg_array_step_individual_kernel(const Ar
     if (drive) {
         V3 h = device_field(m0, a.dev);
         if (a.include_coupling) h = V3{h.x + hc.x, h.y + hc.y, h.z + hc.z};
-        // _simulate_device_dynamics (array_env.py:496-521): alpha = 0.01, gamma = 2.21e5, p_hat = z
-        const V3 mxp{m0.y, -m0.x, 0.0};
-        const V3 t2 = cross(m0, mxp);
-        const double tj = 0.1 * J;
-        const V3 mxh = cross(m0, h);
-        V3 dm{-2.21e5 * mxh.x, -2.21e5 * mxh.y, -2.21e5 * mxh.z};
-        const V3 mxdm = cross(m0, dm);
-        dm = V3{dm.x + 0.01 * mxdm.x + tj * t2.x, dm.y + 0.01 * mxdm.y + tj * t2.y, dm.z + 0.01 * mxdm.z + tj * t2.z};
-        const double dt = T / 10;
-        V3 m = m0;
-#pragma unroll
-        for (int it = 0; it < 10; ++it) {
-            m = V3{m.x + dm.x * dt, m.y + dm.y * dt, m.z + dm.z * dt};
-            const double inv = rsqrt_fast(dot(m, m));           // m / |m| (array_env.py:518), <= 2 ulp per component
-            m = V3{m.x * inv, m.y * inv, m.z * inv};
-        }
+        const V3 m = euler_cell(m0, h, J, T);
         a.pattern[(int64_t)(d * 3) * N + i] = m.x;
         a.pattern[(int64_t)(d * 3 + 1) * N + i] = m.y;
         a.pattern[(int64_t)(d * 3 + 2) * N + i] = m.z;
@@ -462,9 +483,7 @@ __global__ void __launch_bounds__(256) stg_array_step_individual_kernel(const Ar
         const double e_new = sqrt(dot(m, m)) - 1.0;
         se += e_new - e_d; se2 += e_new * e_new - e_d * e_d;
         // energy with the resistance of the UPDATED state (current_m is a view of the pattern, array_env.py:455-463)
-        const double r = cell_resistance(m, a.dev);
-        const double v = J * r * a.dev.area;
-        e_total = (v * v) / r * T;
+        e_total = cell_energy(m, J, T, a.dev);
     }
     const double etot = a.etot[i] + e_total;
     const int32_t step = a.step[i] + 1;
@@ -472,25 +491,13 @@ __global__ void __launch_bounds__(256) stg_array_step_individual_kernel(const Ar
     a.step[i] = step;
     const double sim = sim_sum / n;
     const bool is_success = sim >= a.thr;
-    if (a.obs_mode == 1) {
-        a.obs[(int64_t)(6 * n + 0) * N + i] = (float)sim;
-        a.obs[(int64_t)(6 * n + 1) * N + i] = (float)((double)(a.max_steps - step) / (double)a.max_steps);
-        a.obs[(int64_t)(6 * n + 2) * N + i] = (float)(etot / 1e-12);
-        a.obs[(int64_t)(6 * n + 3) * N + i] = (float)(a.temperature / 300.0);
-    }
+    if (a.obs_mode == 1) vector_rows(a, a.obs, n, i, sim, step, etot);
     // uniformity = 1 - population std of the cell norms (array_env.py:216-224)
     const double me = se / n;
     const double var = fmax(se2 / n - me * me, 0.0);
     const double uniformity = fmax(0.0, 1.0 - sqrt(var));
-    double reward = 10.0 * (is_success ? 10.0 : sim * 5.0);                            // array_env.py:183-224
-    reward += (-a.w_energy) * (-e_total / 1e-12);
-    reward += (sim - prev_sim);
-    reward += 2.0 * uniformity;
-    a.reward[i] = (float)reward;
-    if (a.reward64) a.reward64[i] = reward;
-    if (a.energy) a.energy[i] = e_total;
-    a.term[i] = is_success ? 1 : 0;
-    a.trunc[i] = step >= a.max_steps ? 1 : 0;
+    const double reward = default_reward(sim, prev_sim, is_success, e_total, uniformity, a.w_energy);
+    write_step_outputs(a, i, reward, e_total, is_success, step >= a.max_steps);
 }
 
 struct ArrResetArgs {
@@ -557,10 +564,10 @@ __global__ void __launch_bounds__(64) stg_array_reset_kernel(const ArrResetArgs 
                 a.obs[(int64_t)q * N + i] = (float)a.pattern[(int64_t)q * N + i];
                 a.obs[(int64_t)(3 * n + q) * N + i] = (float)a.target[(int64_t)q * N + i];
             }
-            a.obs[(int64_t)(6 * n + 0) * N + i] = (float)sim;
-            a.obs[(int64_t)(6 * n + 1) * N + i] = (float)((double)(a.max_steps - a.step[i]) / (double)a.max_steps);
-            a.obs[(int64_t)(6 * n + 2) * N + i] = (float)(a.etot[i] / 1e-12);
-            a.obs[(int64_t)(6 * n + 3) * N + i] = (float)(a.temperature / 300.0);
+            a.obs[(int64_t)(6 * n + 0) * N + i] = vector_value<0>(a.max_steps, a.temperature, sim, a.step[i], a.etot[i]);
+            a.obs[(int64_t)(6 * n + 1) * N + i] = vector_value<1>(a.max_steps, a.temperature, sim, a.step[i], a.etot[i]);
+            a.obs[(int64_t)(6 * n + 2) * N + i] = vector_value<2>(a.max_steps, a.temperature, sim, a.step[i], a.etot[i]);
+            a.obs[(int64_t)(6 * n + 3) * N + i] = vector_value<3>(a.max_steps, a.temperature, sim, a.step[i], a.etot[i]);
         }
     }
 }
@@ -617,15 +624,6 @@ __device__ __forceinline__ void many_copy_rows(const ArrArgs& a, const double* l
     }
 }
 
-// the four global values behind the pattern and target rows of a 'vector' observation (array_env.py:547-557)
-__device__ __forceinline__ void many_vector_rows(const ArrArgs& a, float* dst, int n, int64_t i, double sim, int32_t step, double etot) {
-    const int64_t N = a.N;
-    dst[(int64_t)(6 * n + 0) * N + i] = (float)sim;
-    dst[(int64_t)(6 * n + 1) * N + i] = (float)((double)(a.max_steps - step) / (double)a.max_steps);
-    dst[(int64_t)(6 * n + 2) * N + i] = (float)(etot / 1e-12);
-    dst[(int64_t)(6 * n + 3) * N + i] = (float)(a.temperature / 300.0);
-}
-
 // One addressed cell, in place in LDS: effective field with the coupling sum over the current pattern, ten normalised Euler sub-steps of
 // one derivative (array_env.py:478-521).  Returns the cell's energy, with the resistance of the UPDATED state (array_env.py:455-463).
 template <int NDEV>
@@ -641,26 +639,9 @@ __device__ __forceinline__ double many_update_cell(const ArrArgs& a, double* lp,
         }
         h = V3{h.x + hc.x, h.y + hc.y, h.z + hc.z};
     }
-    // _simulate_device_dynamics (array_env.py:496-521): alpha = 0.01, gamma = 2.21e5, p_hat = z
-    const V3 mxp{m0.y, -m0.x, 0.0};
-    const V3 t2 = cross(m0, mxp);
-    const double tj = 0.1 * J;
-    const V3 mxh = cross(m0, h);
-    V3 dm{-2.21e5 * mxh.x, -2.21e5 * mxh.y, -2.21e5 * mxh.z};
-    const V3 mxdm = cross(m0, dm);
-    dm = V3{dm.x + 0.01 * mxdm.x + tj * t2.x, dm.y + 0.01 * mxdm.y + tj * t2.y, dm.z + 0.01 * mxdm.z + tj * t2.z};
-    const double dt = T / 10;
-    V3 m = m0;
-#pragma unroll
-    for (int it = 0; it < 10; ++it) {
-        m = V3{m.x + dm.x * dt, m.y + dm.y * dt, m.z + dm.z * dt};
-        const double inv = rsqrt_fast(dot(m, m));               // m / |m| (array_env.py:518), <= 2 ulp per component
-        m = V3{m.x * inv, m.y * inv, m.z * inv};
-    }
+    const V3 m = euler_cell(m0, h, J, T);
     lp[(d * 3) * 64 + lane] = m.x; lp[(d * 3 + 1) * 64 + lane] = m.y; lp[(d * 3 + 2) * 64 + lane] = m.z;
-    const double r = cell_resistance(m, a.dev);
-    const double v = J * r * a.dev.area;
-    return (v * v) / r * T;
+    return cell_energy(m, J, T, a.dev);
 }
 
 // stg_array_reset_kernel's random draw for one array (same stream key, same normalisation), into the array's LDS column
@@ -747,19 +728,11 @@ __global__ void __launch_bounds__(64) stg_array_step_many_kernel(const ArrManyAr
         }
         const double uniformity = fmax(0.0, 1.0 - sqrt(var / n));
         // default reward (array_env.py:183-224): pattern match, energy (sign as written), progress, uniformity
-        double reward = 10.0 * (is_success ? 10.0 : sim * 5.0);
-        reward += (-a.w_energy) * (-e_total / 1e-12);
-        reward += (sim - prev_sim);
-        reward += 2.0 * uniformity;
+        const double reward = default_reward(sim, prev_sim, is_success, e_total, uniformity, a.w_energy);
         const bool truncated = step >= a.max_steps;
         if (emit) {
-            if (a.obs_mode == 1) many_vector_rows(a, obs, n, i, sim, step, etot);
-            const int64_t o = slot * N + i;
-            a.reward[o] = (float)reward;
-            if (a.reward64) a.reward64[o] = reward;
-            if (a.energy) a.energy[o] = e_total;
-            a.term[o] = is_success ? 1 : 0;
-            a.trunc[o] = truncated ? 1 : 0;
+            if (a.obs_mode == 1) vector_rows(a, obs, n, i, sim, step, etot);
+            write_step_outputs(a, slot * N + i, reward, e_total, is_success, truncated);
         }
         if (b.autoreset && (is_success || truncated)) {
             // the step above reported the finished episode; its terminal observation goes to final_obs and the array restarts as
@@ -767,7 +740,7 @@ __global__ void __launch_bounds__(64) stg_array_step_many_kernel(const ArrManyAr
             if (emit && b.final_obs) {
                 float* fo = b.final_obs + slot * obs_rows * N;
                 many_copy_rows(a, lp, lane, n, i, fo);
-                if (a.obs_mode == 1) many_vector_rows(a, fo, n, i, sim, step, etot);
+                if (a.obs_mode == 1) vector_rows(a, fo, n, i, sim, step, etot);
             }
             const uint32_t rs = b.resets[i];
             many_draw_pattern(lp, lane, n, b.seed, (uint64_t)(b.env_id0 + i), rs);
@@ -775,7 +748,7 @@ __global__ void __launch_bounds__(64) stg_array_step_many_kernel(const ArrManyAr
             etot = 0.0;
             step = 0;
             sim_sum = many_pass(a, lp, lane, n, i, obs, norm_sum);
-            if (emit && a.obs_mode == 1) many_vector_rows(a, obs, n, i, sim_sum / n, step, etot);
+            if (emit && a.obs_mode == 1) vector_rows(a, obs, n, i, sim_sum / n, step, etot);
         }
     }
     for (int q = 0; q < 3 * n; ++q) a.pattern[(int64_t)q * N + i] = lp[q * 64 + lane];
@@ -809,6 +782,28 @@ struct stg_array_ctx {
                               // 2 the 4 x 4 kernel with the pattern in LDS in 'global' mode too
 };
 
+// LDS per workgroup: the coupling matrix alone (streaming and register kernels), and behind one wavefront's pattern [n*3][64] (the general
+// and the fused kernel: 26 KB at 4 x 4, 128 KB at 8 x 8)
+static size_t coupling_bytes(const stg_array_config& c) {
+    const size_t n = (size_t)c.rows * c.cols;
+    return c.include_coupling ? sizeof(double) * n * n : 0;
+}
+static size_t lds_bytes(const stg_array_config& c) { return sizeof(double) * ((size_t)c.rows * c.cols * 3 * 64) + coupling_bytes(c); }
+
+// one step's kernel arguments: the context's configuration and state, the caller's actions and outputs
+static ArrArgs fill_args(const stg_array_ctx* ctx, const float* actions, float* obs, float* reward, double* reward_f64, double* energy,
+                         uint8_t* terminated, uint8_t* truncated) {
+    const stg_array_config& c = ctx->cfg;
+    ArrArgs a{};
+    a.N = ctx->N; a.rows = c.rows; a.cols = c.cols; a.mode = c.action_mode; a.include_coupling = c.include_coupling;
+    a.max_steps = c.max_steps; a.obs_mode = c.obs_mode; a.max_current = c.max_current; a.max_duration = c.max_duration;
+    a.thr = c.success_threshold; a.w_energy = c.energy_penalty_weight; a.temperature = c.temperature; a.dev = ctx->dev;
+    a.coupling = ctx->coupling; a.pattern = ctx->pattern; a.target = ctx->target; a.etot = ctx->etot; a.step = ctx->step;
+    a.actions = actions; a.obs = obs; a.reward = reward; a.reward64 = reward_f64; a.energy = energy; a.term = terminated;
+    a.trunc = truncated;
+    return a;
+}
+
 extern "C" {
 
 int stg_array_create(stg_array_ctx** out, int device_id, int64_t n_arrays, int64_t env_id0, const stg_array_config* cfg,
@@ -831,11 +826,15 @@ int stg_array_create(stg_array_ctx** out, int device_id, int64_t n_arrays, int64
     if (!c) return afail(STG_E_NOMEM, "out of host memory");
     c->device = device_id; c->N = n_arrays; c->env_id0 = env_id0; c->cfg = *cfg;
     if (const char* e = std::getenv("STG_ARRAY_VARIANT")) c->variant = std::atoi(e);
-    (void)hipDeviceGetAttribute(&c->lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device_id);
-    {   // stg_array_step_many's launch above 48 KB of LDS needs the opt-in once; here, so that the call itself only enqueues
-        const size_t lds_many = sizeof(double) * ((size_t)n * 3 * 64 + (cfg->include_coupling ? (size_t)n * n : 0));
-        if (n != 16 && lds_many > 48 * 1024 && lds_many <= (size_t)c->lds_max) {
-            hipError_t ea = hipFuncSetAttribute((const void*)stg_array_step_many_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_many);
+    {
+        hipError_t eq = hipDeviceGetAttribute(&c->lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device_id);
+        if (eq != hipSuccess) { delete c; return afail(STG_E_HIP, std::string("hipDeviceGetAttribute: ") + hipGetErrorString(eq)); }
+    }
+    // A launch of the generic LDS kernels above 48 KB of LDS needs the opt-in once; here, so that a step call only enqueues.  The limit is
+    // per kernel, not per context, so it is raised to the device's: a later context with smaller arrays must not lower it again.
+    if (const size_t need = lds_bytes(*cfg); need > 48 * 1024 && need <= (size_t)c->lds_max) {
+        for (const void* k : {(const void*)stg_array_step_kernel<0>, (const void*)stg_array_step_many_kernel<0>}) {
+            hipError_t ea = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_max);
             if (ea != hipSuccess) { delete c; return afail(STG_E_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(ea)); }
         }
     }
@@ -900,38 +899,22 @@ int stg_array_step(stg_array_ctx* ctx, const float* actions, float* obs, float* 
     if (!actions || !obs || !reward || !terminated || !truncated) return afail(STG_E_INVALID, "actions/obs/reward/terminated/truncated must not be NULL");
     AHIP_TRY(hipSetDevice(ctx->device));
     const stg_array_config& c = ctx->cfg;
-    ArrArgs a{};
-    a.N = ctx->N; a.rows = c.rows; a.cols = c.cols; a.mode = c.action_mode; a.include_coupling = c.include_coupling;
-    a.max_steps = c.max_steps; a.obs_mode = c.obs_mode; a.max_current = c.max_current; a.max_duration = c.max_duration;
-    a.thr = c.success_threshold; a.w_energy = c.energy_penalty_weight; a.temperature = c.temperature; a.dev = ctx->dev;
-    a.coupling = ctx->coupling; a.pattern = ctx->pattern; a.target = ctx->target; a.etot = ctx->etot; a.step = ctx->step;
-    a.actions = actions; a.obs = obs; a.reward = reward; a.reward64 = reward_f64; a.energy = energy; a.term = terminated;
-    a.trunc = truncated;
+    const ArrArgs a = fill_args(ctx, actions, obs, reward, reward_f64, energy, terminated, truncated);
     const int n = c.rows * c.cols;
+    const hipStream_t st = (hipStream_t)stream;
+    const dim3 grid256((unsigned)((ctx->N + 255) / 256)), grid64((unsigned)((ctx->N + 63) / 64));
     if (c.action_mode == 0) {
         // one addressed cell per step: streaming kernel, only the coupling matrix in LDS (<= 32 KB at 8 x 8)
-        const size_t lds_c = c.include_coupling ? sizeof(double) * (size_t)n * n : 0;
-        hipLaunchKernelGGL(stg_array_step_individual_kernel, dim3((unsigned)((ctx->N + 255) / 256)), dim3(256), lds_c,
-                           (hipStream_t)stream, a);
-        AHIP_TRY(hipGetLastError());
-        return STG_OK;
-    }
-    if (c.action_mode == 3 && n == 16 && ctx->variant >= 1 && ctx->variant != 2 && ctx->N <= (4ll << 20)) {
-        // 'global' mode on 4 x 4 arrays: fully unrolled sweep, pattern in registers (STG_ARRAY_VARIANT=2: the LDS form of this size)
-        const size_t lds_c = c.include_coupling ? sizeof(double) * (size_t)n * n : 0;
-        hipLaunchKernelGGL((stg_array_step_global_kernel<16>), dim3((unsigned)((ctx->N + 255) / 256)), dim3(256), lds_c, (hipStream_t)stream, a);
-        AHIP_TRY(hipGetLastError());
-        return STG_OK;
-    }
-    const size_t lds = sizeof(double) * ((size_t)n * 3 * 64 + (c.include_coupling ? (size_t)n * n : 0));
-    const dim3 grid((unsigned)((ctx->N + 63) / 64));
-    if (n == 16 && ctx->variant != 0) {
+        hipLaunchKernelGGL(stg_array_step_individual_kernel, grid256, dim3(256), coupling_bytes(c), st, a);
+    } else if (c.action_mode == 3 && n == 16 && ctx->variant >= 1 && ctx->variant != 2 && ctx->N <= (4ll << 20)) {
+        // 'global' mode on 4 x 4 arrays: pattern in registers (STG_ARRAY_VARIANT=2: the LDS form of this size).  The kernel's buffer
+        // descriptors hold 32-bit sizes: up to 4 M arrays.
+        hipLaunchKernelGGL((stg_array_step_global_kernel<16>), grid256, dim3(256), coupling_bytes(c), st, a);
+    } else if (n == 16 && ctx->variant != 0) {
         // 4 x 4 arrays (the registered SpinTorqueArray-v0): the coupling sum unrolled
-        hipLaunchKernelGGL((stg_array_step_kernel<16>), grid, dim3(64), lds, (hipStream_t)stream, a);
+        hipLaunchKernelGGL((stg_array_step_kernel<16>), grid64, dim3(64), lds_bytes(c), st, a);
     } else {
-        if (lds > 48 * 1024)
-            AHIP_TRY(hipFuncSetAttribute((const void*)stg_array_step_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((stg_array_step_kernel<0>), grid, dim3(64), lds, (hipStream_t)stream, a);
+        hipLaunchKernelGGL((stg_array_step_kernel<0>), grid64, dim3(64), lds_bytes(c), st, a);
     }
     AHIP_TRY(hipGetLastError());
     return STG_OK;
@@ -960,19 +943,12 @@ int stg_array_step_many(stg_array_ctx* ctx, int32_t K, const float* actions, int
     AHIP_TRY(hipSetDevice(ctx->device));
     const stg_array_config& c = ctx->cfg;
     const int n = c.rows * c.cols;
-    // pattern [n*3][64] and the coupling matrix: 26 KB at 4 x 4, 128 KB at 8 x 8 -- checked against the device before anything is launched
-    const size_t lds = sizeof(double) * ((size_t)n * 3 * 64 + (c.include_coupling ? (size_t)n * n : 0));
+    const size_t lds = lds_bytes(c);           // checked against the device before anything is launched
     if (lds > (size_t)ctx->lds_max)
         return afail(STG_E_INVALID, "stg_array_step_many: the array's pattern and coupling matrix (" + std::to_string(lds) +
                                         " bytes per workgroup) do not fit the device's LDS (" + std::to_string(ctx->lds_max) + ")");
     ArrManyArgs b{};
-    ArrArgs& a = b.s;
-    a.N = ctx->N; a.rows = c.rows; a.cols = c.cols; a.mode = c.action_mode; a.include_coupling = c.include_coupling;
-    a.max_steps = c.max_steps; a.obs_mode = c.obs_mode; a.max_current = c.max_current; a.max_duration = c.max_duration;
-    a.thr = c.success_threshold; a.w_energy = c.energy_penalty_weight; a.temperature = c.temperature; a.dev = ctx->dev;
-    a.coupling = ctx->coupling; a.pattern = ctx->pattern; a.target = ctx->target; a.etot = ctx->etot; a.step = ctx->step;
-    a.actions = actions; a.obs = obs; a.reward = reward; a.reward64 = reward_f64; a.energy = energy; a.term = terminated;
-    a.trunc = truncated;
+    b.s = fill_args(ctx, actions, obs, reward, reward_f64, energy, terminated, truncated);
     b.env_id0 = ctx->env_id0; b.K = K; b.out_every = out_every ? 1 : 0; b.autoreset = autoreset ? 1 : 0; b.seed = seed;
     b.resets = ctx->resets; b.final_obs = final_obs;
     const dim3 grid((unsigned)((ctx->N + 63) / 64));

@@ -338,6 +338,49 @@ def test_nan_duration_lanes_in_a_rollout(stg):
     assert np.isfinite(f["pattern"]).all() and np.isfinite(f["total_energy"]).all()
 
 
+def test_nan_index_lanes_in_a_rollout(stg):
+    """3 x 5 'row', K = 3, max_steps = 3, auto-reset, N = 65 (one wavefront and one ragged lane): four driven lanes carry a NaN row index at
+    step 1.  A NaN index addresses nothing: at that step those lanes' pattern stays as it was and their energy is 0, where the same lanes
+    with an ordinary index move and spend energy; nothing is NaN.  The fused launch agrees with the composed path everywhere, and every
+    other lane is bit-identical to a run without the NaN indices.  (The four lanes start close to the opposite of the target, so none of
+    them finishes before step 2 and no restart hides the comparison.)"""
+    n, shape, K = 65, (3, 5), 3
+    lanes = [0, 31, 63, 64]
+    n3 = 3 * shape[0] * shape[1]
+    rng = np.random.default_rng(10)
+    init = _unit(rng, n, *shape)
+    tilted = -stg.array_env.checkerboard_pattern(*shape) + 0.1 * _unit(rng, len(lanes), *shape)
+    init[lanes] = tilted / np.linalg.norm(tilted, axis=-1, keepdims=True)
+    ordinary = np.stack([_actions(rng, n, shape, "row", s) for s in range(K)])
+    ordinary[:, lanes, 1] = 1.5e6                      # driven: only the index keeps the cells from moving
+    ordinary[:, lanes, 2] = 5e-10
+    special = ordinary.copy()
+    special[1, lanes, 0] = np.nan
+    runs = {}
+    for name, acts, fused in (("fused", special, True), ("composed", special, False), ("plain", ordinary, True)):
+        env = stg.SpinTorqueArrayVecEnv(n, shape, action_mode="row", coupling_strength=0.2, observation_mode="vector",
+                                        success_threshold=_finish_threshold(15), max_steps=3)
+        env.reset(seed=4, options={"initial_pattern": init})
+        runs[name] = _many(env, acts, autoreset=True, fused=fused)
+        env.close()
+    f, c, p = runs["fused"], runs["composed"], runs["plain"]
+    others = np.setdiff1d(np.arange(n), lanes)
+    _same_bits({k: f[k][:, others] if k in BITWISE else f[k][..., others] for k in BITWISE + STATE},
+               {k: p[k][:, others] if k in BITWISE else p[k][..., others] for k in BITWISE + STATE}, BITWISE + STATE, "other lanes")
+    for key in ("term", "trunc", "done", "step_count", "resets", "target"):
+        assert np.array_equal(f[key], c[key]), key
+    _outputs_close(f, c, "fused against composed")
+    _state_close(f, c, "fused against composed")
+    sp = np.array(lanes)
+    assert not f["done"][:2, sp].any() and f["trunc"][2, sp].all()
+    for r in (f, c):
+        assert np.array_equal(r["obs"][1, sp, :n3], r["obs"][0, sp, :n3])                         # pattern rows: nothing moved at step 1
+        assert (r["energy"][1, sp] == 0.0).all() and (r["energy"][0, sp] > 0.0).all()
+        for key in ("obs", "reward", "energy", "pattern", "total_energy"):
+            assert np.isfinite(r[key]).all(), key
+    assert (p["energy"][1, sp] > 0.0).all() and (p["obs"][1, sp, :n3] != p["obs"][0, sp, :n3]).any(axis=1).all()
+
+
 # ------------------------------------------------------------------------------------------------
 # f. set_state / get_resets, rejected arguments
 # ------------------------------------------------------------------------------------------------
