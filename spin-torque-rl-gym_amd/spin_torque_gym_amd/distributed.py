@@ -32,7 +32,7 @@ import torch
 import torch.distributed as dist
 
 from .backend import RECORD_BYTES, record_views
-from .envs import SpinTorqueVecEnv, _TimerTable
+from .envs import STATE_TENSORS, SpinTorqueVecEnv, _TimerTable, assemble_state, check_state_config, state_span
 
 
 def shard_range(n_global: int, world: int, rank: int):
@@ -48,8 +48,29 @@ def global_views(records: torch.Tensor):
     return obs, reward, term.view(torch.bool), trunc.view(torch.bool)
 
 
+def _records_behind(obs, reward, term, trunc, status) -> torch.Tensor:
+    """The record array uint8 [ko, n, 56] of a SpinTorqueVecEnv.step_many in the records layout, from the obs [ko, n, 12] it returned:
+    with the HIP backend that obs IS a strided view of the array the launch wrote (backend.record_views), and this is the view back,
+    no copy.  A backend that hands out separate arrays instead (the CPU oracle behind the tests' backend seam) gets them packed."""
+    ko, n, _ = obs.shape
+    words = RECORD_BYTES // 4
+    if (obs.dtype == torch.float32 and tuple(obs.stride()) == (words * n, words, 1) and obs.storage_offset() == 0
+            and obs.untyped_storage().nbytes() >= ko * n * RECORD_BYTES):
+        return obs.as_strided((ko, n, words), (words * n, words, 1)).view(torch.uint8)
+    if obs.is_cuda:
+        raise RuntimeError("step_many did not return views of a record array (out_layout='records' is what the sharded env builds)")
+    rec = torch.zeros((ko, n, RECORD_BYTES), dtype=torch.uint8)
+    o, r, te, tr, st = record_views(rec)
+    o.copy_(obs), r.copy_(reward), te.copy_(term), tr.copy_(trunc)
+    if status is not None:
+        st.copy_(status)
+    return rec
+
+
 class ShardedSpinTorqueVecEnv:
-    """`num_envs` global environments sharded over the ranks of `group` (default: the world group)."""
+    """`num_envs` global environments sharded over the ranks of `group` (default: the world group).  step() / step_many() advance
+    every env by one / K steps per launch and gather the records; state_dict() / load_state_dict() checkpoint the shards and
+    resume them under any other world size (or in a one-process SpinTorqueVecEnv)."""
 
     def __init__(self, num_envs: int, group: Optional[dist.ProcessGroup] = None, device_index: Optional[int] = None,
                  class_index=None, gather_algo: str = "all_gather", inplace: bool = False, overlap: Optional[bool] = None,
@@ -262,6 +283,198 @@ class ShardedSpinTorqueVecEnv:
         for w in (dist.batch_isend_irecv(ops) if ops else []):
             w.wait()
         return local
+
+    # -- K fused steps per launch ----------------------------------------------------------------------------------------
+    def step_many(self, actions, out_every: bool = True, autoreset: Optional[bool] = None, gather: bool = True,
+                  actions_are_local: bool = False, final_obs_out: Optional[torch.Tensor] = None):
+        """K env.step()s of this rank's shard in ONE launch (SpinTorqueVecEnv.step_many in the records layout), then the exchange.
+        actions: [K, N_global, 2], or [K, n_local, 2] with actions_are_local; float32 or float64 as for step().  `autoreset` must be
+        the env's own convention (it is fixed at construction and part of every checkpoint); None = that.
+        Returns (obs [ko, N_global, 12], reward [ko, N_global], terminated, truncated, info) with ko = K (out_every) or 1 (the last
+        step only): typed strided views of ONE new record array uint8 [ko, N_global, 56], which is info['records'];
+        info['status'] is its status byte and, with autoreset, info['final_obs'] float32 [ko, N_global, 12] holds the terminal
+        observation of the envs whose episode ended (zero elsewhere, as in the one-process env).  The arrays are this call's own:
+        they stay valid for as long as the caller holds them (the two-array ring of step() is not involved).
+        final_obs_out (out_every only): a float32 [K, N_global, 12] array of the caller's that receives the terminal observations
+        instead -- rows of envs that did not end at that step are left as they are; it is then info['final_obs'].
+        gather=False: no exchange; the same tuple for this rank's envs only (views of the launch's own [ko, n_local, 56] output).
+
+        Form of the exchange.  The launch writes [ko][n_local][56]: step k of this rank is one contiguous block, and so is
+        out[k, lo_r:hi_r] of every rank r in the global array, but the K blocks of a rank are N_global records apart there, so
+        the kernel cannot write them in place and one all-gather cannot cover all K.  Equal shards with gather_algo 'all_gather':
+        ONE all_gather_into_tensor PER STEP SLICE, from the launch's block k straight into out[k] (ko collectives, enqueued back to
+        back; RCCL's most travelled call).  gather_algo 'p2p', which ragged shards always use: ONE grouped batch for all K --
+        ko x (world - 1) sends of block k and receives straight into out[k, lo_r:hi_r] -- plus a device copy of this rank's own
+        ko blocks into its slices.  Nothing is transposed or concatenated.  final_obs travels the same way, 48 B/env.  Over gloo
+        (host memory) a rank's ko blocks go through one staging tensor per peer, as the one-step exchange stages there.  The
+        exchange runs on the side stream when the env overlaps; the current stream waits for it before this call returns."""
+        if autoreset is not None and bool(autoreset) != self.local.autoreset:
+            raise ValueError(f"autoreset={bool(autoreset)} but this env was built with autoreset={self.local.autoreset}")
+        a = torch.as_tensor(actions)
+        if a.dim() != 3 or a.shape[2] != 2 or a.shape[1] != (self.n_local if actions_are_local else self.num_envs):
+            raise ValueError(f"expected actions [K, {self.n_local if actions_are_local else self.num_envs}, 2], got {tuple(a.shape)}")
+        if not actions_are_local:
+            a = a[:, self.lo:self.hi]
+        K = int(a.shape[0])
+        ko = K if out_every else 1
+        auto = self.local.autoreset
+        if final_obs_out is not None:
+            if not (auto and out_every and gather):
+                raise ValueError("final_obs_out needs autoreset, out_every=True (the flags that say which rows to write are per step) "
+                                 "and gather=True")
+            if (final_obs_out.dtype != torch.float32 or tuple(final_obs_out.shape) != (K, self.num_envs, 12)
+                    or final_obs_out.device != self.device):
+                raise ValueError(f"final_obs_out must be float32 [{K}, {self.num_envs}, 12] on {self.device}")
+        obs, reward, term, trunc, info = self.local.step_many(a, out_every=out_every)
+        if not gather:
+            return obs, reward, term, trunc, info
+        rec = _records_behind(obs, reward, term, trunc, info.get("status"))
+        out = torch.empty((ko, self.num_envs, RECORD_BYTES), dtype=torch.uint8, device=self.device)
+        pairs = [(rec, out)]
+        if auto:
+            fin = info["final_obs"]
+            fin = fin if fin.is_contiguous() else fin.contiguous()       # (env-major [ko, n_local, 12] already in the records layout)
+            fout = torch.empty((ko, self.num_envs, 12), dtype=torch.float32, device=self.device)
+            pairs.append((fin.view(torch.uint8), fout.view(torch.uint8)))
+        t0 = time.perf_counter()
+        if not self._overlap:
+            self._exchange_many(pairs)
+        else:
+            cur = torch.cuda.current_stream(self.device)
+            ready = torch.cuda.Event()
+            ready.record(cur)                                            # the launch that wrote the blocks
+            with torch.cuda.stream(self._comm_stream):
+                self._comm_stream.wait_event(ready)
+                self._exchange_many(pairs)
+                done = torch.cuda.Event()
+                done.record(self._comm_stream)
+            # (the arrays were allocated on the current stream; it waits here, so whatever frees or reuses them comes after)
+            cur.wait_event(done)
+        self.profiler.add("gather_many", time.perf_counter() - t0)
+        g_obs, g_reward, g_term, g_trunc, g_status = record_views(out)
+        g_term, g_trunc = g_term.view(torch.bool), g_trunc.view(torch.bool)
+        g_info = {"records": out, "status": g_status}
+        if auto:
+            if final_obs_out is not None:
+                ended = (g_term | g_trunc).unsqueeze(-1)
+                final_obs_out.copy_(torch.where(ended, fout, final_obs_out))
+                fout = final_obs_out
+            g_info["final_obs"] = fout
+        return g_obs, g_reward, g_term, g_trunc, g_info
+
+    def _exchange_many(self, pairs) -> None:
+        """For every (mine uint8 [ko, n_local, B], glob uint8 [ko, N_global, B]): glob[k, lo_r:hi_r] = rank r's mine[k]."""
+        p2p = self.gather_algo == "p2p" and self.world > 1
+        if self._gloo:
+            for mine, g in pairs:
+                ko, _, nb = mine.shape
+                src = mine.cpu()
+                host = torch.empty(g.shape, dtype=torch.uint8)
+                if p2p:
+                    # one message per peer and array (gloo matches a pair's messages in order): the peer's ko blocks, then placed
+                    stage = {peer: torch.empty((ko, phi - plo, nb), dtype=torch.uint8)
+                             for peer, (plo, phi) in enumerate(self._spans) if peer != self.rank}
+                    ops = []
+                    for peer, buf in stage.items():
+                        ops.append(dist.P2POp(dist.isend, src, self._global[peer], group=self.group))
+                        ops.append(dist.P2POp(dist.irecv, buf, self._global[peer], group=self.group))
+                    for w in dist.batch_isend_irecv(ops):
+                        w.wait()
+                    for peer, buf in stage.items():
+                        plo, phi = self._spans[peer]
+                        host[:, plo:phi] = buf
+                    host[:, self.lo:self.hi] = src
+                else:
+                    for k in range(ko):
+                        dist.all_gather_into_tensor(host[k].view(-1), src[k].reshape(-1), group=self.group)
+                g.copy_(host)
+            return
+        if p2p:
+            ops = []
+            for mine, g in pairs:
+                for k in range(mine.shape[0]):
+                    for peer, (plo, phi) in enumerate(self._spans):
+                        if peer != self.rank:
+                            ops.append(dist.P2POp(dist.isend, mine[k], self._global[peer], group=self.group))
+                            ops.append(dist.P2POp(dist.irecv, g[k, plo:phi], self._global[peer], group=self.group))
+                g[:, self.lo:self.hi].copy_(mine)
+            for w in dist.batch_isend_irecv(ops):
+                w.wait()            # (stream-ordered on NCCL/RCCL: does not block the host)
+            return
+        for mine, g in pairs:
+            for k in range(mine.shape[0]):
+                dist.all_gather_into_tensor(g[k].view(-1), mine[k].reshape(-1), group=self.group)
+
+    # -- checkpoint / resume -------------------------------------------------------------------------------------------------
+    def _end_gather(self) -> None:
+        """Ends whatever the exchange has in flight and returns the slot ring to its initial state (cf. _AsyncPool.drain)."""
+        if self._pending is not None:
+            self.gather_end()
+        if self._overlap:
+            self._comm_stream.synchronize()
+        self._done = [None, None]
+        self._slot, self._filled, self._last = 0, None, None
+
+    def state_dict(self, gather_to: Optional[int] = None):
+        """This rank's checkpoint: SpinTorqueVecEnv.state_dict()'s keys for its own envs -- m / target [3, n_local], total_energy,
+        step_count, rng_step, done [n_local] (left on the device), host_rng, cfg_seed, env_id0 (= lo) -- plus the global metadata
+        n_global, world, rank, lo, hi and config (SpinTorqueVecEnv.result_config(): solver, thermal field, noise model, max_steps,
+        targets, autoreset, ... -- everything that decides results).  Every rank calls it; without gather_to there is no
+        communication at all (the metadata is checked against this rank's own shard only).
+        gather_to=r: rank r's dict holds the full [N_global] state instead (lo, hi = 0, N_global; env_id0 = 0; one gather per
+        tensor), the dict a SpinTorqueVecEnv(num_envs=N_global) saves, for writing a single file; the other ranks still get
+        their per-rank dict.  load_state_dict takes either, at any world size."""
+        loc = self.local
+        if loc.num_envs != self.hi - self.lo or loc.env_id0 != self.lo:
+            raise RuntimeError(f"shard [{self.lo}, {self.hi}) but the local env holds {loc.num_envs} envs from {loc.env_id0}")
+        loc._no_pool("state_dict")
+        st = dict(loc.backend.get_state())
+        st.update(host_rng=loc._rng.bit_generator.state, cfg_seed=int(loc.cfg.seed), env_id0=int(self.lo),
+                  n_global=self.num_envs, world=self.world, rank=self.rank, lo=self.lo, hi=self.hi, config=loc.result_config())
+        if gather_to is None:
+            return st
+        if not 0 <= int(gather_to) < self.world:
+            raise ValueError(f"gather_to must be a rank of the group, 0..{self.world - 1}")
+        full = {key: self._gather_to(st[key], int(gather_to)) for key in STATE_TENSORS}
+        if self.rank != int(gather_to):
+            return st
+        st = dict(st, **full)
+        st.update(env_id0=0, lo=0, hi=self.num_envs)
+        return st
+
+    def _gather_to(self, t: torch.Tensor, dst: int):
+        """One gather of a per-env tensor [..., n_local] to group rank dst: [..., N_global] there, None elsewhere.  Ragged shards
+        are padded to the largest one for the collective (gather needs equal contributions)."""
+        dev = torch.device("cpu") if self._gloo else self.device
+        width = self._spans[0][1] - self._spans[0][0]
+        mine = torch.zeros((*t.shape[:-1], width), dtype=t.dtype, device=dev)
+        mine[..., :self.n_local] = t
+        bufs = [torch.empty_like(mine) for _ in range(self.world)] if self.rank == dst else None
+        dist.gather(mine, bufs, dst=self._global[dst], group=self.group)
+        if bufs is None:
+            return None
+        return torch.cat([b[..., :phi - plo] for b, (plo, phi) in zip(bufs, self._spans)], dim=-1).to(self.device)
+
+    def load_state_dict(self, st) -> None:
+        """Resumes bit for bit from (a) a per-rank dict of the same world size and rank, (b) a full [N_global] dict -- state_dict(
+        gather_to=...)'s or a SpinTorqueVecEnv(num_envs=N_global).state_dict() -- of which this rank slices its [lo, hi), or (c) a
+        LIST of the per-rank dicts of ANY world size, of which it takes the overlaps with its [lo, hi).  An env's streams are keyed
+        by (cfg_seed, global env id, rng_step), all of which travel, so the partition does not matter.  ValueError, naming the
+        field: n_global or a result-deciding config field differs, or the lo, hi ranges of a list do not tile [0, n_global).
+        Ends a gather in flight first.  No communication."""
+        self._end_gather()
+        is_list = isinstance(st, (list, tuple))
+        pieces = list(st) if is_list else [st]
+        for p in pieces:
+            n_g = p.get("n_global")
+            if n_g is None and not is_list and state_span(p)[0] == 0:
+                n_g = state_span(p)[1]            # a one-process env's dict: all of its envs, from env 0
+            if n_g is not None and int(n_g) != self.num_envs:
+                raise ValueError(f"checkpoint has n_global={n_g}, this env has n_global={self.num_envs}")
+        mine = assemble_state(pieces, self.lo, self.hi, tile=is_list)
+        check_state_config(mine, self.local.result_config())
+        mine.pop("config", None)
+        self.local.load_state_dict(mine)
 
     def get_performance_stats(self):
         st = self.local.get_performance_stats()

@@ -110,6 +110,81 @@ def _default_env_side_params(device_type: str) -> Dict[str, Any]:
             "polarization": 0.7}
 
 
+# -- checkpoints across partitions of the envs (shared by SpinTorqueVecEnv and distributed.ShardedSpinTorqueVecEnv) ----------------
+# EnvConfig fields that decide results (SpinTorqueVecEnv.result_config adds target_states, autoreset and the device classes)
+_RESULT_FIELDS = ("solver", "include_thermal_fluctuations", "temperature", "gamma", "max_step", "rtol", "atol", "max_steps",
+                  "max_current", "max_duration", "success_threshold", "energy_penalty_weight", "max_attempts", "skip_done",
+                  "torque_model", "noise_model", "correlation_time")
+# per-env tensors of a state dict; the env index is the LAST dimension of each (m and target are [3, n])
+STATE_TENSORS = ("m", "target", "total_energy", "step_count", "rng_step", "done")
+
+
+def state_span(st) -> tuple:
+    """[lo, hi) of global env ids that a state dict holds: what a sharded checkpoint says, else env_id0 and the tensors' length."""
+    if "lo" in st and "hi" in st:
+        return int(st["lo"]), int(st["hi"])
+    lo = int(st.get("env_id0", 0))
+    return lo, lo + int(st["m"].shape[-1])
+
+
+def check_state_config(st, config) -> None:
+    """ValueError naming the first result-deciding field on which the checkpoint's recorded configuration differs from `config`
+    (a dict without one -- a plain SpinTorqueVecEnv.state_dict() -- records nothing to compare)."""
+    theirs = st.get("config")
+    if theirs is None:
+        return
+    for k, v in config.items():
+        if k in theirs and theirs[k] != v:
+            raise ValueError(f"checkpoint was taken with {k}={theirs[k]!r}, this env has {k}={v!r}")
+
+
+def assemble_state(pieces, lo: int, hi: int, tile: bool = True):
+    """The state dict of envs [lo, hi) out of `pieces`, state dicts of contiguous spans of global env ids (state_span) saved under any
+    partition.  The pieces must agree on n_global, cfg_seed and config; with `tile` they must tile [0, n_global) exactly, otherwise
+    they must at least cover [lo, hi).  ValueError names what does not hold.  Slices and at most one torch.cat per tensor."""
+    pieces = sorted(pieces, key=state_span)
+    if not pieces:
+        raise ValueError("an empty list of state dicts")
+    first = pieces[0]
+    for key in ("n_global", "cfg_seed", "config"):
+        for p in pieces[1:]:
+            if (key in p) != (key in first):
+                raise ValueError(f"some state dicts of the list record {key}, others do not")
+            if key == "config":
+                check_state_config(p, first.get("config") or {})
+            elif key in p and p[key] != first[key]:
+                raise ValueError(f"the state dicts disagree on {key}: {first[key]!r} and {p[key]!r}")
+    n_global = first.get("n_global")
+    cursor = 0 if tile else state_span(first)[0]
+    for p in pieces:
+        plo, phi = state_span(p)
+        if phi - plo != int(p["m"].shape[-1]) or phi < plo:
+            raise ValueError(f"a state dict claims lo, hi = [{plo}, {phi}) but holds {int(p['m'].shape[-1])} envs")
+        if plo > cursor:
+            raise ValueError(f"the lo, hi ranges of the state dicts leave a hole: envs [{cursor}, {plo}) are in none of them")
+        if plo < cursor:
+            raise ValueError(f"the lo, hi ranges of the state dicts overlap: envs [{plo}, {min(cursor, phi)}) are in two of them")
+        cursor = phi
+    if tile and n_global is not None and cursor != int(n_global):
+        if cursor < int(n_global):
+            raise ValueError(f"the lo, hi ranges of the state dicts leave a hole: envs [{cursor}, {int(n_global)}) are in none of them")
+        raise ValueError(f"the lo, hi ranges of the state dicts end at {cursor}, past n_global={int(n_global)}")
+    if lo < state_span(first)[0] or hi > cursor:
+        raise ValueError(f"envs [{lo}, {hi}) asked for, the state dicts hold lo, hi = [{state_span(first)[0]}, {cursor})")
+    parts = []                                                   # (piece, first and one-past-last column of it to take)
+    for p in pieces:
+        plo, phi = state_span(p)
+        a, b = max(lo, plo), min(hi, phi)
+        if a < b:
+            parts.append((p, a - plo, b - plo))
+    out = {k: v for k, v in first.items() if k in ("host_rng", "cfg_seed", "config")}
+    for key in STATE_TENSORS:
+        cols = [torch.as_tensor(p[key])[..., a:b] for p, a, b in parts]
+        out[key] = cols[0] if len(cols) == 1 else torch.cat([c.to(cols[0].device) for c in cols], dim=-1)
+    out["env_id0"] = int(lo)
+    return out
+
+
 class SpinTorqueVecEnv:
     """N parallel SpinTorque-v0 environments on one MI355X.
 
@@ -291,7 +366,19 @@ class SpinTorqueVecEnv:
         return t.t().contiguous()
 
     # -- checkpoint / resume ---------------------------------------------------------------------------
-    _HOST_KEYS = ("host_rng", "cfg_seed", "env_id0")
+    # (the second row: the global metadata a ShardedSpinTorqueVecEnv checkpoint adds to the same dict, distributed.py)
+    _HOST_KEYS = ("host_rng", "cfg_seed", "env_id0",
+                  "n_global", "world", "rank", "lo", "hi", "config")
+
+    def result_config(self) -> Dict[str, Any]:
+        """The constructor arguments that decide an env's results, as plain data: what a checkpoint taken under one partition of the
+        envs must agree on with the env that loads it (check_state_config).  Not in it: what is bit-identical by construction
+        (lane_sort, wave_spec, lane_refill, out_layout, diagnostics) and the per-env tables (class_index, per_env_params)."""
+        d = {k: getattr(self.cfg, k) for k in _RESULT_FIELDS}
+        d["target_states"] = [[float(x) for x in t] for t in self.cfg.target_states]
+        d["autoreset"] = self.autoreset
+        d["device_params"] = [bytes(flatten_params(dev)).hex() for dev in self.devices]
+        return d
 
     def state_dict(self):
         """Device state + everything the random streams hang on: the host PCG64 state (reset seeds), `cfg.seed` (the
@@ -305,8 +392,14 @@ class SpinTorqueVecEnv:
 
     def load_state_dict(self, st):
         """Resumes bit-for-bit: an env built with another stream key (e.g. seed=None in a new process) or env_id0 gets
-        its context rebuilt with the checkpoint's before the state is restored."""
+        its context rebuilt with the checkpoint's before the state is restored.
+        Also takes a LIST of ShardedSpinTorqueVecEnv per-rank dicts (any world size): this env then takes the envs
+        [env_id0, env_id0 + num_envs) out of them.  A dict that names its configuration (`config`, the sharded env's) must agree with
+        this env's on every field that decides results, else ValueError."""
         self._end_async()
+        if isinstance(st, (list, tuple)):
+            st = assemble_state(st, self.env_id0, self.env_id0 + self.num_envs)
+        check_state_config(st, self.result_config())
         seed, id0 = int(st.get("cfg_seed", self.cfg.seed)), int(st.get("env_id0", self.env_id0))
         if seed != int(self.cfg.seed) or id0 != self.env_id0:
             self.backend.close()
