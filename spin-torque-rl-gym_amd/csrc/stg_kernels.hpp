@@ -633,7 +633,7 @@ __device__ __forceinline__ void refill_wave(const StepArgs& a, int64_t w, int64_
     LlgsLane L;
     L.active = false; L.idle = true; L.rejected = false; L.attempts = 0; L.npts = 0;
     L.y = L.f = L.m0 = V3{0.0, 0.0, 1.0};
-    L.t = L.T = L.h_abs = L.min_step = L.bJ = L.bpJ = 0.0;
+    L.t = L.T = L.h_abs = L.h_floor = L.bJ = L.bpJ = 0.0;
     V3 out_m{0.0, 0.0, 1.0};
 
     // takes queue entry p (if there is one): state, action, the solve's prologue
@@ -714,7 +714,7 @@ __device__ __forceinline__ void refill_wave(const StepArgs& a, int64_t w, int64_
             llgs_lane_gate<false>(L, M, (int32_t)a.c.max_attempts);
             if (M.active == 0ull) break;
             V3 z2{0.0, 0.0, 0.0}, z3{0.0, 0.0, 0.0};
-            llgs_lane_attempt<THERMAL, false, AXIS_Z, false>(L, M, 0, out_m, k, tb, a.c.rtol, a.c.atol, a.c.max_step, norec, noek, ns, z2, z3);
+            llgs_lane_attempt<THERMAL, false, AXIS_Z, false>(L, M, out_m, k, tb, a.c.rtol, a.c.atol, a.c.max_step, norec, noek, ns, z2, z3);
         }
         llgs_masks_close(L, M);
         // ... then a refill point: finished lanes write their env; every lane without an env -- finished just now, or one that drew an

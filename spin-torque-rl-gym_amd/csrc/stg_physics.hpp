@@ -139,6 +139,14 @@ __device__ __forceinline__ double rsqrt_fast(double s) {
     return __builtin_fma(y * e, __builtin_fma(0.375, e, 0.5), y);
 }
 
+// Two thermal fields fetched from LDS as ONE batch: all six values are operands of one (empty) statement together with `at`, a value the
+// caller forms just before the first of them is used.  The compiler then waits for the batch once, there (one s_waitcnt lgkmcnt(0)), instead
+// of once per value where each is first read: the loads were issued a whole RHS evaluation earlier, so a partial wait hides nothing and
+// costs a lone wavefront an issue slot each.  (Inputs only: an output would have to be copied out of the load's register tuple.)
+__device__ __forceinline__ void batch_ready(double at, double a0, double a1, double a2, double b0, double b1, double b2) {
+    asm volatile("" : : "v"(at), "v"(a0), "v"(a1), "v"(a2), "v"(b0), "v"(b1), "v"(b2));
+}
+
 // a wave-uniform constant held in a VGPR pair (opaque to the optimiser: it is not moved back into SGPRs)
 __device__ __forceinline__ double vgpr_const(double c) {
     asm volatile("" : "+v"(c));
@@ -156,16 +164,12 @@ __device__ __forceinline__ double fmax_abs(double a, double b) {
 }
 
 // The commit of an accepted RK45 attempt, in the lanes of `mask` (a ballot) and nowhere else, under EXEC = mask:
-//  * dst_i = src_i, seven doubles (time, state, f(state)): seven v_mov_b64 instead of fourteen v_cndmask_b32;
-//  * min_step = 10 ulp(t_new), from the exponent (stg_minstep.hpp: min_step_pos -- t_new > 0 in an accepting lane, it is at least the
-//    step just taken; `unit` = MIN_STEP_UNIT): an unchanged t leaves min_step unchanged, so the other lanes keep theirs;
-//  * h = max(h, min_step): the next step()'s lower clamp (rk.py:121-126), which applies after an accepted attempt only.
-// (s0 is the new time.  The old EXEC waits in an SGPR pair of its own.)
+// dst_i = src_i, seven doubles (time, state, f(state)): seven v_mov_b64 instead of fourteen v_cndmask_b32.
+// (s0 is the new time.  The old EXEC waits in an SGPR pair of its own.  The next step()'s lower clamp of h is the caller's: see
+// llgs_lane_attempt, "minimum step".)
 __device__ __forceinline__ void commit_step(unsigned long long mask, double& d0, double s0, double& d1, double s1, double& d2, double s2,
-                                            double& d3, double s3, double& d4, double s4, double& d5, double s5, double& d6, double s6,
-                                            double& min_step, double& h, double unit) {
+                                            double& d3, double s3, double& d4, double s4, double& d5, double s5, double& d6, double s6) {
     unsigned long long saved;
-    int e;
     asm("s_and_saveexec_b64 %[sv], %[m]\n\t"
         "v_mov_b64 %[d0], %[s0]\n\t"
         "v_mov_b64 %[d1], %[s1]\n\t"
@@ -174,15 +178,9 @@ __device__ __forceinline__ void commit_step(unsigned long long mask, double& d0,
         "v_mov_b64 %[d4], %[s4]\n\t"
         "v_mov_b64 %[d5], %[s5]\n\t"
         "v_mov_b64 %[d6], %[s6]\n\t"
-        "v_frexp_exp_i32_f64 %[e], %[s0]\n\t"
-        "v_max_i32 %[e], %[fl], %[e]\n\t"
-        "v_ldexp_f64 %[ms], %[u], %[e]\n\t"
-        "v_max_f64 %[h], %[h], %[ms]\n\t"
         "s_mov_b64 exec, %[sv]"
-        : [d0] "+v"(d0), [d1] "+v"(d1), [d2] "+v"(d2), [d3] "+v"(d3), [d4] "+v"(d4), [d5] "+v"(d5), [d6] "+v"(d6), [ms] "+v"(min_step),
-          [h] "+v"(h), [e] "=&v"(e), [sv] "=&s"(saved)
-        : [s0] "v"(s0), [s1] "v"(s1), [s2] "v"(s2), [s3] "v"(s3), [s4] "v"(s4), [s5] "v"(s5), [s6] "v"(s6), [u] "v"(unit), [m] "s"(mask),
-          [fl] "n"(MIN_STEP_EXP_FLOOR)
+        : [d0] "+v"(d0), [d1] "+v"(d1), [d2] "+v"(d2), [d3] "+v"(d3), [d4] "+v"(d4), [d5] "+v"(d5), [d6] "+v"(d6), [sv] "=&s"(saved)
+        : [s0] "v"(s0), [s1] "v"(s1), [s2] "v"(s2), [s3] "v"(s3), [s4] "v"(s4), [s5] "v"(s5), [s6] "v"(s6), [m] "s"(mask)
         : "scc");
 }
 
@@ -194,11 +192,12 @@ __device__ __forceinline__ double rcp_fast(double x) {
 
 // e2^(-1/10) for e2 = err^2 in (3.5e-11, 3.4e6), i.e. err^(-1/5): fp32 transcendental seed + one third-order Newton step
 // on y^-10 = e2 (~1 ulp).  Stands in for the libm pow of SciPy's step-size controller (rk.py:158-168).
-__device__ __forceinline__ double inv_tenth_root(double e2) {
+// `tenth`: 0.1 (the caller may hold it in a register of its own).
+__device__ __forceinline__ double inv_tenth_root(double e2, double tenth = 0.1) {
     const double y = (double)__builtin_amdgcn_exp2f(-0.1f * __builtin_amdgcn_logf((float)e2));
     const double y2 = y * y, y4 = y2 * y2, y8 = y4 * y4;
     const double e = __builtin_fma(-e2, y8 * y2, 1.0);                // e = 1 - e2 y^10 = -(10 d + 45 d^2), y = y*(1+d)
-    return __builtin_fma(y * e, __builtin_fma(0.055, e, 0.1), y);     // y (1 + e/10 + 11 e^2/200)
+    return __builtin_fma(y * e, __builtin_fma(0.055, e, tenth), y);   // y (1 + e/10 + 11 e^2/200)
 }
 
 // x^(1/5) for finite x > 0 (any exponent): r = x^(-1/5) from an fp32 transcendental seed on the mantissa plus one
@@ -352,6 +351,7 @@ struct InlineNormals {
     __device__ __forceinline__ void peek() {}
     __device__ __forceinline__ bool chunk_end(bool lane_continues) { return lane_continues; }
     __device__ __forceinline__ bool chunk_end_wave(bool mine) { return mine; }
+    __device__ __forceinline__ int32_t chunk_end_go(int32_t go) { return go; }
 };
 
 // A chunk of the shared stream (one rendezvous of an integrating wavefront with its producer): an RK45 attempt (18 normals; the
@@ -400,19 +400,20 @@ struct SharedNormalsT {
     int lane, it, idx, seen;   // seen: the producer's count as last read (a lane-uniform value in a VGPR)
     bool broken;               // the poll budget ran out (never, unless the protocol is broken): the solve reports failure
     // The RK45 ring (a barrier per attempt, two slots): where the current slot starts and which flag copy is next are per-lane values that
-    // TOGGLE -- one v_xor_b32 each per attempt -- instead of being rebuilt from `it` (s_bitcmp1 / s_cselect / v_or and s_and / s_lshl / v_mov)
+    // TOGGLE -- one v_xor_b32 each per attempt -- instead of being rebuilt from `it` (s_bitcmp1 / s_cselect / v_or and s_and / s_lshl / v_mov).
+    // They are BYTE offsets, so that the address needs no shift after the toggle.
     static constexpr bool kToggle = BARRIER && SCALED;
-    int slot_el, flag_el;      // kToggle: element offset of this lane in the current slot (lane, or CHUNK * 64 + lane); 0 / 1
+    int slot_b, flag_b;        // kToggle: byte offset of this lane in the current slot (lane, or CHUNK * 64 + lane, times sizeof(T)); 0 / 4
     __device__ __forceinline__ void begin(const RngKey&) {
         it = 0; idx = 0; seen = 1; broken = false;                                                         // chunk 0 is there (H2)
         if (kToggle) {
             static_assert(((CHUNK * 64) & 63) == 0, "the slot bit and the lane bits are disjoint");
-            slot_el = lane; flag_el = 0;
-            asm volatile("" : "+v"(slot_el), "+v"(flag_el));      // (kept in VGPRs)
+            slot_b = lane * (int)sizeof(T); flag_b = 0;
+            asm volatile("" : "+v"(slot_b), "+v"(flag_b));        // (kept in VGPRs)
         }
     }
     __device__ __forceinline__ V3 draw(bool) {
-        const T* b = kToggle ? buf + slot_el + idx * 64 : buf + ((it & (DEPTH - 1)) * CHUNK + idx) * 64 + lane;
+        const T* b = kToggle ? (const T*)((const char*)buf + slot_b) + idx * 64 : buf + ((it & (DEPTH - 1)) * CHUNK + idx) * 64 + lane;
         idx += 3;
         return V3{(double)b[0], (double)b[64], (double)b[128]};
     }
@@ -425,14 +426,22 @@ struct SharedNormalsT {
     // that, once the next chunk is in LDS.  Straight-line when the producer is ahead (the normal case).
     __device__ __forceinline__ bool chunk_end(bool lane_continues) { return chunk_end_wave(__ballot(lane_continues) != 0ull); }
     // (the same for a caller that holds the wave-uniform answer already)
-    __device__ __forceinline__ bool chunk_end_wave(bool mine) {
+    __device__ __forceinline__ bool chunk_end_wave(bool mine) { return chunk_end_go(mine ? 1 : 0) != 0; }
+    // (... and for one that holds it as the flag's own value, 1 or 0, in a scalar register: the flag is then a move of it and the caller's
+    // branch a scalar compare, where a bool becomes a lane mask, a select and a mask test)
+    __device__ __forceinline__ int32_t chunk_end_go(int32_t go) {
+        const bool mine = go != 0;
         if (BARRIER) {
-            lds_flag(hs)[kToggle ? flag_el : (it & 1)] = mine ? 1 : 0;
-            if (kToggle) { flag_el ^= 1; slot_el ^= CHUNK * 64; }
+            if (kToggle) {
+                *(volatile lds_int*)((volatile __attribute__((address_space(3))) char*)lds_flag(hs) + flag_b) = go;
+                flag_b ^= (int)sizeof(int); slot_b ^= CHUNK * 64 * (int)sizeof(T);
+            } else {
+                lds_flag(hs)[it & 1] = go;
+            }
             __syncthreads();
             ++it;
             idx = 0;
-            return mine;
+            return go;
         }
         ++it;
         idx = 0;
@@ -449,7 +458,7 @@ struct SharedNormalsT {
         }
         seen = have;
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");      // the ring reads below stay below
-        return mine && !broken;
+        return (mine && !broken) ? 1 : 0;
     }
 };
 
@@ -892,7 +901,9 @@ __device__ __forceinline__ double rms3(const V3& a) { return sqrt(dot(a, a)) / 1
 // (stage nodes C = 1/5, 3/10, 4/5, 8/9, 1, 1: the RHS is autonomous but for the pulse gate, see llgs_lane_attempt)
 struct Dp5Tab {
     double A51, A52, A53, A54, A61, A62, A63, A64, A65, E1, E3, E4, E5, E6, E7;
-    double ms_unit;          // MIN_STEP_UNIT (commit_step)
+    // constants that shared an SGPR half with a neighbour and had the other half rebuilt in every attempt (s_mov_b32), and the 0.1 of
+    // inv_tenth_root, which as a loop-invariant literal was copied into the accumulator of a v_fmac_f64 in every attempt
+    double B4, third, c09, tenth;
 };
 __device__ __forceinline__ Dp5Tab make_dp5_tab() {
     Dp5Tab t;
@@ -901,7 +912,7 @@ __device__ __forceinline__ Dp5Tab make_dp5_tab() {
     t.A65 = vgpr_const(-5103.0 / 18656);
     t.E1 = vgpr_const(-71.0 / 57600); t.E3 = vgpr_const(71.0 / 16695); t.E4 = vgpr_const(-71.0 / 1920); t.E5 = vgpr_const(17253.0 / 339200);
     t.E6 = vgpr_const(-22.0 / 525); t.E7 = vgpr_const(1.0 / 40);
-    t.ms_unit = vgpr_const(MIN_STEP_UNIT);
+    t.B4 = vgpr_const(125.0 / 192); t.third = vgpr_const(1.0 / 3.0); t.c09 = vgpr_const(0.9); t.tenth = vgpr_const(0.1);
     return t;
 }
 
@@ -909,7 +920,8 @@ __device__ __forceinline__ Dp5Tab make_dp5_tab() {
 struct LlgsLane {
     V3 y, f;                 // state and f(y) (FSAL)
     V3 m0;                   // the input row (returned when the solve fails)
-    double t, T, h_abs, min_step;
+    double t, T, h_abs;
+    double h_floor;          // min_step at T: min_step(t) = 10 ulp(t) grows with t, so no min_step of this solve is above it
     double bJ, bpJ;          // beta J, beta' J (0 when |J| < 1e-12)
     int32_t attempts;        // (the host rejects a budget beyond 32 bits: stg_create)
     int32_t npts;
@@ -920,13 +932,16 @@ struct LlgsLane {
 // The flags an attempt loop updates, as 64-bit lane masks (wave-uniform values: SGPR pairs, combined by scalar instructions; the
 // per-lane booleans of LlgsLane cost a 0/1 VGPR each, with a v_cndmask / v_cmp round trip per update, once they are carried around a loop).
 //  active: the lane integrates.  pacc: the lane's previous attempt was accepted (rk.py's `step_rejected`, inverted); only a lane that
-//  is active reads it, so for the others it holds anything.
+//  is active reads it, so for the others it holds anything.  low: the lane's step size is below h_floor (llgs_lane_gate); a function of
+//  the lane's state, so it needs no flag in LlgsLane.
 typedef unsigned long long lanemask;
 struct LlgsMasks {
-    lanemask active, pacc;
+    lanemask active, pacc, low;
 };
 __device__ __forceinline__ bool lane_in(lanemask m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
-__device__ __forceinline__ LlgsMasks llgs_masks_open(const LlgsLane& L) { return LlgsMasks{__ballot(L.active), __ballot(!L.rejected)}; }
+__device__ __forceinline__ LlgsMasks llgs_masks_open(const LlgsLane& L) {
+    return LlgsMasks{__ballot(L.active), __ballot(!L.rejected), __ballot(L.h_abs < L.h_floor)};
+}
 __device__ __forceinline__ void llgs_masks_close(LlgsLane& L, const LlgsMasks& M) {
     L.active = lane_in(M.active);
     L.rejected = !lane_in(M.pacc);
@@ -998,22 +1013,52 @@ __device__ __forceinline__ void llgs_lane_begin(LlgsLane& L, V3& out_m, const V3
     }
     L.rejected = false;
     L.attempts = 0;
-    L.min_step = min_step_at(L.t);
-    L.h_abs = h_abs > max_step ? max_step : (h_abs < L.min_step ? L.min_step : h_abs);          // rk.py:121-126
+    const double min_step = min_step_at(L.t);
+    L.h_abs = h_abs > max_step ? max_step : (h_abs < min_step ? min_step : h_abs);          // rk.py:121-126
+    // (|t| <= |T| throughout; a T that is no finite number -- the solve API passes what it is given -- bounds nothing: +inf sends every
+    // attempt down the exact path of llgs_lane_attempt)
+    L.h_floor = isfinite(T) ? min_step_at(T) : __builtin_inf();
     L.active = enabled && (L.t != T);       // (a disabled lane only walks the workgroup's chunk loop)
     // A lane that starts stops for one of three reasons: it arrived (t == T), its step fell below min_step, or the attempt budget ran
     // out.  So "ok" needs no flag of its own inside the loop: it is `idle || t == T` afterwards (llgs_lane_finish).
     L.idle = !L.active;
 }
 
-// The minimum-step test that opens an attempt (rk.py:132-133); a lane that fails it stops.  UNIFORM_IT: every lane of the wavefront
-// started at iteration 0 of the loop (one env per lane), so the attempt budget is a test of the loop's scalar counter, made by the
-// loop itself; otherwise (lane refill) a lane has a counter of its own and the budget is tested here.
+// What opens an attempt: the minimum step and the attempt budget.
+// Minimum step.  SciPy clamps the step size from below to min_step = 10 ulp(t) after an accepted attempt (the next step()'s prologue,
+// rk.py:121-126) and stops a lane whose attempt would start below it (rk.py:132-133).  min_step grows with t, so h_floor -- its value at
+// T -- bounds it: while h_abs >= h_floor neither can happen, and min_step is not even formed.  The attempt that produced h_abs made that
+// ONE compare (M.low: llgs_lane_attempt; the mask is tested here, an attempt's preamble later, because compare -> mask -> branch back to
+// back stalls a lone wavefront); if it holds for a lane that goes on, the whole wavefront takes the branch below -- never, on a healthy
+// batch: steps of 1e-13 s against min_step(1 ns) = 2e-24 s -- and does SciPy's arithmetic: the clamp, in the select form that keeps the
+// NaN step size a prologue can produce, then the test.  A lane's result does not depend on whether its wavefront took the branch.
+// Budget.  UNIFORM_IT: every lane of the wavefront started at iteration 0 of the loop (one env per lane), so it is a test of the loop's
+// scalar counter, made by the loop itself; otherwise (lane refill) a lane has a counter of its own and the budget is tested here.
 template <bool UNIFORM_IT>
-__device__ __forceinline__ void llgs_lane_gate(const LlgsLane& L, LlgsMasks& M, int32_t max_attempts) {
-    lanemask stop = __ballot(L.h_abs < L.min_step);
-    if (!UNIFORM_IT) stop |= __ballot(L.attempts >= max_attempts);
-    M.active &= ~stop;
+__device__ __forceinline__ void llgs_lane_gate(LlgsLane& L, LlgsMasks& M, int32_t max_attempts) {
+    if (__builtin_expect((M.low & M.active) != 0ull, 0)) {
+        const double min_step = min_step_at(L.t);
+        if (lane_in(M.pacc)) L.h_abs = L.h_abs < min_step ? min_step : L.h_abs;
+        M.active &= ~__ballot(L.h_abs < min_step);
+    }
+    if (!UNIFORM_IT) M.active &= ~__ballot(L.attempts >= max_attempts);
+}
+
+// The bottom of a one-env-per-lane attempt loop, in five scalar instructions: counts the attempt, takes the lanes that have arrived out of
+// `active` (arrived: the ballot of t == T, inverted) and returns 1 if there is one more attempt -- somebody is active and the budget
+// allows it: ONE compare against a bound that is 0 once nobody is active -- else 0.  (Written out: from the C++ form the compiler builds
+// two lane-mask booleans and combines them, eleven instructions with the flag and the branch condition.)
+__device__ __forceinline__ int32_t attempt_loop_next(lanemask& active, lanemask not_arrived, int32_t& it, int32_t budget) {
+    int32_t go;
+    asm("s_add_i32 %[it], %[it], 1\n\t"
+        "s_and_b64 %[act], %[act], %[na]\n\t"
+        "s_cselect_b32 %[go], %[bud], 0\n\t"
+        "s_cmp_lt_i32 %[it], %[go]\n\t"
+        "s_cselect_b32 %[go], 1, 0"
+        : [act] "+s"(active), [it] "+s"(it), [go] "=&s"(go)
+        : [na] "s"(not_arrived), [bud] "s"(budget)
+        : "scc");
+    return go;
 }
 
 // ONE attempted step (rk.py:111-181) of a lane; the body has no lane-divergent control flow: a lane that is through (or
@@ -1022,14 +1067,15 @@ __device__ __forceinline__ void llgs_lane_gate(const LlgsLane& L, LlgsMasks& M, 
 // bookkeeping itself: same sequence of attempts per lane, but a wavefront needs max-over-lanes(total attempts) iterations
 // instead of sum-over-steps(max-over-lanes(attempts of that step)).
 // z2, z3: the thermal fields of the first two RHS calls of the attempt (fetched by the caller, see llgs_draw).
-// M: the loop's flags; `it`: attempts the wavefront's loop has behind it (UNIFORM_IT: a still-active lane has made exactly these).
+// M: the loop's flags.  UNIFORM_IT: the caller's loop is one env per lane and takes arrived lanes out of M.active itself.
 template <bool THERMAL, bool RECORD, bool AXIS_Z, bool UNIFORM_IT, class NSRC>
-__device__ __forceinline__ void llgs_lane_attempt(LlgsLane& L, LlgsMasks& M, int32_t it, V3& out_m, const LlgsK& k, const Dp5Tab& tb, double rtol,
+__device__ __forceinline__ void llgs_lane_attempt(LlgsLane& L, LlgsMasks& M, V3& out_m, const LlgsK& k, const Dp5Tab& tb, double rtol,
                                                   double atol, double max_step, const Recorder& rec, const LlgsEnergyK& ek, NSRC& ns, V3 z2, V3 z3) {
     constexpr double A21 = 1.0 / 5;
     constexpr double A31 = 3.0 / 40, A32 = 9.0 / 40;
     constexpr double A41 = 44.0 / 45, A42 = -56.0 / 15, A43 = 32.0 / 9;
-    constexpr double B1 = 35.0 / 384, B3 = 500.0 / 1113, B4 = 125.0 / 192, B5 = -2187.0 / 6784, B6 = 11.0 / 84;
+    constexpr double B1 = 35.0 / 384, B3 = 500.0 / 1113, B5 = -2187.0 / 6784, B6 = 11.0 / 84;
+    const double B4 = tb.B4;
     const double A51 = tb.A51, A52 = tb.A52, A53 = tb.A53, A54 = tb.A54, A61 = tb.A61, A62 = tb.A62, A63 = tb.A63, A64 = tb.A64, A65 = tb.A65;
     const double E1 = tb.E1, E3 = tb.E3, E4 = tb.E4, E5 = tb.E5, E6 = tb.E6, E7 = tb.E7;
     const double T = L.T;
@@ -1038,32 +1084,44 @@ __device__ __forceinline__ void llgs_lane_attempt(LlgsLane& L, LlgsMasks& M, int
     const double t = L.t;
     auto fun = [&](const V3& yy, const V3& ht, bool on) -> V3 { return llgs_fun<THERMAL, AXIS_Z, false>(L, k, yy, ht, on); };
     auto draw = [&](bool even) -> V3 { return llgs_draw<THERMAL>(ns, k, even); };
-    // (one masked 32-bit move; the counter of a lane that is through stays)
-    if (UNIFORM_IT) L.attempts = active ? it + 1 : L.attempts; else L.attempts += active ? 1 : 0;
+    // (the counter of a lane that is through stays)
+    L.attempts += active ? 1 : 0;
     const double t_new = fmin(add_x(t, L.h_abs), T);                       // rk.py:135-138: if t_new - T > 0: t_new = T
     const double h = sub_x(t_new, t);
     const double h_try = fabs(h);
     // rk_step (rk.py:14-70); the one stage time that can pass T is formed without contraction
     const bool on_end = add_x(t, h) <= T;
     const V3 k1 = L.f;
-    // normal-stream phases alternate per call (k2: even, k3: odd, ...); each field is fetched one call ahead
+    // normal-stream phases alternate per call (k2: even, k3: odd, ...).  Inline source: each field is drawn one call ahead.  Shared source: the
+    // six fields are fetched as three batches of two -- z2 + z3 by the caller, z4 + z5 under k3, z6 + z7 under k5 -- each with one wait in
+    // front of its first use (batch_ready)
+    constexpr bool BATCH = THERMAL && NSRC::kShared;
     if (THERMAL && !NSRC::kShared) { z2 = draw(true); z3 = draw(false); }
-    const V3 k2 = fun(V3{y.x + (k1.x * A21) * h, y.y + (k1.y * A21) * h, y.z + (k1.z * A21) * h}, z2, true);
-    const V3 z4 = draw(true);
+    V3 y2{y.x + (k1.x * A21) * h, y.y + (k1.y * A21) * h, y.z + (k1.z * A21) * h};
+    if (BATCH) batch_ready(y2.z, z2.x, z2.y, z2.z, z3.x, z3.y, z3.z);
+    const V3 k2 = fun(y2, z2, true);
+    V3 z4 = draw(true), z5{0.0, 0.0, 0.0};
+    // (nothing is scheduled across this point: left to itself the compiler sinks a batch's loads to just above its wait)
+    if (BATCH) { z5 = draw(false); __builtin_amdgcn_sched_barrier(0); }
     const V3 k3 = fun(V3{y.x + (k1.x * A31 + k2.x * A32) * h, y.y + (k1.y * A31 + k2.y * A32) * h,
                          y.z + (k1.z * A31 + k2.z * A32) * h}, z3, true);
-    const V3 z5 = draw(false);
-    const V3 k4 = fun(V3{y.x + (k1.x * A41 + k2.x * A42 + k3.x * A43) * h, y.y + (k1.y * A41 + k2.y * A42 + k3.y * A43) * h,
-                         y.z + (k1.z * A41 + k2.z * A42 + k3.z * A43) * h}, z4, true);
-    const V3 z6 = draw(true);
+    if (!BATCH) z5 = draw(false);
+    V3 y4{y.x + (k1.x * A41 + k2.x * A42 + k3.x * A43) * h, y.y + (k1.y * A41 + k2.y * A42 + k3.y * A43) * h,
+          y.z + (k1.z * A41 + k2.z * A42 + k3.z * A43) * h};
+    if (BATCH) batch_ready(y4.z, z4.x, z4.y, z4.z, z5.x, z5.y, z5.z);
+    const V3 k4 = fun(y4, z4, true);
+    V3 z6 = draw(true), z7{0.0, 0.0, 0.0};
+    if (BATCH) { z7 = draw(false); __builtin_amdgcn_sched_barrier(0); }
     const V3 k5 = fun(V3{y.x + (k1.x * A51 + k2.x * A52 + k3.x * A53 + k4.x * A54) * h,
                          y.y + (k1.y * A51 + k2.y * A52 + k3.y * A53 + k4.y * A54) * h,
                          y.z + (k1.z * A51 + k2.z * A52 + k3.z * A53 + k4.z * A54) * h}, z5, true);
     if (THERMAL) ns.peek();
-    const V3 z7 = draw(false);
-    const V3 k6 = fun(V3{y.x + (k1.x * A61 + k2.x * A62 + k3.x * A63 + k4.x * A64 + k5.x * A65) * h,
-                         y.y + (k1.y * A61 + k2.y * A62 + k3.y * A63 + k4.y * A64 + k5.y * A65) * h,
-                         y.z + (k1.z * A61 + k2.z * A62 + k3.z * A63 + k4.z * A64 + k5.z * A65) * h}, z6, on_end);
+    if (!BATCH) z7 = draw(false);
+    V3 y6{y.x + (k1.x * A61 + k2.x * A62 + k3.x * A63 + k4.x * A64 + k5.x * A65) * h,
+          y.y + (k1.y * A61 + k2.y * A62 + k3.y * A63 + k4.y * A64 + k5.y * A65) * h,
+          y.z + (k1.z * A61 + k2.z * A62 + k3.z * A63 + k4.z * A64 + k5.z * A65) * h};
+    if (BATCH) batch_ready(y6.z, z6.x, z6.y, z6.z, z7.x, z7.y, z7.z);
+    const V3 k6 = fun(y6, z6, on_end);
     const V3 y_new{y.x + h * (k1.x * B1 + k3.x * B3 + k4.x * B4 + k5.x * B5 + k6.x * B6),
                    y.y + h * (k1.y * B1 + k3.y * B3 + k4.y * B4 + k5.y * B5 + k6.y * B6),
                    y.z + h * (k1.z * B1 + k3.z * B3 + k4.z * B4 + k5.z * B5 + k6.z * B6)};
@@ -1075,14 +1133,14 @@ __device__ __forceinline__ void llgs_lane_attempt(LlgsLane& L, LlgsMasks& M, int
     // error_norm = rms(ev / scale) (rk.py:104-109); the controller only needs err < 1 and err^-0.2, so the kernel
     // carries err^2 (no sqrt) and divides by reciprocal-multiply (v_rcp_f64 + one Newton step, ~1 ulp)
     const V3 q{ev.x * rcp_fast(sc.x), ev.y * rcp_fast(sc.y), ev.z * rcp_fast(sc.z)};
-    const double err2 = dot(q, q) * (1.0 / 3.0);
+    const double err2 = dot(q, q) * tb.third;
     const double err = err2;      // compared against squared thresholds below
     // Controller (rk.py:158-181), branch-free: both outcomes share err^-0.2 and differ in a handful of selects.
     // 0.9 * err^-0.2 saturates at MAX_FACTOR = 10 for err <= 0.09^5 and at MIN_FACTOR = 0.2 for err >= 4.5^5 (err is
     // the SQUARED norm here); NaN error norms reject (nan < 1 is False) with fmax(0.2, NaN) = 0.2, as in SciPy.
     const lanemask accm = M.active & __ballot(err < 1.0);
     const bool acc = lane_in(accm);
-    const double r9 = 0.9 * inv_tenth_root(err);
+    const double r9 = tb.c09 * inv_tenth_root(err, tb.tenth);
     // (the clamps also cover the ends of the range: err -> 0 makes r9 huge, inf or -- at exactly 0 -- NaN, and
     // fmin/fmax return their other operand for a NaN; err -> inf makes it 0 or NaN)
     // after a rejected attempt the factor is capped at 1 instead of MAX_FACTOR: min(1, min(10, r9)) = min(1, r9) for every r9, NaN
@@ -1094,13 +1152,15 @@ __device__ __forceinline__ void llgs_lane_attempt(LlgsLane& L, LlgsMasks& M, int
     // shrunk h_try <= max_step, so the upper clamp is a no-op there and runs unconditionally.  It never returns a NaN (max_step is none) nor
     // anything below +0, so the lower clamp against 0 that a rejecting lane would get is the identity and is left out (commit_step).
     double h_next = fmin(h_try * (acc ? fa : fr), max_step);
-    // an accepted attempt advances, records, and does the next step()'s prologue
-    commit_step(accm, L.t, t_new, L.y.x, y_new.x, L.y.y, y_new.y, L.y.z, y_new.z, L.f.x, f_new.x, L.f.y, f_new.y, L.f.z, f_new.z,
-                L.min_step, h_next, tb.ms_unit);
+    // the lower clamp and the minimum-step test of the next attempt hang on this one compare (llgs_lane_gate)
+    M.low = __ballot(h_next < L.h_floor);
     L.h_abs = h_next;
+    // an accepted attempt advances and records
+    commit_step(accm, L.t, t_new, L.y.x, y_new.x, L.y.y, y_new.y, L.y.z, y_new.z, L.f.x, f_new.x, L.f.y, f_new.y, L.f.z, f_new.z);
     if (RECORD) { if (acc) llgs_lane_emit<RECORD>(L, out_m, rec, ek); } else L.npts += acc ? 1 : 0;
     M.pacc = accm;
-    M.active &= __ballot(L.t != T);
+    // (the one-env-per-lane loops take the lanes that have arrived out of M.active themselves: attempt_loop_next)
+    if (!UNIFORM_IT) M.active &= __ballot(L.t != T);
 }
 
 // end of a solve: the final row (the input row when the solve failed), accepted points, attempts
@@ -1133,10 +1193,11 @@ __device__ __forceinline__ SolveOut llgs_solve(const V3& m0, double J, double T,
     LlgsMasks M = llgs_masks_open(L);
     atol = vgpr_const(atol);        // (read next to rtol in one instruction, which takes a single scalar operand: no copy per attempt)
     // the attempt budget as the loop's own bound: whoever is still active when it runs out has failed (t != T: llgs_lane_finish)
-    const int32_t budget = (int32_t)max_attempts;
+    int32_t budget = (int32_t)max_attempts;
+    asm volatile("" : "+s"(budget));        // (held in a register: as a kernel argument it may be loaded again inside the loop)
     int32_t it = 0;
-    bool wave_go = true;
-    if (NSRC::kShared) wave_go = ns.chunk_end_wave(M.active != 0ull);
+    bool wave_go = M.active != 0ull;
+    if (NSRC::kShared) wave_go = ns.chunk_end_wave(wave_go);
     if (wave_go)
     for (;;) {
       // The loop is wave-uniform and its body has no lane-divergent control flow (see llgs_lane_attempt).  (The
@@ -1146,13 +1207,12 @@ __device__ __forceinline__ SolveOut llgs_solve(const V3& m0, double J, double T,
       // under the step-size bookkeeping)
       V3 z2 = zero, z3 = zero;
       if (THERMAL && NSRC::kShared) { z2 = llgs_draw<THERMAL>(ns, k, true); z3 = llgs_draw<THERMAL>(ns, k, false); }
+      // (should the gate stop the wavefront's last lanes, one attempt runs with nobody active before the test below ends the loop: its
+      // selects freeze every lane, counters included)
       llgs_lane_gate<true>(L, M, budget);
-      if (!NSRC::kShared && M.active == 0ull) break;
-      llgs_lane_attempt<THERMAL, RECORD, AXIS_Z, true>(L, M, it, out_m, k, tb, rtol, atol, max_step, rec, ek, ns, z2, z3);
-      ++it;
-      const bool go = it < budget;
-      if (NSRC::kShared) { if (!ns.chunk_end_wave(go && M.active != 0ull)) break; }
-      else if (!go) break;
+      llgs_lane_attempt<THERMAL, RECORD, AXIS_Z, true>(L, M, out_m, k, tb, rtol, atol, max_step, rec, ek, ns, z2, z3);
+      // (at least one attempt is made whatever the budget, as ever: the test follows the attempt)
+      if (!ns.chunk_end_go(attempt_loop_next(M.active, __ballot(L.t != L.T), it, budget))) break;
     }
     llgs_masks_close(L, M);
     return llgs_lane_finish<RECORD>(L, out_m, rec, ek, ns);
