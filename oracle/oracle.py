@@ -15,7 +15,7 @@ _SO = os.path.join(_HERE, "_build", "libstg_oracle.so")
 
 __all__ = ["Params", "Config", "EnvState", "StepOut", "lib", "build", "make_params", "make_config",
            "simple_solve", "llgs_solve", "resistance", "thermal_strength", "env_step", "env_step_batch",
-           "thermal_normals", "parse_action", "simple_dmdt", "llgs_rhs", "DEV_TYPES", "sot_torque", "vcma_keff",
+           "thermal_normals", "parse_action", "parse_action_f64", "env_step_f64", "env_step_batch_f64", "simple_dmdt", "llgs_rhs", "DEV_TYPES", "sot_torque", "vcma_keff",
            "ArrayConfig", "make_array_config", "array_coupling", "ArrayEnvState", "array_step", "array_observation", "array_reset_draw",
            "device_field", "ou_update"]
 
@@ -98,6 +98,14 @@ def lib():
         L.stgo_env_step_batch.argtypes = [C.c_int64, C.POINTER(EnvState), C.POINTER(C.c_float),
                                           C.POINTER(Params), C.POINTER(C.c_uint8), C.POINTER(Config),
                                           C.c_uint64, C.POINTER(StepOut), C.c_int]
+        L.stgo_parse_action_f64.restype = None
+        L.stgo_parse_action_f64.argtypes = [dp, C.POINTER(Config), dp, dp]
+        L.stgo_env_step_f64.restype = None
+        L.stgo_env_step_f64.argtypes = [C.POINTER(EnvState), dp, C.POINTER(Params), C.POINTER(Config), C.c_uint64,
+                                        C.POINTER(StepOut)]
+        L.stgo_env_step_batch_f64.restype = None
+        L.stgo_env_step_batch_f64.argtypes = [C.c_int64, C.POINTER(EnvState), dp, C.POINTER(Params), C.POINTER(C.c_uint8),
+                                              C.POINTER(Config), C.c_uint64, C.POINTER(StepOut), C.c_int]
         L.stgo_thermal_normals.restype = None
         L.stgo_thermal_normals.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, dp]
         L.stgo_simple_dmdt.restype = None
@@ -289,6 +297,15 @@ def parse_action(action, c):
     return J.value, T.value
 
 
+def parse_action_f64(action, c):
+    """The same for a float64 action array (both safety clamps run in float64: monitoring.py:304-313 on the array's dtype)."""
+    a = np.ascontiguousarray(action, dtype=np.float64)
+    J = C.c_double()
+    T = C.c_double()
+    lib().stgo_parse_action_f64(_dp(a), C.byref(c), C.byref(J), C.byref(T))
+    return J.value, T.value
+
+
 def simple_dmdt(m, p, gamma, J, h_thermal=None):
     m = np.ascontiguousarray(m, dtype=np.float64)
     out = np.zeros(3)
@@ -404,6 +421,28 @@ def env_step_batch(states, actions, params, cls, c, env_id0=0, n_threads=0):
         cp = cls.ctypes.data_as(C.POINTER(C.c_uint8))
     lib().stgo_env_step_batch(n, states, a.ctypes.data_as(C.POINTER(C.c_float)), params, cp, C.byref(c),
                               env_id0, outs, n_threads)
+    return outs
+
+
+def env_step_f64(state, action, p, c, env_id=0):
+    """env_step with a float64 action array."""
+    a = np.ascontiguousarray(action, dtype=np.float64)
+    out = StepOut()
+    lib().stgo_env_step_f64(C.byref(state), _dp(a), C.byref(p), C.byref(c), env_id, C.byref(out))
+    return out
+
+
+def env_step_batch_f64(states, actions, params, cls, c, env_id0=0, n_threads=0):
+    """env_step_batch with float64 actions [n,2]."""
+    n = len(states)
+    a = np.ascontiguousarray(actions, dtype=np.float64)
+    assert a.shape == (n, 2)
+    outs = (StepOut * n)()
+    cp = None
+    if cls is not None:
+        cls = np.ascontiguousarray(cls, dtype=np.uint8)
+        cp = cls.ctypes.data_as(C.POINTER(C.c_uint8))
+    lib().stgo_env_step_batch_f64(n, states, _dp(a), params, cp, C.byref(c), env_id0, outs, n_threads)
     return outs
 
 

@@ -580,6 +580,18 @@ void stgo_parse_action(const float action[2], const stgo_config* c, double* J, d
     *J = j; *T = t;
 }
 
+/* The same for a float64 action array: np.clip works on the array's own elements, so both safety clamps run in float64
+ * (1e8, 1e-12 and 1e-6 as doubles); the NaN/Inf replacement is still the float32 array [0.0, 1e-12], whose duration
+ * float32(1e-12) < 1e-12 the env's own clip lifts to 1e-12. */
+void stgo_parse_action_f64(const double action[2], const stgo_config* c, double* J, double* T) {
+    double a0 = action[0], a1 = action[1];
+    if (!isnan(a0)) a0 = fmin(fmax(a0, -1e8), 1e8);
+    if (!isnan(a1)) a1 = fmin(fmax(a1, 1e-12), 1e-6);
+    if (isnan(a0) || isnan(a1) || isinf(a0) || isinf(a1)) { a0 = 0.0; a1 = (double)(float)1e-12; }
+    *J = fmin(fmax(a0, -c->max_current), c->max_current);
+    *T = fmin(fmax(a1, 1e-12), c->max_duration);
+}
+
 /* ------------------------------------------------------------------------------------------------
  * A12  _get_observation (vector mode)
  * ------------------------------------------------------------------------------------------------ */
@@ -605,10 +617,8 @@ void stgo_observation(const stgo_env_state* s, const stgo_params* p, const stgo_
 /* ------------------------------------------------------------------------------------------------
  * A10-A14  SpinTorqueEnv.step
  * ------------------------------------------------------------------------------------------------ */
-void stgo_env_step(stgo_env_state* s, const float action[2], const stgo_params* p, const stgo_config* c,
-                   uint64_t env_id, stgo_step_out* out) {
-    double J, T;
-    stgo_parse_action(action, c, &J, &T);
+static void env_step_parsed(stgo_env_state* s, double J, double T, const stgo_params* p, const stgo_config* c,
+                            uint64_t env_id, stgo_step_out* out) {
     s->last_action[0] = J; s->last_action[1] = T;
     double prev_align = dot3(s->m, s->target);                      /* spin_torque_env.py:338-339 */
     /* _simulate_dynamics (spin_torque_env.py:435-488) */
@@ -656,6 +666,33 @@ void stgo_env_step(stgo_env_state* s, const float action[2], const stgo_params* 
     out->status = ok ? (nreset > 0 ? 2 : 0) : 1;
     out->energy = energy;
     out->n_sub = nsub;
+}
+
+void stgo_env_step(stgo_env_state* s, const float action[2], const stgo_params* p, const stgo_config* c,
+                   uint64_t env_id, stgo_step_out* out) {
+    double J, T;
+    stgo_parse_action(action, c, &J, &T);
+    env_step_parsed(s, J, T, p, c, env_id, out);
+}
+
+void stgo_env_step_f64(stgo_env_state* s, const double action[2], const stgo_params* p, const stgo_config* c,
+                       uint64_t env_id, stgo_step_out* out) {
+    double J, T;
+    stgo_parse_action_f64(action, c, &J, &T);
+    env_step_parsed(s, J, T, p, c, env_id, out);
+}
+
+void stgo_env_step_batch_f64(int64_t n, stgo_env_state* s, const double* actions, const stgo_params* params,
+                             const uint8_t* cls, const stgo_config* c, uint64_t env_id0, stgo_step_out* out,
+                             int n_threads) {
+#ifdef _OPENMP
+    if (n_threads <= 0) n_threads = omp_get_max_threads();
+#pragma omp parallel for schedule(dynamic, 16) num_threads(n_threads)
+#endif
+    for (int64_t i = 0; i < n; ++i) {
+        const stgo_params* p = &params[cls ? cls[i] : 0];
+        stgo_env_step_f64(&s[i], &actions[2 * i], p, c, env_id0 + (uint64_t)i, &out[i]);
+    }
 }
 
 void stgo_env_step_batch(int64_t n, stgo_env_state* s, const float* actions, const stgo_params* params,

@@ -133,6 +133,8 @@ double stgo_thermal_strength(const stgo_params* p, double gamma, double temperat
 /* ---- A10: SafetyWrapper.validate_action + _parse_action (utils/monitoring.py:288-315,
  *      envs/spin_torque_env.py:409-433) ---- */
 void stgo_parse_action(const float action[2], const stgo_config* c, double* J, double* T);
+/* a float64 action array: both clamps in float64 (np.clip keeps the array's dtype) */
+void stgo_parse_action_f64(const double action[2], const stgo_config* c, double* J, double* T);
 
 /* ---- A12: _get_observation, vector mode (envs/spin_torque_env.py:490-524) ---- */
 void stgo_observation(const stgo_env_state* s, const stgo_params* p, const stgo_config* c, float obs[12]);
@@ -140,12 +142,17 @@ void stgo_observation(const stgo_env_state* s, const stgo_params* p, const stgo_
 /* ---- A10-A14: one SpinTorqueEnv.step (envs/spin_torque_env.py:310-407) ---- */
 void stgo_env_step(stgo_env_state* s, const float action[2], const stgo_params* p, const stgo_config* c,
                    uint64_t env_id, stgo_step_out* out);
+void stgo_env_step_f64(stgo_env_state* s, const double action[2], const stgo_params* p, const stgo_config* c,
+                       uint64_t env_id, stgo_step_out* out);
 
 /* batch form used by bench.py's cpu_baseline leg and the gloo tests: env i uses params[cls[i]]
  * (cls == NULL -> params[0]); OpenMP-parallel over envs with n_threads threads (<=0 -> default). */
 void stgo_env_step_batch(int64_t n, stgo_env_state* s, const float* actions /*[n][2]*/,
                          const stgo_params* params, const uint8_t* cls, const stgo_config* c,
                          uint64_t env_id0, stgo_step_out* out, int n_threads);
+void stgo_env_step_batch_f64(int64_t n, stgo_env_state* s, const double* actions /*[n][2]*/,
+                             const stgo_params* params, const uint8_t* cls, const stgo_config* c,
+                             uint64_t env_id0, stgo_step_out* out, int n_threads);
 
 /* thermal-field generator, the same construction as the HIP kernels' (restated, not shared code): per (env, env step)
  * one xoshiro128+ stream seeded by Philox4x32-10(key = seed, counter = (env_id, env_step, tag)), 23-bit uniforms,

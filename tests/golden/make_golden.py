@@ -211,7 +211,7 @@ def G5():
     _llgs_cases("G5_llgs_rk45_stt", cases, lambda tag: stt_params(volume=vols[int(tag)]))
 
 
-def _episode(env, m0, target, actions):
+def _episode(env, m0, target, actions, dtype=np.float32):
     env.cache_observations = False          # H2
     env.solver.timeout = 1e9                # wall-clock guard only
     obs0, _ = env.reset(seed=0, options={"initial_state": np.array(m0, dtype=float),
@@ -220,7 +220,7 @@ def _episode(env, m0, target, actions):
                total_energy=[])
     for a in actions:
         get_optimizer().cache.clear()       # H1
-        o, r, te, tr, info = env.step(np.array(a, dtype=np.float32))
+        o, r, te, tr, info = env.step(np.array(a, dtype=dtype))      # (a fresh array: validate_action clamps in place)
         rec["obs"].append(o)
         rec["reward"].append(r)
         rec["terminated"].append(te)
@@ -725,8 +725,95 @@ def G20():
     save("G20_array_edges", **out)
 
 
+G21_LLGS_SETTINGS = ((1e-4, 1e-7, 5e-12, 2.21e5), (1e-8, 1e-11, 2e-13, 1.9e5), (1e-3, 1e-6, 1e-11, 2.5e5), (1e-5, 0.0, 1e-9, 2.21e5))
+G21_SIMPLE_MAX_STEPS = (2.5e-12, 3e-13, 1e-10)
+G21_TARGETS5 = ([0.0, 0.0, 1.0], [0.0, 0.0, -1.0], [0.6, 0.0, 0.8], [0.0, -2.0, 0.0], [1.0, 1.0, 1.0])      # one non-unit, one off-axis
+G21_TARGETS8 = ([0.0, 0.0, 1.0], [0.0, 0.0, -1.0], [0.6, 0.0, 0.8], [0.0, -0.8, 0.6], [1.0, 1.0, 1.0], [-1.0, 2.0, 2.0], [0.28, 0.0, -0.96],
+                [-3.0, -4.0, 12.0])
+G21_CFG5 = dict(success_threshold=0.6, energy_penalty_weight=0.25, max_current=1.5e6, max_duration=2e-9, temperature=250.0)
+
+
+def G21():
+    """env_config: everything of the configuration that decides results, away from its defaults.  (a) LLGSSolver(rtol, atol, max_step,
+    gamma) at four settings; (b) SimpleLLGSSolver(max_step) for rk4 / euler at three; (c) SpinTorqueEnv episodes with 5, 1 and 8
+    target_states and non-default threshold / weight / limits / temperature; (d) episodes stepped with float64 action arrays whose
+    values float32 cannot carry, beyond the env's limits and beyond the safety wrapper's.  The result cache is keyed without max_step,
+    gamma and the current: it is cleared before every solve."""
+    out = {}
+    rng = np.random.default_rng(2121)
+    # (a) LLGSSolver: volume 9.7e-6, three (m0, J, T) cases per setting, T <= 0.3 ns (the 0.2 ps setting gets shorter pulses: points = T / max_step)
+    params = stt_params(volume=9.7e-6)
+    m_up = np.array([0.02, -0.01, 0.9997]); m_up /= np.linalg.norm(m_up)
+    m_r = np.array([0.5, -0.6, 0.3]); m_r /= np.linalg.norm(m_r)
+    m_q = unit_rows(rng, 1)[0]
+    meta = []
+    for s, (rtol, atol, max_step, gamma) in enumerate(G21_LLGS_SETTINGS):
+        scale = 0.12 if max_step < 1e-12 else 1.0
+        cases = ((m_up, 2e6, 3e-10 * scale), (m_r, -1.3e6, float(np.float32(1.7e-10 * scale))), (m_q, 0.0, 6e-11 * scale))
+        solver = LLGSSolver(rtol=rtol, atol=atol, max_step=max_step, gamma=gamma)
+        for k, (m0, J, T) in enumerate(cases):
+            get_optimizer().cache.clear()
+            r = guarded(300, solver.solve, m0.copy(), (0, T), params, pulse(J, T), zero_field, thermal_noise=False, temperature=300.0)
+            print(f"    G21 llgs setting {s} case {k}: {len(r['t'])} points, success={r['success']}")
+            out[f"llgs_t_{s}_{k}"] = r["t"]
+            out[f"llgs_m_{s}_{k}"] = r["m"]
+            meta.append((s, rtol, atol, max_step, gamma, *m0, J, T, bool(r["success"])))
+    out["llgs_cases"] = np.array(meta, dtype=float)
+    out["llgs_volume"] = np.array(9.7e-6)
+    # (b) SimpleLLGSSolver: volume 8.75e-11, four (J, T) cases per (method, max_step), T = 1 ps and a float32-rounded T among them
+    params = stt_params(volume=8.75e-11)
+    m0s = unit_rows(rng, 4)
+    jt = ((0.0, 1e-12), (2e6, float(np.float32(2.5e-10))), (-2e6, 3e-10), (5e5, 7.7e-11))
+    rows = []
+    for method in ("rk4", "euler"):
+        for max_step in G21_SIMPLE_MAX_STEPS:
+            solver = SimpleLLGSSolver(method=method, max_step=max_step, timeout=1e9)
+            for i, (J, T) in enumerate(jt):
+                get_optimizer().cache.clear()
+                r = solver.solve(m0s[i].copy(), (0, T), params, pulse(J, T), zero_field, False, 300.0)
+                rows.append((method == "euler", max_step, i, J, T, bool(r["success"]), r.get("n_steps", -1), *r["m"][-1]))
+    rows = np.array(rows, dtype=float)
+    print(f"    G21 simple: {len(rows)} solves, step counts {sorted(set(rows[:, 6].astype(int)))}")
+    out.update(simple_m0=m0s, simple_volume=np.array(8.75e-11), simple_euler=rows[:, 0].astype(bool), simple_max_step=rows[:, 1],
+               simple_m0_index=rows[:, 2].astype(int), simple_J=rows[:, 3], simple_T=rows[:, 4], simple_success=rows[:, 5].astype(bool),
+               simple_n_steps=rows[:, 6].astype(int), simple_m_last=rows[:, 7:10])
+    # (c), (d) env episodes
+    episodes = []
+
+    def add(tag, env_kwargs, m0, target, actions, dtype=np.float32, volume=8.75e-11):
+        env = SpinTorqueEnv(device_params=stt_params(volume=volume), include_thermal_fluctuations=False, **env_kwargs)
+        rec = _episode(env, m0, target, actions, dtype=dtype)
+        k = len(episodes)
+        for name, arr in rec.items():
+            out[f"ep{k}_{name}"] = arr
+        out[f"ep{k}_actions"] = np.array(actions, dtype=dtype)
+        out[f"ep{k}_m0"] = np.array(m0, dtype=float)
+        out[f"ep{k}_target"] = np.array(target, dtype=float)
+        out[f"ep{k}_target_states"] = np.array(env.target_states, dtype=float)      # as the constructor validated them
+        out[f"ep{k}_volume"] = np.array(volume)
+        episodes.append(tag)
+        print(f"    G21 episode {k} ({tag}): {len(actions)} steps, terminated {list(rec['terminated'])}, truncated {list(rec['truncated'])}")
+
+    cfg5 = dict(G21_CFG5, target_states=[np.array(t) for t in G21_TARGETS5])
+    add("five_targets", dict(cfg5, max_steps=4), [0.3, 0.2, 0.93], G21_TARGETS5[2],
+        [(1.2e6, 3e-10), (-1.8e6, 2.5e-9), (9e5, 4e-10), (-1.5e6, 1e-9)])
+    add("one_target", dict(G21_CFG5, target_states=[np.array([0.0, 3.0, 4.0])], max_steps=3), [0.1, 0.3, -0.9], [0.0, 3.0, 4.0],
+        [(-1.2e6, 5e-10), (1.5e6, 2e-10), (0.0, 1e-10)])
+    add("eight_targets", dict(G21_CFG5, target_states=[np.array(t) for t in G21_TARGETS8], max_steps=3), [0.02, -0.01, 0.9997],
+        G21_TARGETS8[7], [(1.5e6, 1e-9), (1.5e6, 1e-9), (-7e5, 3e-10)])
+    # float64 action arrays: values float32 cannot carry; beyond max_current / max_duration; a duration below 1 ps; NaN
+    add("float64_five_targets", dict(cfg5, max_steps=6), [0.3, 0.2, 0.93], G21_TARGETS5[3],
+        [(1.234567890123e6, 3.3e-10), (1.7e6, 2.5e-9), (-1.234567890123e6, 0.9999e-12), (-9.87654321e5, 1.23456789e-10),
+         (np.nan, 3.3e-10), (1.1e6, np.inf)], dtype=np.float64)
+    # ... and beyond the safety wrapper's 1e8 A/m^2 and 1 us with max_current above 1e8 (volume scaled so that 1e8 A/m^2 is an ordinary drive)
+    add("float64_beyond_safety", dict(cfg5, max_current=3e8, max_steps=5), [0.3, 0.2, 0.93], G21_TARGETS5[0],
+        [(2.5e8, 3.3e-10), (-1.234567890123e8, 1.1e-10), (5.5e7, 3e-6), (-np.inf, 2.2e-10)], dtype=np.float64, volume=8.75e-9)
+    out["episode_tags"] = np.array(episodes)
+    save("G21_env_config", **out)
+
+
 ALL = dict(G18=G18, G17=G17, G16=G16, G15=G15, G14=G14, G1=G1, G2=G2, G3=G3, G4=G4, G5=G5, G6=G6, G7=G7, G8=G8, G9=G9, G10=G10, G11=G11, G12=G12, G13=G13,
-           G19=G19, G20=G20)
+           G19=G19, G20=G20, G21=G21)
 
 if __name__ == "__main__":
     which = sys.argv[1:] or list(ALL)

@@ -144,12 +144,9 @@ class OracleBackend:
         a = np.ascontiguousarray(a.T)          # [N,2]
         f64 = a.dtype == np.float64
         targets = np.asarray(self.cfg.target_states, dtype=np.float64).reshape(-1, 3)
-        if f64:
-            # float64 actions: the safety clamp runs in float64 (monitoring.py:304-313 on a float64 array); the
-            # oracle's C entry takes float32, so apply the clamp here and pass values float32 can carry exactly
-            raise NotImplementedError("OracleBackend handles float32 actions; float64 parity is tested separately")
-        outs_c = oracle.env_step_batch(self.states, a.astype(np.float32), self.params, self.cls, self.ocfg,
-                                       env_id0=self.env_id0)
+        # float64 actions: the safety clamp runs in float64 (monitoring.py:304-313 on a float64 array), the oracle's float64 entry
+        step_batch = oracle.env_step_batch_f64 if f64 else oracle.env_step_batch
+        outs_c = step_batch(self.states, a if f64 else a.astype(np.float32), self.params, self.cls, self.ocfg, env_id0=self.env_id0)
         for i in range(self.n):
             o = outs_c[i]
             obs[:, i] = torch.tensor(list(o.obs), dtype=torch.float32)

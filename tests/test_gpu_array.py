@@ -198,6 +198,62 @@ def test_array_kernels_vs_oracle(stg, case, monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------
+# a2. non-default env configuration
+# ------------------------------------------------------------------------------------------------
+CONFIG_CASES = [((1, 1), "individual", 257), ((4, 4), "global", 257)]
+CONFIG_KW = dict(temperature=250.0, max_duration=2e-9, energy_penalty_weight=0.3, observation_mode="vector")
+
+
+@pytest.mark.parametrize("case", CONFIG_CASES, ids=lambda c: f"{c[0][0]}x{c[0][1]}-{c[1]}-N{c[2]}")
+def test_non_default_temperature_duration_limit_and_energy_weight_vs_oracle(stg, case):
+    """temperature = 250, max_duration = 2e-9, energy_penalty_weight = 0.3 in 'vector' observations, on the smallest 'individual' and 'global'
+    shapes of the table: four steps one at a time and the same four in one step_many launch, against the oracle stepped one at a time.  The
+    configuration is not a no-op: the oracle under the default configuration gives other observations and rewards."""
+    from helpers import OracleArrayBackend
+    shape, mode, n = case
+    n_dev, K = shape[0] * shape[1], 4
+    rng = np.random.default_rng(3000 + CONFIG_CASES.index(case))
+    init = _unit(rng, n, *shape)
+    acts = [_actions(rng, n, shape, mode, s) for s in range(K)]
+    thr = _threshold(n_dev)
+    base = dict(action_mode=mode, coupling_strength=0.2, success_threshold=thr, max_steps=3)
+
+    def stepped(backend, **kw):
+        env = stg.SpinTorqueArrayVecEnv(n, shape, backend=backend, **base, **kw)
+        obs, _ = env.reset(options={"initial_pattern": init})
+        rec = [obs.cpu().numpy().copy()] + [_snap(env, env.step(torch.from_numpy(a))) for a in acts]
+        env.close()
+        return rec
+    ora, hip = stepped(OracleArrayBackend, **CONFIG_KW), stepped(None, **CONFIG_KW)
+    for s in range(1, K + 1):
+        assert np.abs(_similarity(ora[s], n_dev) - thr).min() > 1e-9, (s, "pick another seed")
+    assert np.allclose(hip[0], ora[0], rtol=2e-7, atol=1e-12)
+    worst = max(_compare(hip[s], ora[s], (case, s)) for s in range(1, K + 1))
+    print(f"array-dm non-default configuration {shape} {mode} worst |dm| = {worst:.3e}")
+    env = stg.SpinTorqueArrayVecEnv(n, shape, **base, **CONFIG_KW)
+    env.reset(options={"initial_pattern": init})
+    obs, r, te, tr, info = env.step_many(torch.from_numpy(np.stack(acts)))
+    c = lambda t: t.cpu().numpy().copy()
+    many = dict(obs=c(obs), reward=c(info["reward_f64"]), reward32=c(r), term=c(te), trunc=c(tr), energy=c(info["energy"]))
+    last = _snap(env, (obs[-1], r[-1], te[-1], tr[-1], dict(reward_f64=info["reward_f64"][-1], energy=info["energy"][-1])))
+    env.close()
+    for s in range(K):
+        ctx = (case, "step_many", s)
+        o = ora[s + 1]
+        assert np.allclose(many["obs"][s], o["obs"], rtol=3e-7, atol=1e-10, equal_nan=True), ctx
+        assert np.allclose(many["reward"][s], o["reward"], rtol=1e-9, atol=1e-9, equal_nan=True), ctx
+        assert np.array_equal(many["term"][s], o["term"]) and np.array_equal(many["trunc"][s], o["trunc"]), ctx
+        assert np.allclose(many["energy"][s], o["energy"], rtol=1e-10, atol=0, equal_nan=True), ctx
+    _compare(last, ora[K], (case, "step_many", "state"))
+    # what the configuration changes: the temperature entry of the vector observation, the energy term of the reward, the duration clamp
+    dflt = stepped(OracleArrayBackend, observation_mode="vector")
+    assert not np.allclose(ora[1]["obs"], dflt[1]["obs"], rtol=1e-3, atol=1e-6) and (ora[1]["reward"] != dflt[1]["reward"]).any()
+    if mode != "global":            # ('global' mode has no duration in its action -- the pulse is 1 ns -- and its energy term is ~1e-9 of the reward)
+        assert not np.allclose(ora[1]["energy"], dflt[1]["energy"], rtol=1e-3, atol=0)
+        assert not np.allclose(ora[1]["reward"], dflt[1]["reward"], rtol=1e-3, atol=1e-6)
+
+
+# ------------------------------------------------------------------------------------------------
 # b. every output written, nothing else touched
 # ------------------------------------------------------------------------------------------------
 GUARD_CASES = [

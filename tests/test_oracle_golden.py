@@ -503,3 +503,114 @@ def test_g18_stable_states_relaxations(golden, oracle_mod):
                 states.append(r["m_final"])
         ref_states = g[f"{tag}_stable_states"]
         assert len(states) == len(ref_states) == 2 and np.abs(np.array(states) - ref_states).max() <= 1e-8
+
+
+# ------------------------------------------------------------------------------------------------
+# G21: the configuration away from its defaults (solver constants, episode fields, target lists, float64 actions)
+# ------------------------------------------------------------------------------------------------
+G21_CFG5 = dict(success_threshold=0.6, energy_penalty_weight=0.25, max_current=1.5e6, max_duration=2e-9, temperature=250.0)
+G21_EPISODE_CFG = {
+    "five_targets": dict(G21_CFG5, max_steps=4),
+    "one_target": dict(G21_CFG5, max_steps=3),
+    "eight_targets": dict(G21_CFG5, max_steps=3),
+    "float64_five_targets": dict(G21_CFG5, max_steps=6),
+    "float64_beyond_safety": dict(G21_CFG5, max_current=3e8, max_steps=5),
+}
+
+
+def g21_llgs_settings(g):
+    """-> [(rtol, atol, max_step, gamma)] in the order of the golden's setting index"""
+    rows = g["llgs_cases"]
+    return [tuple(rows[rows[:, 0] == s][0, 1:5]) for s in sorted(set(rows[:, 0].astype(int)))]
+
+
+def test_g21_llgs_solver_constants(golden, oracle_mod):
+    """LLGSSolver(rtol, atol, max_step, gamma) at four non-default settings: accepted points, times and states (as G4 / G5)."""
+    o = oracle_mod
+    g = golden("G21_env_config")
+    p = o.make_params(stt_default_params(volume=float(g["llgs_volume"])))
+    settings = g21_llgs_settings(g)
+    assert len(settings) == 4 and len(g["llgs_cases"]) == 12
+    per_setting = {}
+    for row in g["llgs_cases"]:
+        s, (rtol, atol, max_step, gamma), m0, J, T, succ = int(row[0]), row[1:5], row[5:8], row[8], row[9], bool(row[10])
+        k = per_setting.setdefault(s, 0)
+        per_setting[s] += 1
+        c = o.make_config("rk45", rtol=rtol, atol=atol, max_step=max_step, gamma=gamma)
+        r = o.llgs_solve(m0, T, p, c, J)
+        rt, rm = g[f"llgs_t_{s}_{k}"], g[f"llgs_m_{s}_{k}"]
+        assert T <= 3e-10 and r["success"] == succ
+        assert r["n_points"] == len(rt), (s, k, r["n_points"], len(rt))
+        assert np.abs(r["t"] - rt).max() <= 1e-9 * T
+        assert np.abs(r["m"] - rm).max() <= 1e-9, (s, k, np.abs(r["m"] - rm).max())
+        # each setting is its own computation: the default constants give another point count or another end point
+        d = o.llgs_solve(m0, T, p, o.make_config("rk45"), J)
+        assert d["n_points"] != len(rt) or np.abs(d["m_final"] - rm[-1]).max() > 1e-9, (s, k)
+
+
+def test_g21_simple_solver_max_step(golden, oracle_mod):
+    """SimpleLLGSSolver(max_step) for rk4 and euler: step count (the truncation of T / dt, H5), success and the last row (as G2)."""
+    o = oracle_mod
+    g = golden("G21_env_config")
+    p = o.make_params(stt_default_params(volume=float(g["simple_volume"])))
+    assert set(g["simple_max_step"]) == {2.5e-12, 3e-13, 1e-10} and len(g["simple_T"]) == 24
+    assert 1e-12 in g["simple_T"] and any(T == float(np.float32(T)) and T != 1e-12 for T in g["simple_T"])
+    worst = 0.0
+    for k in range(len(g["simple_T"])):
+        c = o.make_config("euler" if g["simple_euler"][k] else "rk4", max_step=float(g["simple_max_step"][k]))
+        r = o.simple_solve(g["simple_m0"][g["simple_m0_index"][k]], g["simple_T"][k], p, c, g["simple_J"][k])
+        assert r["success"] == bool(g["simple_success"][k]), k
+        assert r["n_steps"] == g["simple_n_steps"][k], (k, r["n_steps"], g["simple_n_steps"][k])
+        worst = max(worst, np.abs(r["m_final"] - g["simple_m_last"][k]).max())
+    assert worst <= 1e-11, worst
+    assert len(set(g["simple_n_steps"])) >= 4           # max_step does set the sub-step count
+
+
+def g21_episode(g, k, o):
+    """Oracle state, parameters and configuration at the start of G21 episode k, and whether its actions are float64."""
+    tag = str(g["episode_tags"][k])
+    p = o.make_params(stt_default_params(volume=float(g[f"ep{k}_volume"])))
+    c = o.make_config("rk4", thermal=False, **G21_EPISODE_CFG[tag])
+    s = o.EnvState()
+    m0, tgt = g[f"ep{k}_m0"], g[f"ep{k}_target"]
+    s.m[:] = list(m0 / np.linalg.norm(m0))
+    s.target[:] = list(tgt / np.linalg.norm(tgt))
+    return tag, p, c, s, g[f"ep{k}_actions"].dtype == np.float64
+
+
+def test_g21_env_episodes_and_float64_actions(golden, oracle_mod):
+    """SpinTorqueEnv episodes with 5 / 1 / 8 target_states and non-default threshold, weight, limits and temperature; two of them stepped
+    with float64 action arrays (the oracle's float64 entry).  Tolerances of G6."""
+    o = oracle_mod
+    g = golden("G21_env_config")
+    tags = [str(t) for t in g["episode_tags"]]
+    assert tags == list(G21_EPISODE_CFG)
+    assert [len(g[f"ep{k}_target_states"]) for k in range(3)] == [5, 1, 8]
+    for k, tag in enumerate(tags):
+        ts = g[f"ep{k}_target_states"]
+        assert np.abs(np.linalg.norm(ts, axis=1) - 1).max() <= 1e-15           # the constructor normalises the list
+        tag, p, c, s, f64 = g21_episode(g, k, o)
+        assert f64 == tag.startswith("float64")
+        acts = g[f"ep{k}_actions"]
+        if f64:             # the recorded actions are not float32 values, and some lie beyond every limit
+            finite = acts[np.isfinite(acts)]
+            assert np.any(finite.astype(np.float32).astype(np.float64) != finite)
+            assert np.nanmax(np.abs(acts[:, 0])) > c.max_current and np.nanmax(acts[:, 1]) > c.max_duration
+        for j, a in enumerate(acts):
+            out = o.env_step_f64(s, a, p, c) if f64 else o.env_step(s, a, p, c)
+            ref_obs = g[f"ep{k}_obs"][j + 1]
+            assert np.allclose(np.array(out.obs[:]), ref_obs, rtol=2e-7, atol=1e-12), (tag, j, np.array(out.obs[:]), ref_obs)
+            ref_r = g[f"ep{k}_reward"][j]
+            assert abs(out.reward - ref_r) <= 1e-11 * max(1.0, abs(ref_r)), (tag, j, out.reward, ref_r)
+            assert bool(out.terminated) == bool(g[f"ep{k}_terminated"][j]), (tag, j)
+            assert bool(out.truncated) == bool(g[f"ep{k}_truncated"][j]), (tag, j)
+            assert (out.status != 1) == bool(g[f"ep{k}_success"][j]), (tag, j)
+            ref_e = g[f"ep{k}_energy"][j]
+            assert abs(out.energy - ref_e) <= 1e-13 * max(abs(ref_e), 1e-300), (tag, j)
+            assert np.abs(np.array(s.m[:]) - g[f"ep{k}_m"][j + 1]).max() <= 1e-11, (tag, j)
+            if f64:         # what the float64 clamps made of the action is what the observation reports (obs 10, 11)
+                J, T = o.parse_action_f64(a, c)
+                assert np.float32(J / c.max_current) == ref_obs[10] and np.float32(T / c.max_duration) == ref_obs[11], (tag, j, J, T)
+    # beyond the safety wrapper: 2.5e8 A/m^2 came back as 1e8 under max_current = 3e8, 3 us as max_duration
+    k = tags.index("float64_beyond_safety")
+    assert g[f"ep{k}_obs"][1][10] == np.float32(1e8 / 3e8) and g[f"ep{k}_obs"][3][11] == np.float32(1.0)
