@@ -197,8 +197,8 @@ int stg_set_params_per_env(stg_ctx* ctx, const double* soa_params, const uint8_t
  * device.validate_magnetization does); NULL: drawn on the device (normal(0,1,3) normalised; uniform choice among
  * cfg.targets) from Philox(seed, env_id, episode).  obs_out [dev] float[12][N] (cfg.out_layout = STG_OUT_RECORDS: the
  * record array, 8-byte aligned: the obs fields of every env are written -- a masked call reports the current observation of
- * the envs it leaves alone --, the reward/flag fields are zeroed for the reset envs and left untouched for the others)
- * may be NULL. */
+ * the envs it leaves alone --, the reward/flag fields are zeroed for the reset envs and left untouched for the others: bytes
+ * 0-47 of every record are written, bytes 48-55 of the reset envs' records only) may be NULL. */
 int stg_reset(stg_ctx* ctx, const uint8_t* mask, const double* init_m, const double* target,
               uint64_t seed, float* obs_out, void* stream);
 
@@ -298,7 +298,12 @@ int stg_solve(stg_ctx* ctx, const double* m0, const double* J, const double* T, 
 /* as stg_solve, additionally recording the trajectory: the first traj_cap rows of t [traj_cap][N],
  * m [traj_cap][3][N] (normalised rows, llgs_solver.py:152-153), energy [traj_cap][N] (llgs_solver.py:239-262) and
  * torques [traj_cap][N] = |tau_stt| + |tau_fl| at each accepted point (llgs_solver.py:159-172); energy and torques are
- * the LLGSSolver result dict's by-products: RK45 only, either may be NULL.  Row 0 is t0. */
+ * the LLGSSolver result dict's by-products: RK45 only, either may be NULL; t and m may be NULL too.  Row 0 is t0.
+ * Footprint: lane i writes rows 0 ... min(n_points[i], traj_cap - 1) of each array and nothing else -- the rows behind a lane's last
+ * point, and everything from row traj_cap on, are left untouched (not zeroed); m_final, n_points and success do not depend on
+ * traj_cap.  A failed solve (success = 0; m_final = m0): a fixed-step solve whose inputs are rejected (T <= 0, a non-finite m0,
+ * an invalid parameter set) records NO row, not even row 0, and reports n_points = 0.  An RK45 solve that exhausts
+ * cfg.max_attempts keeps the rows of the points it accepted until then, and n_points counts them. */
 int stg_solve_traj(stg_ctx* ctx, const double* m0, const double* J, const double* T, uint32_t env_step,
                    int32_t traj_cap, double* t, double* m, double* energy, double* torques,
                    double* m_final, int32_t* n_points, uint8_t* success, void* stream);

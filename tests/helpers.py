@@ -349,3 +349,82 @@ class OracleArrayBackend:
                     target=torch.from_numpy(np.stack([s.target.reshape(-1) for s in self.states], axis=1).copy()),
                     total_energy=torch.tensor([s.total_energy.value for s in self.states], dtype=torch.float64),
                     step_count=torch.tensor([s.step_count.value for s in self.states], dtype=torch.int32))
+
+
+# ------------------------------------------------------------------------------------------------
+# write-footprint guards (tests/test_gpu_write_footprint.py, tests/test_footprint_checker.py)
+# ------------------------------------------------------------------------------------------------
+# A caller-owned output array is handed to the C-ABI as the interior of a larger allocation that is filled with a sentinel bit
+# pattern: a store outside the logical array lands in a guard (and fails an assertion instead of faulting), an element that is never
+# written keeps the sentinel.  The patterns are quiet NaNs with a recognisable payload (no kernel computes them), 0xA5 bytes (flags are
+# <= 1, status <= 4) and 0xA5A5A5A5 words; they are compared as integers, never with isnan.
+GUARD_TILE = 4096                      # the sorted schedule's slot space is whole tiles of this many envs
+GUARD_ALIGN = 256                      # bytes: the interior starts on this boundary, like an allocation of its own
+_SENTINEL = {torch.float32: (torch.int32, 0x7FC5A5A5), torch.float64: (torch.int64, 0x7FF8A5A5A5A5A5A5),
+             torch.uint8: (torch.uint8, 0xA5), torch.int32: (torch.int32, 0xA5A5A5A5 - (1 << 32))}
+
+
+def sentinel_bits(dtype):
+    """(integer dtype of the same width, the sentinel as a value of that dtype)"""
+    return _SENTINEL[dtype]
+
+
+class Guarded:
+    """A sentinel-filled allocation around one logical array of `shape` whose axis `n_axis` is the env axis (length N, or M).
+
+    `interior` is the contiguous view whose data_ptr() goes to the library.  Multi-row arrays are ONE flat block with the real row
+    stride between a front and a back guard (a stride mix-up then shows as a wrong value or an unwritten element):
+      back guard  >= the elements the array would have with N rounded up to the next multiple of 4096, plus one more row,
+      front guard >= one row (the block along the env axis: N x the trailing dimensions), the interior 256-byte aligned.
+    `min_back`: a larger back guard in elements (a capped array whose uncapped form must still fit inside the allocation)."""
+
+    def __init__(self, name, shape, dtype, n_axis=-1, device="cuda", min_back=0):
+        self.name, self.dtype = name, dtype
+        self.bits_dtype, self.sentinel = sentinel_bits(dtype)
+        shape = tuple(int(s) for s in shape)
+        n_axis = n_axis % len(shape)
+        n = shape[n_axis]
+        numel = int(np.prod(shape))
+        row = n * int(np.prod(shape[n_axis + 1:], dtype=np.int64))
+        n_up = -(-n // GUARD_TILE) * GUARD_TILE
+        item = torch.empty(0, dtype=dtype).element_size()
+        per_line = GUARD_ALIGN // item
+        self.back = max(numel // n * n_up + row, int(min_back))
+        raw_numel = row + 2 * per_line + numel + self.back
+        self.raw = torch.empty(raw_numel, dtype=self.bits_dtype, device=device)
+        self.raw.fill_(self.sentinel)
+        lo = row                       # first element at or behind one row whose address is a multiple of GUARD_ALIGN
+        while (self.raw.data_ptr() + lo * item) % GUARD_ALIGN:
+            lo += 1
+        assert lo < row + 2 * per_line
+        self.front, self.numel, self.shape = lo, numel, shape
+        self.interior = self.raw[lo:lo + numel].view(dtype).view(shape)
+        assert self.interior.is_contiguous() and self.interior.data_ptr() % GUARD_ALIGN == 0
+
+    def bits(self):
+        """the interior as integers (same shape)"""
+        return self.raw[self.front:self.front + self.numel].view(self.shape)
+
+    def untouched(self):
+        """bool tensor of the interior's shape: the element still holds the sentinel"""
+        return self.bits() == self.sentinel
+
+    def check_guards(self):
+        """Asserts that every guard element, in front of the interior and behind it, still holds the sentinel."""
+        front, back = self.raw[:self.front], self.raw[self.front + self.numel:]
+        for where, g in (("front", front), ("back", back)):
+            bad = (g != self.sentinel).nonzero()
+            assert bad.numel() == 0, f"{self.name}: {where} guard overwritten at {bad.reshape(-1)[:8].tolist()} ({bad.shape[0]} elements, guard of {g.numel()})"
+
+    def check(self, written=True):
+        """check_guards(), and the interior elements selected by `written` (True: all, False: none, or a bool tensor broadcastable to
+        the interior's shape) do NOT hold the sentinel while every other interior element still does.  Returns the interior."""
+        self.check_guards()
+        un = self.untouched()
+        want = torch.as_tensor(written, dtype=torch.bool, device=un.device).expand(un.shape) if not isinstance(written, bool) \
+            else torch.full(un.shape, written, dtype=torch.bool, device=un.device)
+        miss = (un & want).nonzero()
+        assert miss.numel() == 0, f"{self.name}: {miss.shape[0]} elements were never written, first at {miss[:4].tolist()}"
+        extra = (~un & ~want).nonzero()
+        assert extra.numel() == 0, f"{self.name}: {extra.shape[0]} elements that must stay untouched were written, first at {extra[:4].tolist()}"
+        return self.interior
