@@ -70,6 +70,7 @@ enum { STG_OUT_SOA = 0, STG_OUT_RECORDS = 1 };
 
 #define STG_MAX_TARGETS 8
 #define STG_MAX_CLASSES 64
+#define STG_MAX_KNOTS 32          /* knots of one piecewise-linear waveform (stg_solve_wave) */
 
 /* SpinTorqueEnv.__init__ keyword arguments + solver constructor arguments
  * (spin_torque_env.py:36-53,93-102; llgs_solver.py:24-31; simple_solver.py:24-31) */
@@ -287,9 +288,10 @@ int stg_get_placement(stg_ctx* ctx, int32_t launches_back, uint32_t* out, int32_
 
 /* ---- solver level ------------------------------------------------------------------------------------- */
 
-/* RobustLLGSSolver.solve / LLGSSolver.solve over (0, T[i]) with current_func(t) = J[i] if t <= T[i] else 0 and zero
- * applied field, as SpinTorqueEnv._simulate_dynamics calls it (spin_torque_env.py:442-459), for N independent
- * problems.  m0 double[3][N]; J, T double[N]; m_final double[3][N] (last trajectory row; m0 when success = 0);
+/* RobustLLGSSolver.solve / LLGSSolver.solve over (0, T[i]) for N independent problems.  stg_solve and stg_solve_traj integrate
+ * the rectangular form -- current_func(t) = J[i] if t <= T[i] else 0 and zero applied field, as SpinTorqueEnv._simulate_dynamics
+ * calls the solvers (spin_torque_env.py:442-459); stg_solve_wave below takes current_func(t) and field_func(t) as
+ * piecewise-linear tables.  m0 double[3][N]; J, T double[N]; m_final double[3][N] (last trajectory row; m0 when success = 0);
  * n_points int32[N] (RK4/Euler: sub-steps n; RK45: accepted points excluding t0); success uint8[N].
  * env_step: Philox counter word (thermal on only).  Uses the context's config and parameter table/classes. */
 int stg_solve(stg_ctx* ctx, const double* m0, const double* J, const double* T, uint32_t env_step,
@@ -307,6 +309,48 @@ int stg_solve(stg_ctx* ctx, const double* m0, const double* J, const double* T, 
 int stg_solve_traj(stg_ctx* ctx, const double* m0, const double* J, const double* T, uint32_t env_step,
                    int32_t traj_cap, double* t, double* m, double* energy, double* torques,
                    double* m_final, int32_t* n_points, uint8_t* success, void* stream);
+
+/* The same solvers with piecewise-linear waveforms for current_func(t) [A/m^2] and field_func(t) [A/m, three components].
+ *
+ * A waveform is K knots, 2 <= K <= STG_MAX_KNOTS: times tk[0] < tk[1] < ... < tk[K-1], strictly increasing and finite, and values
+ * vk (finite).  Its value at time t:
+ *   t <= tk[0]   -> vk[0]
+ *   t >= tk[K-1] -> vk[K-1]
+ *   otherwise    -> k = the largest index with tk[k] <= t (k <= K-2),
+ *                   v = vk[k] + (t - tk[k]) * ((vk[k+1] - vk[k]) / (tk[k+1] - tk[k]))
+ *                   in IEEE fp64 with the quotient rounded first, then the product, then the sum (no FMA contraction); each field
+ *                   component is evaluated separately.
+ * The integration span is still (0, T[i]); the knots need not cover it and may extend past it.  A current table has no built-in
+ * t <= T gate: what the table says is what the solver sees, also at a stage time an ulp beyond T (the gate belongs to the
+ * rectangular form only).  The solvers use the value as the reference does, per RHS call at that call's own time:
+ *   RK4 / Euler (simple_solver.py:297-388): the Slonczewski term is on iff |current| > 1e-12 at that stage, h_applied is added to
+ *     the effective field; stage times are t_i, t_i + dt/2, t_i + dt with t_i = i * dt (np.linspace).  RobustLLGSSolver's gates
+ *     (robust_solver.py:152-205) apply as in stg_solve.
+ *   RK45 (llgs_solver.py:92-126,182-237): torques are off iff |current| < 1e-12, h_applied starts h_eff; stage times are
+ *     t + c h (SciPy rk_step).  The by-products of each accepted point use the waveforms at that point's time: energy includes the
+ *     Zeeman term -mu_0 Ms V m.h_applied (llgs_solver.py:250), torques use current(t).
+ *
+ * Tables are per problem, problem index fastest [dev]: tj, jk double[kj][N]; th double[kh][N]; hk double[kh][3][N].
+ *   kj = 0: no current table -- the rectangular J[i] while t <= T[i] of stg_solve (J must be non-NULL; tj, jk unused).  With kj > 0, J
+ *           is not read and may be NULL.
+ *   kh = 0: zero field (th, hk unused).
+ * A knot count of 1 or above STG_MAX_KNOTS (or negative), a missing pointer, or traj_cap < 0 returns STG_E_INVALID with nothing
+ * launched.  Table CONTENTS are checked on the device: a problem whose table is not strictly increasing or not finite fails like a
+ * rejected input -- success = 0, m_final = m0, n_points = 0, no trajectory row -- and leaves the other problems as they are.
+ *
+ * traj_cap = 0 (t, m, energy, torques then unused, NULL) is the plain solve; traj_cap >= 1 records as stg_solve_traj does, with the
+ * same footprint: lane i writes rows 0 ... min(n_points[i], traj_cap - 1) of each array and nothing else -- the rows behind a lane's
+ * last point, and everything from row traj_cap on, are left untouched (not zeroed); m_final, n_points and success do not depend on
+ * traj_cap.  energy and torques are RK45 only; any of t, m, energy, torques, n_points, success may be NULL.  A failed solve
+ * (success = 0; m_final = m0): a solve whose inputs are rejected (fixed-step: T <= 0, a non-finite m0, an invalid parameter set; any
+ * solver: a bad table) records NO row, not even row 0, and reports n_points = 0.  An RK45 solve that exhausts cfg.max_attempts keeps
+ * the rows of the points it accepted until then, and n_points counts them.
+ * Enqueues kernels only (no synchronisation, no allocation); works on the class table (stg_set_params), as stg_solve does.  The
+ * thermal field draws from the same per-problem stream as stg_solve: with all-zero tables the two agree up to rounding. */
+int stg_solve_wave(stg_ctx* ctx, const double* m0, const double* J, const double* T, int32_t kj, const double* tj,
+                   const double* jk, int32_t kh, const double* th, const double* hk, uint32_t env_step, int32_t traj_cap,
+                   double* t, double* m, double* energy, double* torques, double* m_final, int32_t* n_points, uint8_t* success,
+                   void* stream);
 
 /* ---- device-class formulas (opt-in torque model) ------------------------------------------- */
 

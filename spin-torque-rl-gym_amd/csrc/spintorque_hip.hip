@@ -12,6 +12,7 @@
 // constants are read through scalar loads (SGPRs); with several each lane reads its row of derived constants from LDS;
 // with per-env parameters each lane derives its constants from its env's record into registers (step kernel, MULTI == 2).
 #include "stg_kernels.hpp"
+#include "stg_wave.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -780,6 +781,36 @@ int stg_solve_traj(stg_ctx* ctx, const double* m0, const double* J, const double
                    double* t, double* m, double* energy, double* torques, double* m_final, int32_t* n_points, uint8_t* success,
                    void* stream) {
     return solve_common(ctx, m0, J, T, env_step, traj_cap, t, m, energy, torques, m_final, n_points, success, stream, true);
+}
+
+// the waveform solve: its kernels live in stg_solve_wave.hip (stg_wave_launch); stg_solve_kernel is not involved
+int stg_solve_wave(stg_ctx* ctx, const double* m0, const double* J, const double* T, int32_t kj, const double* tj, const double* jk,
+                   int32_t kh, const double* th, const double* hk, uint32_t env_step, int32_t traj_cap, double* t, double* m,
+                   double* energy, double* torques, double* m_final, int32_t* n_points, uint8_t* success, void* stream) {
+    if (!ctx) return fail(STG_E_INVALID, "ctx is NULL");
+    if (!ctx->have_params) return fail(STG_E_STATE, "stg_set_params must precede stg_solve_wave");
+    if (ctx->per_env) return fail(STG_E_STATE, "stg_solve* works on the class table (stg_set_params), not on per-env parameters");
+    if (!m0 || !T || !m_final) return fail(STG_E_INVALID, "m0/T/m_final must not be NULL");
+    if (kj != 0 && (kj < 2 || kj > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kj must be 0 or 2 ... STG_MAX_KNOTS");
+    if (kh != 0 && (kh < 2 || kh > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kh must be 0 or 2 ... STG_MAX_KNOTS");
+    if (kj == 0 && !J) return fail(STG_E_INVALID, "J must not be NULL without a current table (kj = 0)");
+    if (kj != 0 && (!tj || !jk)) return fail(STG_E_INVALID, "tj/jk must not be NULL with kj > 0");
+    if (kh != 0 && (!th || !hk)) return fail(STG_E_INVALID, "th/hk must not be NULL with kh > 0");
+    if (traj_cap < 0) return fail(STG_E_INVALID, "traj_cap must be >= 0");
+    HIP_TRY(hipSetDevice(ctx->device));
+    WaveSolveArgs w{};
+    SolveArgs& a = w.s;
+    a.c = cfg_view(ctx->cfg); a.N = ctx->N; a.env_id0 = ctx->env_id0;
+    a.ctab = ctx->ctab; a.cls = ctx->cls; a.ncls = ctx->ncls;
+    a.m0 = m0; a.J = J; a.T = T; a.env_step = env_step; a.m_final = m_final; a.n_points = n_points; a.success = success;
+    const bool record = traj_cap > 0;
+    a.traj_cap = traj_cap;
+    if (record) { a.traj_t = t; a.traj_m = m; a.traj_e = energy; a.traj_tq = torques; }
+    w.kj = kj; w.tj = tj; w.jk = jk; w.kh = kh; w.th = th; w.hk = hk;
+    const bool thermal = ctx->cfg.solver == STG_SOLVER_RK45 ? ctx->cfg.thermal != 0 : (ctx->cfg.thermal && ctx->cfg.temperature > 0);
+    stg_wave_launch(w, ctx->cfg.solver, thermal, ctx->ncls > 1, record, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return STG_OK;
 }
 
 int stg_get_state(stg_ctx* ctx, double* m, double* target, double* total_energy, int32_t* step_count, uint32_t* rng_step,

@@ -404,7 +404,11 @@ class HipBackend:
         self._keep = (m, tg, e, sc, rs, dn)
 
     # -- solver level -------------------------------------------------------------------------------
-    def solve(self, m0, J, T, env_step=0, traj_cap=0, want_energy=False):
+    def solve(self, m0, J, T, env_step=0, traj_cap=0, want_energy=False, wave=None):
+        """N solves over (0, T).  wave = None: rectangular pulses J while t <= T, zero field (stg_solve / stg_solve_traj).
+        wave = dict(current=(tj [K,N], jk [K,N]) | None, field=(th [K,N], hk [K,3,N]) | None): piecewise-linear waveforms
+        (stg_solve_wave; a missing current table means the rectangular J, a missing field table zero field; J may be None
+        with a current table)."""
         n, dev = self.n, self.device
         m0 = self._dev(m0, torch.float64, (3, n))
         J = self._dev(J, torch.float64, (n,))
@@ -413,16 +417,34 @@ class HipBackend:
         npts = torch.empty(n, dtype=torch.int32, device=dev)
         succ = torch.empty(n, dtype=torch.uint8, device=dev)
         out = dict(m_final=mf, n_points=npts, success=succ)
+        t = m = e = tq = None
         if traj_cap > 0:
             t = torch.zeros((traj_cap, n), dtype=torch.float64, device=dev)
             m = torch.zeros((traj_cap, 3, n), dtype=torch.float64, device=dev)
             # energy and torques are LLGSSolver's by-products (llgs_solver.py:154-172), recorded together
             e = torch.zeros((traj_cap, n), dtype=torch.float64, device=dev) if want_energy else None
             tq = torch.zeros((traj_cap, n), dtype=torch.float64, device=dev) if want_energy else None
+            out.update(t=t, m=m, energy=e, torques=tq)
+        if wave is not None:
+            tj = jk = th = hk = None
+            kj = kh = 0
+            if wave.get("current") is not None:
+                tj, jk = wave["current"]
+                kj = int(torch.as_tensor(tj).shape[0])
+                tj, jk = self._dev(tj, torch.float64, (kj, n)), self._dev(jk, torch.float64, (kj, n))
+            if wave.get("field") is not None:
+                th, hk = wave["field"]
+                kh = int(torch.as_tensor(th).shape[0])
+                th, hk = self._dev(th, torch.float64, (kh, n)), self._dev(hk, torch.float64, (kh, 3, n))
+            _lib.check(self.lib.stg_solve_wave(self._ctx, _ptr(m0), _ptr(J), _ptr(T), kj, _ptr(tj), _ptr(jk), kh, _ptr(th), _ptr(hk),
+                                               int(env_step), int(traj_cap), _ptr(t), _ptr(m), _ptr(e), _ptr(tq), _ptr(mf),
+                                               _ptr(npts), _ptr(succ), self._stream()))
+            self._keep = (m0, J, T, tj, jk, th, hk)
+            return out
+        if traj_cap > 0:
             _lib.check(self.lib.stg_solve_traj(self._ctx, _ptr(m0), _ptr(J), _ptr(T), int(env_step), int(traj_cap),
                                                _ptr(t), _ptr(m), _ptr(e), _ptr(tq), _ptr(mf), _ptr(npts), _ptr(succ),
                                                self._stream()))
-            out.update(t=t, m=m, energy=e, torques=tq)
         else:
             _lib.check(self.lib.stg_solve(self._ctx, _ptr(m0), _ptr(J), _ptr(T), int(env_step), _ptr(mf),
                                           _ptr(npts), _ptr(succ), self._stream()))

@@ -5,11 +5,20 @@
   RobustLLGSSolver ...... utils/robust_solver.py:22-345   (input/output gates, fallback result)
   ThermalFluctuations ... physics/thermal_model.py:12-137 (Brown field strength, white / OU field generator)
 
-`solve()` keeps the reference signature and result dict ('t', 'm', 'success', and for LLGSSolver 'energy').  The GPU
-integrates rectangular pulses -- current_func(t) = J while t <= T, else 0, zero applied field -- which is the only
-form SpinTorqueEnv ever passes (spin_torque_env.py:442-447); `solve()` recognises that form by probing the callable
-and raises NotImplementedError for anything else (arbitrary Python callables cannot run in a kernel).  The batched
-entry `solve_batch()` takes arrays of (m0, J, T) and is what a vectorised caller should use.
+`solve()` keeps the reference signature and result dict ('t', 'm', 'success', and for LLGSSolver 'energy').  A Python
+callable cannot run in a kernel, so `current_func` and `field_func` come in two forms the GPU integrates:
+
+  * `PiecewiseLinear(times, values)` (below): a table of 2 ... 32 knots, for the current (scalar values) and / or the
+    applied field (three components, A/m) -- rise and fall times, bipolar or pre-charge pulses, field-assisted
+    switching, a bias field during relaxation.  The kernels evaluate the table per RHS call at that call's own time,
+    with exactly the arithmetic of `PiecewiseLinear.__call__`, so the same object can be handed to the reference's
+    solvers.
+  * the rectangular pulse -- current_func(t) = J while t <= T, else 0, zero applied field -- the only form
+    SpinTorqueEnv ever passes (spin_torque_env.py:442-447); `solve()` recognises it by probing the callable.
+
+Any mixture works (table current with no field, rectangular callable with a table field, two tables with different
+knots); any other callable raises NotImplementedError.  The batched entry `solve_batch()` takes arrays of (m0, J, T),
+optionally `current_knots` / `field_knots`, and is what a vectorised caller should use.
 
 SimpleLLGSSolver here always applies RobustLLGSSolver's gates, because that is the only way the reference env runs it;
 the two classes differ only in their constructor signature.  The result cache of the reference (keyed
@@ -49,6 +58,86 @@ def _flat_for(device_params: Dict[str, Any], device_type: str = "stt_mram", vali
     return p
 
 
+MAX_KNOTS = 32          # STG_MAX_KNOTS of include/spintorque_hip.h
+
+
+class PiecewiseLinear:
+    """A piecewise-linear waveform: K knots (2 <= K <= 32) at strictly increasing, finite `times`; `values` [K] (a current,
+    A/m^2) or [K,3] (an applied field, A/m).  Calling it evaluates at time t, in plain Python floats:
+
+        t <= times[0]   -> values[0]
+        t >= times[-1]  -> values[-1]
+        otherwise       -> k = the largest index with times[k] <= t,
+                           values[k] + (t - times[k]) * ((values[k+1] - values[k]) / (times[k+1] - times[k]))
+
+    -- the quotient is rounded first, then the product, then the sum, each field component by itself.  The kernels of
+    stg_solve_wave use exactly this arithmetic, so the object gives the reference's solvers (as `current_func` /
+    `field_func`) the same drive the GPU integrates.  A scalar table returns a float, a field table a new ndarray [3]."""
+
+    def __init__(self, times, values):
+        t = np.asarray(times, dtype=np.float64)
+        v = np.asarray(values, dtype=np.float64)
+        if t.ndim != 1 or not 2 <= t.shape[0] <= MAX_KNOTS:
+            raise ValueError(f"a waveform has 2 ... {MAX_KNOTS} knots, got times of shape {t.shape}")
+        if v.shape not in ((t.shape[0],), (t.shape[0], 3)):
+            raise ValueError(f"values must have shape [K] or [K,3] with K = {t.shape[0]}, got {v.shape}")
+        if not (np.isfinite(t).all() and np.isfinite(v).all()):
+            raise ValueError("knot times and values must be finite")
+        if not (np.diff(t) > 0).all():
+            raise ValueError("knot times must be strictly increasing")
+        self.times, self.values = t, v
+        self.vector = v.ndim == 2
+        self._t = [float(x) for x in t]
+        self._v = [[float(x) for x in row] for row in (v if self.vector else v[:, None])]
+
+    def __call__(self, t):
+        t = float(t)
+        tk, vk = self._t, self._v
+        if t <= tk[0]:
+            out = list(vk[0])
+        elif t >= tk[-1]:
+            out = list(vk[-1])
+        else:
+            k = 0
+            while tk[k + 1] <= t:
+                k += 1
+            out = [a + (t - tk[k]) * ((b - a) / (tk[k + 1] - tk[k])) for a, b in zip(vk[k], vk[k + 1])]
+        return np.array(out) if self.vector else out[0]
+
+    def knots(self):
+        """(times [K], values [K] or [K,3]) as `solve_batch` takes them."""
+        return self.times, self.values
+
+
+def _knot_tables(knots, n: int, width: int, what: str):
+    """`(times, values)` of `solve_batch` -> (times [K,n], values [K,n] (width 1) or [K,3,n]) as the C-ABI lays them out.
+    times [K] / values [K] or [K,3] are broadcast to all n problems; [K,n] / [K,n] or [K,n,3] are per problem.  Shapes and
+    the knot count are checked here; the table CONTENTS (finite, strictly increasing) are checked per problem on the device."""
+    if knots is None:
+        return None
+    try:
+        times, values = knots
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a pair (times, values)") from None
+    t = np.asarray(times, dtype=np.float64)
+    v = np.asarray(values, dtype=np.float64)
+    if t.ndim not in (1, 2) or (t.ndim == 2 and t.shape[1] != n):
+        raise ValueError(f"{what}: times must have shape [K] or [K,{n}], got {t.shape}")
+    k = t.shape[0]
+    if not 2 <= k <= MAX_KNOTS:
+        raise ValueError(f"{what}: a waveform has 2 ... {MAX_KNOTS} knots, got {k}")
+    tail = () if width == 1 else (3,)
+    if v.shape == (k,) + tail:
+        v = np.broadcast_to(v[:, None] if width == 1 else v[:, None, :], (k, n) + tail)
+    elif v.shape != (k, n) + tail:
+        raise ValueError(f"{what}: values must have shape {(k,) + tail} or {(k, n) + tail}, got {v.shape}")
+    if t.ndim == 1:
+        t = np.broadcast_to(t[:, None], (k, n))
+    if width == 3:
+        v = np.transpose(v, (0, 2, 1))
+    return np.array(t, order="C"), np.array(v, order="C")          # (copies: the broadcast views are read-only)
+
+
 def _pulse_from_callable(current_func: Optional[Callable], t0: float, t1: float) -> float:
     """Recovers J from a rectangular-pulse current function; refuses anything else."""
     if current_func is None:
@@ -57,7 +146,8 @@ def _pulse_from_callable(current_func: Optional[Callable], t0: float, t1: float)
     span = t1 - t0
     probes = [t0 + f * span for f in (0.0, 0.25, 0.5, 0.75, 1.0)]
     if any(float(current_func(t)) != j0 for t in probes):
-        raise NotImplementedError("the GPU solver integrates rectangular pulses (constant J over the time span); "
+        raise NotImplementedError("the GPU solver integrates rectangular pulses (constant J over the time span) and "
+                                  "physics.PiecewiseLinear waveforms; describe the current as a PiecewiseLinear table, or "
                                   "use the reference CPU solver for arbitrary current_func callables")
     return j0
 
@@ -67,8 +157,9 @@ def _check_zero_field(field_func: Optional[Callable], t0: float, t1: float) -> N
         return
     for t in (t0, 0.5 * (t0 + t1), t1):
         if np.any(np.asarray(field_func(t), dtype=float) != 0.0):
-            raise NotImplementedError("an applied field is not part of the SpinTorque-v0 step path "
-                                      "(spin_torque_env.py:446-447 passes zeros); use the reference CPU solver")
+            raise NotImplementedError("an applied field must be given as a physics.PiecewiseLinear table with [K,3] values "
+                                      "(a constant field is two knots); arbitrary field_func callables need the reference "
+                                      "CPU solver")
 
 
 class _GpuSolverBase:
@@ -93,16 +184,31 @@ class _GpuSolverBase:
 
     def solve_batch(self, m_initial, current, duration, device_params: Dict[str, Any], thermal_noise: bool = False,
                     temperature: float = 300.0, device_type: str = "stt_mram", return_trajectory: int = 0,
-                    env_step: int = 0) -> Dict[str, Any]:
-        """N independent solves.  m_initial [N,3]; current, duration [N] (rectangular pulses over (0, duration)).
+                    env_step: int = 0, current_knots=None, field_knots=None) -> Dict[str, Any]:
+        """N independent solves over (0, duration).  m_initial [N,3]; current, duration [N].
+        Without knots: rectangular pulses `current` while t <= duration, zero applied field.
+        current_knots = (tk, jk): piecewise-linear current_func(t) (`current` is then unused and may be None); field_knots =
+        (tk, hk): piecewise-linear field_func(t) in A/m.  tk [K] with jk [K] / hk [K,3] is one table for all problems, tk [K,N]
+        with jk [K,N] / hk [K,N,3] one per problem; 2 <= K <= 32, semantics as PiecewiseLinear.  A problem whose table is not
+        finite or not strictly increasing fails (success False, m_final = m0).
         return_trajectory = K > 0 additionally returns the first K accepted points ('t' [K,N], 'm' [K,N,3])."""
         m0 = torch.as_tensor(np.asarray(m_initial, dtype=np.float64) if not torch.is_tensor(m_initial) else m_initial)
         n = m0.shape[0]
+        wave = None
+        if current_knots is not None or field_knots is not None:
+            wave = {"current": _knot_tables(current_knots, n, 1, "current_knots"),
+                    "field": _knot_tables(field_knots, n, 3, "field_knots")}
+            wave = {k: None if v is None else tuple(torch.from_numpy(a) for a in v) for k, v in wave.items()}
+        if current is None:
+            if current_knots is None:
+                raise ValueError("current is required without current_knots")
+            current = np.zeros(n)
         b = self._backend(n, device_params, device_type, thermal_noise, temperature)
         try:
             out = b.solve(m0.t().contiguous(), torch.as_tensor(current, dtype=torch.float64),
                           torch.as_tensor(duration, dtype=torch.float64), env_step=env_step,
-                          traj_cap=int(return_trajectory), want_energy=self._solver_name == "rk45")
+                          traj_cap=int(return_trajectory), want_energy=self._solver_name == "rk45",
+                          **({} if wave is None else {"wave": wave}))      # (a backend without waveforms is never asked for them)
             res = {"m_final": out["m_final"].t().cpu().numpy(), "success": out["success"].cpu().numpy().astype(bool),
                    "n_points": out["n_points"].cpu().numpy()}
             if return_trajectory:
@@ -122,10 +228,22 @@ class _GpuSolverBase:
         t0, t1 = float(t_span[0]), float(t_span[1])
         if t0 != 0.0:
             raise NotImplementedError("time spans start at 0 on the step path (spin_torque_env.py:453)")
-        J = _pulse_from_callable(current_func, t0, t1)
-        _check_zero_field(field_func, t0, t1)
+        J, current_knots, field_knots = 0.0, None, None
+        if isinstance(current_func, PiecewiseLinear):
+            if current_func.vector:
+                raise ValueError("current_func must be a scalar PiecewiseLinear (values [K])")
+            current_knots = current_func.knots()
+        else:
+            J = _pulse_from_callable(current_func, t0, t1)
+        if isinstance(field_func, PiecewiseLinear):
+            if not field_func.vector:
+                raise ValueError("field_func must be a vector PiecewiseLinear (values [K,3])")
+            field_knots = field_func.knots()
+        else:
+            _check_zero_field(field_func, t0, t1)
         r = self.solve_batch(np.asarray(m_initial, dtype=np.float64)[None, :], [J], [t1], device_params,
-                             thermal_noise, temperature, return_trajectory=traj_cap)
+                             thermal_noise, temperature, return_trajectory=traj_cap, current_knots=current_knots,
+                             field_knots=field_knots)
         k = int(r["n_points"][0]) + 1
         return r, k
 
@@ -223,9 +341,11 @@ class LLGSSolver(_GpuSolverBase):
         return {"t": t, "m": m, "energy": r["energy"][:k, 0], "torques": r["torques"][:k, 0], "success": bool(r["success"][0])}
 
     def find_stable_states(self, device_params: Dict[str, Any], n_trials: int = 100, threshold: float = 1e-6,
-                           relax_time: float = 10e-9, seed: Optional[int] = None, initial_states=None) -> np.ndarray:
+                           relax_time: float = 10e-9, seed: Optional[int] = None, initial_states=None,
+                           applied_field=None) -> np.ndarray:
         """llgs_solver.py:264-305 as ONE batched relaxation of the n_trials random initial states (J = 0, no field, thermal
-        off, 10 ns).  The reference draws each trial's state from the GLOBAL legacy generator -- `np.random.normal(0, 1, 3)`
+        off, 10 ns).  applied_field: a constant bias field [3] in A/m during the relaxation (a two-knot table; the reference
+        method has no such argument).  The reference draws each trial's state from the GLOBAL legacy generator -- `np.random.normal(0, 1, 3)`
         per trial (llgs_solver.py:275-276) -- so does this method when `seed` is None: after `np.random.seed(s)` both give
         the same initial states, hence (within the solver tolerance) the same de-duplicated list, in the same order.
         `seed` draws from a private `RandomState(seed)` instead (same stream as `np.random.seed(seed)`, global state
@@ -237,7 +357,12 @@ class LLGSSolver(_GpuSolverBase):
             m0 = np.array([gen.normal(0, 1, 3) for _ in range(n_trials)], dtype=np.float64).reshape(-1, 3)
         m0 = m0 / np.linalg.norm(m0, axis=1, keepdims=True)
         n = len(m0)
-        r = self.solve_batch(m0, np.zeros(n), np.full(n, relax_time), device_params, thermal_noise=False)
+        field_knots = None
+        if applied_field is not None:
+            h = np.asarray(applied_field, dtype=np.float64).reshape(3)
+            field_knots = (np.array([0.0, relax_time if relax_time > 0 else 1.0]), np.stack([h, h]))
+        r = self.solve_batch(m0, np.zeros(n), np.full(n, relax_time), device_params, thermal_noise=False,
+                             field_knots=field_knots)
         states = []
         for mf, ok in zip(r["m_final"], r["success"]):          # llgs_solver.py:290-300: first-come de-duplication
             if ok and all(np.linalg.norm(mf - s) >= threshold for s in states):
