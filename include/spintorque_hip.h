@@ -352,6 +352,44 @@ int stg_solve_wave(stg_ctx* ctx, const double* m0, const double* J, const double
                    double* t, double* m, double* energy, double* torques, double* m_final, int32_t* n_points, uint8_t* success,
                    void* stream);
 
+/* SpinTorqueEnv.step for all N envs with the drive of stg_solve_wave: current_func(t) and field_func(t) as piecewise-linear tables
+ * in place of the rectangular pulse in zero field of stg_step (spin_torque_env.py:442-447).
+ *
+ * Actions are parsed exactly as in stg_step (safety clamp, NaN/Inf -> (0, 1e-12), clips to cfg.max_current / cfg.max_duration).  The
+ * parsed T[i] is the integration span (0, T[i]); the parsed J[i] and T[i] fill obs[10], obs[11] and the last-action fields as in
+ * stg_step.  With kj > 0 the parsed J is not the drive.
+ * Tables: layout, value rule, knot limits and validity are those of stg_solve_wave above (env index fastest: tj, jk double[kj][N];
+ * th double[kh][N]; hk double[kh][3][N]; times absolute, in seconds, t = 0 at the start of this pulse; no built-in t <= T gate).
+ *   kj = 0: the rectangular J[i] while t <= T[i] (tj, jk unused);  kh = 0: zero field (th, hk unused).
+ *   kj = kh = 0 is stg_step: the kernel then runs stg_step's own integrator and every output, the state and the counters equal
+ *   stg_step's bit for bit (thermal field included: the Philox key is (cfg.seed, env_id0 + i, stream position), as there).
+ * A knot count of 1 or above STG_MAX_KNOTS (or negative) or a missing pointer returns STG_E_INVALID with nothing launched.  Table
+ * CONTENTS are checked on the device: an env whose table is not strictly increasing or not finite takes the failed-solve path --
+ * STG_STATUS_NOOP, m unchanged, energy 0 -- and the step still counts (step count, stream position, counters); other envs are not
+ * affected.
+ * Energy of the pulse (info['energy_consumed']; with R = the resistance of m before the step, A = the area):
+ *   kj = 0: stg_step's (J R A)^2 / R * T  (0 when |J| <= 1e-12);
+ *   kj > 0: E = ((R A) * (R A)) / R * I,  I = the integral of j(t)^2 over [0, T], in closed form per env, in knot order, IEEE fp64
+ *           without FMA contraction, starting from I = 0:
+ *             if tk[0] > 0:      I = min(tk[0], T) * (vk[0] * vk[0])
+ *             for k = 0 ... K-2, with a = max(tk[k], 0), b = min(tk[k+1], T), if b > a:
+ *                 s  = (vk[k+1] - vk[k]) / (tk[k+1] - tk[k])
+ *                 ja = vk[k]   if a == tk[k]   else vk[k] + (a - tk[k]) * s          (the table's values at a and at b)
+ *                 jb = vk[k+1] if b == tk[k+1] else vk[k] + (b - tk[k]) * s
+ *                 I  = I + ((b - a) * ((ja * ja + ja * jb) + jb * jb)) / 3
+ *             if T > tk[K-1]:    I = I + (T - max(tk[K-1], 0)) * (vk[K-1] * vk[K-1])
+ * Outputs, cfg.out_layout (SoA and records), autoreset with final_obs, cfg.skip_done, the status values and the counters: as
+ * stg_step_many with K = 1.  All three solvers, with and without the thermal field (cfg.noise_model = 1 for the fixed-step solvers
+ * included), class tables (stg_set_params with cls).
+ * Limits, each a checked error with nothing launched: per-env parameter records (stg_set_params_per_env) -> STG_E_STATE;
+ * cfg.torque_model = 1 -> STG_E_INVALID.
+ * One kernel, one env per lane in env order (no lane sort, no wave specialisation, no refill).  Enqueues that kernel only: no
+ * synchronisation, no allocation, none of the context's launch scratch (the on-device counters take atomics) -- the call can be
+ * captured in a graph.  stg_get_placement does not see these launches. */
+int stg_step_wave(stg_ctx* ctx, const void* actions, int32_t act_f64, int32_t autoreset, int32_t kj, const double* tj,
+                  const double* jk, int32_t kh, const double* th, const double* hk, float* obs, float* final_obs, float* reward,
+                  double* reward_f64, double* energy, uint8_t* terminated, uint8_t* truncated, uint8_t* status, void* stream);
+
 /* ---- device-class formulas (opt-in torque model) ------------------------------------------- */
 
 /* Evaluates, per env, the device-class formulas the torque model uses: for SOT classes tau_dl, tau_fl of

@@ -737,6 +737,37 @@ int stg_step_ids(stg_ctx* ctx, int64_t M, const uint32_t* env_ids, const void* a
     return enqueue_step(ctx, a, act_f64, &ws, (hipStream_t)stream);
 }
 
+// One env step of all N envs with the drive of stg_solve_wave; its kernel lives in stg_step_wave.hip (stg_step_wave_launch).  Everything
+// arrives as arguments: one kernel, identity order, no plan kernel and none of the context's launch scratch.
+int stg_step_wave(stg_ctx* ctx, const void* actions, int32_t act_f64, int32_t autoreset, int32_t kj, const double* tj, const double* jk,
+                  int32_t kh, const double* th, const double* hk, float* obs, float* final_obs, float* reward, double* reward_f64,
+                  double* energy, uint8_t* terminated, uint8_t* truncated, uint8_t* status, void* stream) {
+    if (!ctx) return fail(STG_E_INVALID, "ctx is NULL");
+    if (!ctx->have_params || !ctx->have_state) return fail(STG_E_STATE, "stg_set_params and stg_reset must precede stg_step_wave");
+    if (ctx->per_env) return fail(STG_E_STATE, "stg_step_wave works on the class table (stg_set_params), not on per-env parameters");
+    if (ctx->cfg.torque_model == 1) return fail(STG_E_INVALID, "stg_step_wave implements the reference torque model (cfg.torque_model = 0)");
+    if (!actions || !obs) return fail(STG_E_INVALID, "actions/obs must not be NULL");
+    if (kj != 0 && (kj < 2 || kj > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kj must be 0 or 2 ... STG_MAX_KNOTS");
+    if (kh != 0 && (kh < 2 || kh > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kh must be 0 or 2 ... STG_MAX_KNOTS");
+    if (kj != 0 && (!tj || !jk)) return fail(STG_E_INVALID, "tj/jk must not be NULL with kj > 0");
+    if (kh != 0 && (!th || !hk)) return fail(STG_E_INVALID, "th/hk must not be NULL with kh > 0");
+    WaveStepArgs w{};
+    StepArgs& a = w.s;
+    if (int rc = step_outputs(ctx, a, obs, final_obs, reward, reward_f64, energy, terminated, truncated, status)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    a.s = ctx->s; a.c = cfg_view(ctx->cfg); a.N = ctx->N; a.env_id0 = ctx->env_id0;
+    a.ctab = ctx->ctab; a.cls = ctx->cls; a.ncls = ctx->ncls;
+    a.actions = actions; a.K = 1; a.out_every = 1; a.autoreset = autoreset ? 1 : 0;
+    a.counters = ctx->counters;
+    w.kj = kj; w.tj = tj; w.jk = jk; w.kh = kh; w.th = th; w.hk = hk;
+    const bool rk45 = ctx->cfg.solver == STG_SOLVER_RK45;
+    w.axis_z = (rk45 ? ctx->axis_z_llgs : ctx->axis_z) ? 1 : 0;
+    const bool thermal = rk45 ? ctx->cfg.thermal != 0 : (ctx->cfg.thermal && ctx->cfg.temperature > 0);
+    stg_step_wave_launch(w, ctx->cfg.solver, thermal, ctx->ncls > 1, act_f64, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return STG_OK;
+}
+
 extern "C++" {
 template <int SOLVER>
 static void dispatch_solve(const SolveArgs& a, bool thermal, bool multi, bool record, hipStream_t st) {

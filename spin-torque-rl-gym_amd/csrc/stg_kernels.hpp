@@ -521,10 +521,17 @@ __device__ __forceinline__ int64_t stg_hybrid_block(uint32_t b, int wave, uint32
 // ------------------------------------------------------------------------------------------------
 // m, tgt, etot, step, rng, done: the env's state before the step in, after it out (the caller stores it); so: the solve's result
 // (ignored when !lane_solves: an env that is not stepped -- skip_done, or a lane without an env).
+// WAVE (stg_step_wave_kernel only; the step kernels instantiate the default and compile to what they were,
+// profiles/step_wave_existing_kernels_unchanged.txt): the pulse need not be rectangular -- e_mode STG_PULSE_TABLE charges
+// (R A)^2 / R * e_int with e_int = the integral of j(t)^2 over [0, T] of the current table, STG_PULSE_NONE (a lane whose tables are
+// bad) charges nothing, STG_PULSE_RECT is the rectangular J of every other kernel.
+enum : int { STG_PULSE_RECT = 0, STG_PULSE_TABLE = 1, STG_PULSE_NONE = 2 };
+template <bool WAVE = false>
 __device__ __forceinline__ void env_step_tail(const StepArgs& a, int64_t i, int64_t ko, bool wr, bool live, bool lane_solves,
                                               const double* row, uint64_t env_id, V3& m, V3& tgt, double& etot, int32_t& step,
                                               uint32_t& rng, bool& done, double J, double T, const SolveOut& so,
-                                              unsigned long long& c_steps, unsigned long long& c_sub, unsigned long long& c_noop) {
+                                              unsigned long long& c_steps, unsigned long long& c_sub, unsigned long long& c_noop,
+                                              int e_mode = STG_PULSE_RECT, double e_int = 0.0) {
     // the env-step arithmetic around the solver (energy, reward, flags) has no contraction: same roundings in every
     // instantiation, and the same as NumPy's
 #pragma clang fp contract(off)
@@ -538,7 +545,14 @@ __device__ __forceinline__ void env_step_tail(const StepArgs& a, int64_t i, int6
         truncated = step >= a.c.max_steps;
     } else {
         const double prev_align = dot(m, tgt);                                   // spin_torque_env.py:338-339
-        if (fabs(J) > 1e-12) {                                                   // spin_torque_env.py:474-480
+        if (WAVE && e_mode != STG_PULSE_RECT) {
+            if (e_mode == STG_PULSE_TABLE) {
+                const V3 ref{row[C_REFX], row[C_REFY], row[C_REFZ]};
+                const double r = resistance(m, (int)row[C_DEVTYPE], row[C_RP], row[C_RAP], row[C_TMR], ref, row[C_RSERIES]);
+                const double ra = r * row[C_AREA];
+                energy = (ra * ra) / r * e_int;
+            }
+        } else if (fabs(J) > 1e-12) {                                            // spin_torque_env.py:474-480
             const V3 ref{row[C_REFX], row[C_REFY], row[C_REFZ]};
             const double r = resistance(m, (int)row[C_DEVTYPE], row[C_RP], row[C_RAP], row[C_TMR], ref, row[C_RSERIES]);
             const double v = J * r * row[C_AREA];

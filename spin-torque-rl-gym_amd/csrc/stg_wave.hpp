@@ -1,10 +1,12 @@
-// stg_wave.hpp -- piecewise-linear current and field waveforms on the solve path (stg_solve_wave, include/spintorque_hip.h).
+// stg_wave.hpp -- piecewise-linear current and field waveforms on the solve path and the env step path (stg_solve_wave, stg_step_wave,
+// include/spintorque_hip.h).
 //
 // The solvers of the reference take current_func(t) and field_func(t); a Python callable cannot run in a kernel, a table of knots can.
 // This header holds the waveform variants of the functions of stg_physics.hpp that take J as a per-solve constant (simple_solve, the
 // llgs_lane_* family); the functions in which the drive enters as an argument -- llgs_rhs, validation, the RK45 controller pieces, the
-// recorder, the normal stream -- are reused as they are.  Only stg_solve_wave.hip instantiates anything in here: the step kernels,
-// stg_solve_kernel and the array kernels do not see this file's device code (profiles/waveform_existing_kernels_unchanged.txt).
+// recorder, the normal stream -- are reused as they are.  Only stg_solve_wave.hip and stg_step_wave.hip instantiate anything in here: the
+// step kernels, stg_solve_kernel and the array kernels do not see this file's device code (profiles/waveform_existing_kernels_unchanged.txt,
+// profiles/step_wave_existing_kernels_unchanged.txt).
 //
 // Waveform semantics (the C header states them for callers; physics.PiecewiseLinear and tests/waveform_ref.py use the same arithmetic):
 //   K knots, 2 <= K <= STG_MAX_KNOTS, times tk[0] < ... < tk[K-1] finite, values vk (a scalar, or three field components).
@@ -25,6 +27,18 @@ struct WaveSolveArgs {
 
 // defined in stg_solve_wave.hip: enqueues the one kernel of a waveform solve
 void stg_wave_launch(const WaveSolveArgs& a, int solver, bool thermal, bool multi, bool record, hipStream_t st);
+
+// one env step with the same drive (stg_step_wave): the step launch's arguments plus the tables, [k][N] over the context's envs
+struct WaveStepArgs {
+    StepArgs s;
+    int32_t kj, kh;
+    const double *tj, *jk;
+    const double *th, *hk;
+    int32_t axis_z;               // which form of the rectangular solvers stg_step takes for this context (zero-table launches run it)
+};
+
+// defined in stg_step_wave.hip: enqueues the one kernel of a waveform step
+void stg_step_wave_launch(const WaveStepArgs& a, int solver, bool thermal, bool multi, int act_f64, hipStream_t st);
 
 namespace stg {
 

@@ -254,14 +254,9 @@ class HipBackend:
         self._keep = (mask, init_m, target)      # keep inputs alive until the stream has consumed them
         return self.obs
 
-    def step(self, actions, autoreset=False, out: Optional[torch.Tensor] = None):
-        """actions: [2,N] float32 or float64 tensor (row 0 current density, row 1 duration).  One kernel launch; the
-        RL-facing outputs land in `self.packed`.  autoreset (same-step): an env whose episode ends ON THIS step reports
-        this step's reward / terminated / truncated, is reset on the device inside the same launch, and its `obs` row
-        already holds the new episode's first observation; the terminal observation goes to `self.final_obs` (always, with or
-        without `diagnostics`: a learner that bootstraps at truncation needs it; rows of other envs keep their last content).
-        out ('records' layout only): another uint8 [N,56] record array to write this step's outputs into instead of
-        `self.packed` (callers that double-buffer, e.g. the pipelined multi-GPU gather); the returned views are of `out`."""
+    def _one_step(self, launch, actions, autoreset, out):
+        """What step() and step_wave() share: the actions on the device, the final_obs buffer, the destination (`out=`), the eight
+        output pointers, and the views handed back.  launch(a, f64, out_ptrs): the library call, returns its code."""
         a = torch.as_tensor(actions)
         f64 = a.dtype == torch.float64
         a = self._dev(a, torch.float64 if f64 else torch.float32, (2, self.n))
@@ -273,14 +268,52 @@ class HipBackend:
         if self.records_layout and (dst.dtype != torch.uint8 or tuple(dst.shape) != (self.n, RECORD_BYTES) or not dst.is_contiguous()
                                     or dst.device != self.device):
             raise ValueError(f"out must be a contiguous uint8 [{self.n}, {RECORD_BYTES}] tensor on {self.device}")
-        _lib.check(self.lib.stg_step_many(self._ctx, 1, _ptr(a), int(f64), 1, int(bool(autoreset)),
-                                          *self._out_ptrs(dst, self._final_buf if autoreset else None, self.reward, self.reward64,
-                                                          self.energy, self.terminated, self.truncated, self.status), self._stream()))
+        _lib.check(launch(a, int(f64), self._out_ptrs(dst, self._final_buf if autoreset else None, self.reward, self.reward64, self.energy,
+                                                      self.terminated, self.truncated, self.status)))
         self._keep = (a,)
         if out is None:
             return self.obs, self.reward, self.reward64, self.terminated, self.truncated, self.status
         obs, reward, term, trunc, st = record_views(out)
         return obs.t(), reward, self.reward64, term, trunc, (self.status if self.diagnostics else st)
+
+    def step(self, actions, autoreset=False, out: Optional[torch.Tensor] = None):
+        """actions: [2,N] float32 or float64 tensor (row 0 current density, row 1 duration).  One kernel launch; the
+        RL-facing outputs land in `self.packed`.  autoreset (same-step): an env whose episode ends ON THIS step reports
+        this step's reward / terminated / truncated, is reset on the device inside the same launch, and its `obs` row
+        already holds the new episode's first observation; the terminal observation goes to `self.final_obs` (always, with or
+        without `diagnostics`: a learner that bootstraps at truncation needs it; rows of other envs keep their last content).
+        out ('records' layout only): another uint8 [N,56] record array to write this step's outputs into instead of
+        `self.packed` (callers that double-buffer, e.g. the pipelined multi-GPU gather); the returned views are of `out`."""
+        return self._one_step(lambda a, f64, outs: self.lib.stg_step_many(self._ctx, 1, _ptr(a), f64, 1, int(bool(autoreset)), *outs,
+                                                                          self._stream()), actions, autoreset, out)
+
+    def _wave_tables(self, wave):
+        """wave = dict(current=(tj [K,N], jk [K,N]) | None, field=(th [K,N], hk [K,3,N]) | None) -> (kj, tj, jk, kh, th, hk) on the
+        device, as stg_solve_wave / stg_step_wave take them (a missing table: knot count 0, no pointers)."""
+        n = self.n
+        tj = jk = th = hk = None
+        kj = kh = 0
+        if wave.get("current") is not None:
+            tj, jk = wave["current"]
+            kj = int(torch.as_tensor(tj).shape[0])
+            tj, jk = self._dev(tj, torch.float64, (kj, n)), self._dev(jk, torch.float64, (kj, n))
+        if wave.get("field") is not None:
+            th, hk = wave["field"]
+            kh = int(torch.as_tensor(th).shape[0])
+            th, hk = self._dev(th, torch.float64, (kh, n)), self._dev(hk, torch.float64, (kh, 3, n))
+        return kj, tj, jk, kh, th, hk
+
+    def step_wave(self, actions, wave, autoreset=False, out: Optional[torch.Tensor] = None):
+        """step() with piecewise-linear waveforms (stg_step_wave): wave = dict(current=(tj [K,N], jk [K,N]) | None,
+        field=(th [K,N], hk [K,3,N]) | None) as solve(wave=) takes it -- times in seconds from the start of this pulse; a missing
+        current table means the rectangular parsed J, a missing field table zero field.  The parsed duration is the integration
+        span; with a current table the parsed J only fills the observation.  Everything else -- outputs, autoreset, out= -- as step()."""
+        kj, tj, jk, kh, th, hk = self._wave_tables(wave)
+        res = self._one_step(lambda a, f64, outs: self.lib.stg_step_wave(self._ctx, _ptr(a), f64, int(bool(autoreset)), kj, _ptr(tj), _ptr(jk),
+                                                                         kh, _ptr(th), _ptr(hk), *outs, self._stream()),
+                             actions, autoreset, out)
+        self._keep = self._keep + (tj, jk, th, hk)
+        return res
 
     def step_many(self, actions, out_every=True, autoreset=False):
         """actions: [K,2,N]; returns tensors with a leading K (out_every) or 1 dimension."""
@@ -426,16 +459,7 @@ class HipBackend:
             tq = torch.zeros((traj_cap, n), dtype=torch.float64, device=dev) if want_energy else None
             out.update(t=t, m=m, energy=e, torques=tq)
         if wave is not None:
-            tj = jk = th = hk = None
-            kj = kh = 0
-            if wave.get("current") is not None:
-                tj, jk = wave["current"]
-                kj = int(torch.as_tensor(tj).shape[0])
-                tj, jk = self._dev(tj, torch.float64, (kj, n)), self._dev(jk, torch.float64, (kj, n))
-            if wave.get("field") is not None:
-                th, hk = wave["field"]
-                kh = int(torch.as_tensor(th).shape[0])
-                th, hk = self._dev(th, torch.float64, (kh, n)), self._dev(hk, torch.float64, (kh, 3, n))
+            kj, tj, jk, kh, th, hk = self._wave_tables(wave)
             _lib.check(self.lib.stg_solve_wave(self._ctx, _ptr(m0), _ptr(J), _ptr(T), kj, _ptr(tj), _ptr(jk), kh, _ptr(th), _ptr(hk),
                                                int(env_step), int(traj_cap), _ptr(t), _ptr(m), _ptr(e), _ptr(tq), _ptr(mf),
                                                _ptr(npts), _ptr(succ), self._stream()))

@@ -75,6 +75,9 @@ class ShardedSpinTorqueVecEnv:
     def __init__(self, num_envs: int, group: Optional[dist.ProcessGroup] = None, device_index: Optional[int] = None,
                  class_index=None, gather_algo: str = "all_gather", inplace: bool = False, overlap: Optional[bool] = None,
                  **env_kwargs):
+        if env_kwargs.get("pulse_shape") is not None or env_kwargs.get("applied_field") is not None:
+            raise NotImplementedError("ShardedSpinTorqueVecEnv is not implemented with pulse_shape or applied_field: shaped pulses and "
+                                      "an applied field run on SpinTorqueVecEnv.step() only (stg_step_wave has no sharded variant yet)")
         if not dist.is_initialized():
             raise RuntimeError("torch.distributed must be initialised (backend 'nccl' = RCCL on ROCm, or 'gloo')")
         if gather_algo not in ("all_gather", "p2p"):

@@ -185,6 +185,60 @@ def assemble_state(pieces, lo: int, hi: int, tile: bool = True):
     return out
 
 
+# -- shaped pulses and an applied field on the step path (stg_step_wave) ------------------------------------------------------------
+_WAVE_LIMIT = ("{what} is not implemented while pulse_shape or applied_field is set: shaped pulses and an applied field run on "
+               "step() only (stg_step_wave has no fused K-step, subset, send/recv or sharded variant yet)")
+
+
+def check_pulse_shape(shape):
+    """pulse_shape= of the envs: a scalar physics.PiecewiseLinear over normalised time tau in [0, 1] (None passes)."""
+    from .physics import PiecewiseLinear
+    if shape is None:
+        return None
+    if not isinstance(shape, PiecewiseLinear):
+        raise ValueError("pulse_shape must be a physics.PiecewiseLinear (times = normalised tau in [0, 1], scalar values)")
+    if shape.vector:
+        raise ValueError("pulse_shape takes scalar values [K] (a factor on the action's current density), got [K,3]")
+    if float(shape.times[0]) < 0.0 or float(shape.times[-1]) > 1.0:
+        raise ValueError("pulse_shape times are normalised: every tau must lie in [0, 1] (tau * pulse duration is the knot time)")
+    return shape
+
+
+def field_knots(applied_field, max_duration):
+    """applied_field= of the envs -> (times [K], values [K,3]) in seconds and A/m, or None.  A constant 3-vector becomes the two-knot
+    table (0, max_duration) -- the last value holds beyond it --; a physics.PiecewiseLinear with [K,3] values is taken as it is."""
+    from .physics import PiecewiseLinear
+    if applied_field is None:
+        return None
+    if isinstance(applied_field, PiecewiseLinear):
+        if not applied_field.vector:
+            raise ValueError("applied_field as a PiecewiseLinear takes [K,3] values (A/m), got scalar values")
+        return applied_field.times.copy(), applied_field.values.copy()
+    h = np.asarray(applied_field, dtype=np.float64)
+    if h.shape != (3,) or not np.isfinite(h).all():
+        raise ValueError("applied_field must be a finite 3-vector in A/m or a physics.PiecewiseLinear with [K,3] values")
+    return np.array([0.0, float(max_duration) if max_duration > 0 else 1.0]), np.stack([h, h])
+
+
+def parse_actions_fp64(a: torch.Tensor, max_current: float, max_duration: float):
+    """The kernels' action parse restated in torch, for actions [2,N] float32 or float64: the safety clamp in the action's own dtype
+    (current to +-1e8, duration to [1e-12, 1e-6], NaN kept), NaN / Inf in either -> (0, 1e-12), then in fp64 the clips to max_current and
+    [1e-12, max_duration].  Returns (J [N], T [N]) float64 -- the values stg_step_wave parses from the same actions, bit for bit."""
+    a0, a1 = a[0].clamp(-1e8, 1e8), a[1].clamp(1e-12, 1e-6)                 # (clamp keeps NaN; the bounds are rounded to a's dtype)
+    bad = torch.isnan(a0) | torch.isnan(a1) | torch.isinf(a0) | torch.isinf(a1)
+    a0 = torch.where(bad, torch.zeros_like(a0), a0)
+    a1 = torch.where(bad, torch.full_like(a1, 1e-12), a1)
+    return a0.double().clamp(-max_current, max_current), a1.double().clamp(1e-12, max_duration)
+
+
+def pulse_tables(shape, J: torch.Tensor, T: torch.Tensor):
+    """(tj [K,N], jk [K,N]) of a pulse_shape for the parsed (J [N], T [N]): knot times tau_k * T, knot values J * s_k, each ONE rounded
+    fp64 product."""
+    tau = torch.as_tensor(shape.times, dtype=torch.float64, device=T.device)
+    s = torch.as_tensor(shape.values, dtype=torch.float64, device=T.device)
+    return (tau[:, None] * T[None, :]).contiguous(), (J[None, :] * s[:, None]).contiguous()
+
+
 class SpinTorqueVecEnv:
     """N parallel SpinTorque-v0 environments on one MI355X.
 
@@ -202,6 +256,12 @@ class SpinTorqueVecEnv:
     (``info['status']`` is then the records' status byte).
     Subsets and asynchronous stepping: ``step_ids(actions, env_ids)`` steps the listed envs only (outputs compact, in list order);
     ``async_reset`` / ``recv`` / ``send`` are the EnvPool contract on top of it (in-flight batches on a small pool of streams).
+    Shaped pulses and an applied field (``step()`` only): ``pulse_shape`` -- a scalar ``physics.PiecewiseLinear`` over normalised time
+    tau in [0, 1]: with the parsed action (J, T) the current is the table of knots (tau_k T, J s_k), last value held beyond the last
+    knot -- and ``applied_field`` -- a constant 3-vector in A/m, or a ``PiecewiseLinear`` with [K,3] values in absolute seconds, the
+    same for every env, restarted at t = 0 of every pulse.  The step's energy is then (R A)^2 / R times the integral of j(t)^2 over the
+    pulse (include/spintorque_hip.h, stg_step_wave).  Class tables work; ``per_env_params`` and ``torque_model='device'`` are refused by
+    the library; ``step_many``, ``step_ids`` and ``send`` / ``recv`` raise NotImplementedError while either is set.
     """
 
     def __init__(self, num_envs: int, device_type: Union[str, Sequence[str]] = "stt_mram",
@@ -214,8 +274,13 @@ class SpinTorqueVecEnv:
                  max_attempts: int = 200_000, lane_sort: Optional[bool] = None, wave_spec: Optional[bool] = None, torque_model: str = "reference",
                  noise_model: str = "white", correlation_time: float = 1e-12,
                  per_env_params: Optional[Dict[str, Any]] = None, out_layout: str = "records",
-                 diagnostics: bool = False, lane_refill: Optional[int] = None, backend=None):
+                 diagnostics: bool = False, lane_refill: Optional[int] = None, backend=None, pulse_shape=None, applied_field=None):
         self.num_envs = int(num_envs)
+        self.pulse_shape = check_pulse_shape(pulse_shape)
+        self.applied_field = applied_field
+        self._field_knots = field_knots(applied_field, max_duration)
+        self._wave_on = self.pulse_shape is not None or self._field_knots is not None
+        self._field_tab = None                # the field table on the device, [K,N] / [K,3,N], built on the first shaped step
         factory = DeviceFactory()
         types = [device_type] if isinstance(device_type, str) else list(device_type)
         if device_params is None:
@@ -318,7 +383,11 @@ class SpinTorqueVecEnv:
         if not actions_soa:
             a = a.t()
         t0 = time.perf_counter()
-        if out is None:
+        if self._wave_on:
+            a = a.to(device=self.backend.device, dtype=torch.float64 if a.dtype == torch.float64 else torch.float32)
+            kw = {} if out is None else {"out": out}
+            obs, rew, rew64, term, trunc, status = self.backend.step_wave(a, self._wave_tables(a), autoreset=self.autoreset, **kw)
+        elif out is None:
             obs, rew, rew64, term, trunc, status = self.backend.step(a, autoreset=self.autoreset)
         else:
             obs, rew, rew64, term, trunc, status = self.backend.step(a, autoreset=self.autoreset, out=out)
@@ -336,9 +405,30 @@ class SpinTorqueVecEnv:
             info.update(reward_f64=rew64, energy=self.backend.energy)
         return obs.t(), rew, term.bool(), trunc.bool(), info
 
+    def _wave_tables(self, a):
+        """The tables of one shaped step for actions a [2,N] on the device (the `wave` of HipBackend.step_wave): a few elementwise
+        ops on [K,N].  The current table follows the parsed action; the field table is the same at every step."""
+        wave = {"current": None, "field": None}
+        if self.pulse_shape is not None:
+            J, T = parse_actions_fp64(a, self.cfg.max_current, self.cfg.max_duration)
+            wave["current"] = pulse_tables(self.pulse_shape, J, T)
+        if self._field_knots is not None:
+            if self._field_tab is None:
+                n, dev = self.num_envs, self.backend.device
+                th = torch.as_tensor(self._field_knots[0], dtype=torch.float64, device=dev)
+                hk = torch.as_tensor(self._field_knots[1], dtype=torch.float64, device=dev)
+                self._field_tab = (th[:, None].expand(-1, n).contiguous(), hk[:, :, None].expand(-1, -1, n).contiguous())
+            wave["field"] = self._field_tab
+        return wave
+
+    def _no_wave(self, what):
+        if self._wave_on:
+            raise NotImplementedError(_WAVE_LIMIT.format(what=what))
+
     def step_many(self, actions, out_every: bool = True, actions_soa: bool = False):
         """K env steps in one launch.  actions [K,N,2] (or [K,2,N] with actions_soa)."""
         self._no_pool("step_many")
+        self._no_wave("step_many")
         a = torch.as_tensor(actions)
         if not actions_soa:
             a = a.transpose(1, 2)
@@ -378,6 +468,9 @@ class SpinTorqueVecEnv:
         d["target_states"] = [[float(x) for x in t] for t in self.cfg.target_states]
         d["autoreset"] = self.autoreset
         d["device_params"] = [bytes(flatten_params(dev)).hex() for dev in self.devices]
+        if self._wave_on:                     # (only then: a plain env's dict stays what it was)
+            d["pulse_shape"] = None if self.pulse_shape is None else [self.pulse_shape.times.tolist(), self.pulse_shape.values.tolist()]
+            d["applied_field"] = None if self._field_knots is None else [x.tolist() for x in self._field_knots]
         return d
 
     def state_dict(self):
@@ -477,6 +570,7 @@ class SpinTorqueVecEnv:
         if self._needs_reset:
             raise RuntimeError("Environment must be reset before calling step_ids")
         self._no_pool("step_ids")
+        self._no_wave("step_ids")
         ids = self._check_ids(env_ids)
         a = self._ids_actions(actions, ids.size)
         if self._ids_ws is None:
@@ -491,6 +585,7 @@ class SpinTorqueVecEnv:
         """Resets every env and enters async mode (EnvPool's contract): batch k = envs [kB, (k+1)B) is then ready for recv() with its
         reset observation.  batch_size B must be even (envs 2k and 2k+1 share a 128-byte line of state and are always sent together,
         see send).  num_streams (<= 4 by default, the HIP runtime's default hardware-queue count): streams of the pool."""
+        self._no_wave("async_reset / send / recv")
         B, N = int(batch_size), self.num_envs
         if B < 2 or B % 2:
             raise ValueError("batch_size must be even (>= 2): envs 2k and 2k+1 are stepped together")
@@ -505,6 +600,7 @@ class SpinTorqueVecEnv:
         """Outputs of a completed in-flight batch, the oldest completed first (spin-polls the batches' events): (obs, reward,
         terminated, truncated, info) as step_ids returns them, info['env_id'] naming the envs.  The tensors stay valid until those ids are
         sent again."""
+        self._no_wave("recv")
         if self._pool is None:
             raise RuntimeError("recv: not in async mode (call async_reset first)")
         return self._pool.recv()
@@ -514,6 +610,7 @@ class SpinTorqueVecEnv:
         since, and be pair-closed: with env 2k or 2k+1 the set holds its partner too (the last env of an odd num_envs has none) -- the
         two share a 128-byte line of state, which two launches in flight at once must not (include/spintorque_hip.h, stg_step_ids).
         A send may merge received batches or split one along pairs."""
+        self._no_wave("send")
         if self._pool is None:
             raise RuntimeError("send: not in async mode (call async_reset first)")
         self._pool.send(actions, env_ids)
@@ -618,7 +715,7 @@ class SpinTorqueEnv(_EnvBase):
                  reward_components: Optional[Dict[str, Dict]] = None, action_mode: str = "continuous",
                  observation_mode: str = "vector", success_threshold: float = 0.9, energy_penalty_weight: float = 0.1,
                  render_mode: Optional[str] = None, seed: Optional[int] = None, solver: str = "rk4",
-                 device_index: int = 0, backend=None):
+                 device_index: int = 0, backend=None, pulse_shape=None, applied_field=None):
         if reward_components is not None:
             raise NotImplementedError("custom reward callables are arbitrary Python and stay on the reference "
                                       "(SURVEY.md section 2); the GPU path implements the default 4-component reward")
@@ -637,7 +734,8 @@ class SpinTorqueEnv(_EnvBase):
         self._vec = SpinTorqueVecEnv(1, device_type, device_params, None, target_states, max_steps, max_current,
                                      max_duration, temperature, include_thermal_fluctuations, success_threshold,
                                      energy_penalty_weight, solver, seed, False, False,
-                                     device_index, 0, diagnostics=True, backend=backend)
+                                     device_index, 0, diagnostics=True, backend=backend, pulse_shape=pulse_shape,
+                                     applied_field=applied_field)
         self.device = self._vec.devices[0]
         self.target_states = self._vec.target_states
         self.solver_name = solver
@@ -778,13 +876,25 @@ class SpinTorqueEnv(_EnvBase):
         self._vec.close()
 
     # -- introspection (spin_torque_env.py:699-745) ------------------------------------------------------------
+    def _drive_info(self):
+        """pulse_shape / applied_field as plain data (empty without either)."""
+        v = self._vec
+        if not v._wave_on:
+            return {}
+        return {"pulse_shape": None if v.pulse_shape is None else {"tau": v.pulse_shape.times.tolist(), "scale": v.pulse_shape.values.tolist()},
+                "applied_field": None if v._field_knots is None else {"times": v._field_knots[0].tolist(), "values": v._field_knots[1].tolist()}}
+
     def get_device_info(self):
-        return self.device.get_device_info()
+        info = self.device.get_device_info()
+        info.update(self._drive_info())
+        return info
 
     def get_solver_info(self):
-        return {"method": self.solver_name, "solve_count": self._solve_count, "timeout_count": 0,
+        info = {"method": self.solver_name, "solve_count": self._solve_count, "timeout_count": 0,
                 "last_solve_time": self._solve_time[0], "timeout_rate": 0.0,
                 "avg_solve_time": self._solve_time[1] / max(self._solve_count, 1), "backend": "hip/gfx950"}
+        info.update(self._drive_info())
+        return info
 
     def get_health_report(self):
         from .harness import health_report
