@@ -220,7 +220,16 @@ int stg_step(stg_ctx* ctx, const void* actions, int32_t act_f64, float* obs, flo
  * init_m/target, Philox key cfg.seed) and its obs row holds the NEW episode's first observation; final_obs
  * (float[K or 1][12][N] -- float[K or 1][N][12] with STG_OUT_RECORDS --, may be NULL) receives the terminal observation of
  * such envs (entries of other envs untouched).  With STG_OUT_RECORDS the record array and final_obs must be 8-byte
- * aligned (the kernel stores float pairs); a misaligned pointer is rejected with STG_E_INVALID. */
+ * aligned (the kernel stores float pairs); a misaligned pointer is rejected with STG_E_INVALID.
+ * Graph capture.  stg_step, stg_step_many and stg_step_wave enqueue only kernels and memsets on `stream` (as it stands only kernels;
+ * no host synchronisation, no allocation, and nothing that the host counts from launch to launch: the RK45 lane-refill kernel puts
+ * the cursors of its queue back to zero itself when its last wavefront retires), so a call may be captured in a graph and replayed
+ * any number of times, also interleaved with eager calls on the same context: a replay gives the bits of the eager call.  Launches
+ * of one context must be ordered (one stream, or streams ordered by events): they share the context's lane schedule and refill
+ * cursors.  A captured launch bakes in
+ *   - the static buffers: the action, table and output pointers of the call, and the context's state and scratch;
+ *   - the slot of the placement ring it was given at capture: a replay overwrites that slot, and stg_get_placement's launches_back
+ *     counts host calls, not replays. */
 int stg_step_many(stg_ctx* ctx, int32_t K, const void* actions, int32_t act_f64, int32_t out_every, int32_t autoreset,
                   float* obs, float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated,
                   uint8_t* truncated, uint8_t* status, void* stream);

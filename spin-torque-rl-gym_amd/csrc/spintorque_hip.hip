@@ -361,8 +361,8 @@ struct stg_ctx {
     int32_t ncls = 0;
     const uint8_t* cls = nullptr;     // caller-owned device pointer
     unsigned long long* counters = nullptr;
-    unsigned long long* refill_cursor = nullptr;   // the refill launches' two alternating sets of stripe cursors (each cursor in a 128-byte line of its own)
-    uint64_t refill_seq = 0;                       // refill launches so far: launch k uses cursor k & 1 and zeroes the other
+    unsigned long long* refill_cursor = nullptr;   // the full step's refill launches: stripe cursors, then retire counters (each in a 128-byte line of its own);
+                                                   // all 0 between launches (stg_kernels.hpp: refill_retire)
     uint32_t* placement = nullptr;    // [PLACEMENT_RING][PLACEMENT_WORDS]: where the wavefronts of the last launches ran (stg_get_placement)
     uint64_t launch_seq = 0;          // step launches so far
     uint32_t* perm = nullptr;
@@ -606,12 +606,12 @@ int stg_reset(stg_ctx* ctx, const uint8_t* mask, const double* init_m, const dou
 }
 
 // stg_step_ids's workspace (caller-owned, one per launch in flight): slot -> list position, the slot-order actions, the refill launch's
-// cursor set (zeroed on the launch's stream) and the set a refill kernel zeroes for the context's next launch (unused here).  The offsets
-// grow with M, so a workspace sized for M serves every smaller list.
+// cursor set and, in a second block of the same size, its retire counters (both zeroed on the launch's stream).  The offsets grow with
+// M, so a workspace sized for M serves every smaller list.
 struct IdsWorkspace {
     uint32_t* perm;
     void* act_sorted;
-    unsigned long long *cursor, *cursor_next;
+    unsigned long long *cursor, *done;
     size_t cursor_bytes, bytes;
 };
 static IdsWorkspace ids_workspace(void* base, int64_t M) {
@@ -623,7 +623,7 @@ static IdsWorkspace ids_workspace(void* base, int64_t M) {
     w.perm = (uint32_t*)p;
     w.act_sorted = (void*)(p + rp);
     w.cursor = (unsigned long long*)(p + rp + ra);
-    w.cursor_next = (unsigned long long*)(p + rp + ra + w.cursor_bytes);
+    w.done = (unsigned long long*)(p + rp + ra + w.cursor_bytes);
     w.bytes = rp + ra + 2 * w.cursor_bytes;
     return w;
 }
@@ -669,18 +669,16 @@ static int enqueue_step(stg_ctx* ctx, StepArgs& a, int32_t act_f64, const IdsWor
     a.hybrid = p.hybrid;
     a.refill = p.refill; a.refill_check = p.refill_check; a.refill_nw = p.refill_nw;
     if (p.refill) {
+        // Every refill launch leaves its cursors and retire counters at 0 (refill_retire), so the full step, whose launches are ordered,
+        // finds the context's own set at 0 -- zeroed by stg_create, then by each launch -- and bakes nothing but two pointers into a captured
+        // launch.  An id launch has its set in the caller's workspace, whose content is the caller's: zeroed on the launch's stream.
         if (ws) {
-            // the launch's own cursors, zeroed on its stream (no context-owned cursor: launches on other streams may overlap, and a captured
-            // graph replays the memset with the kernel)
-            HIP_TRY(hipMemsetAsync(ws->cursor, 0, ws->cursor_bytes, st));
+            HIP_TRY(hipMemsetAsync(ws->cursor, 0, 2 * ws->cursor_bytes, st));
             a.refill_cursor = ws->cursor;
-            a.refill_cursor_next = ws->cursor_next;
+            a.refill_done = ws->done;
         } else {
-            // two cursors alternate: this launch finds its own at 0 (zeroed by the previous refill launch, or by stg_create) and
-            // zeroes the next one's -- launches of a context are ordered on their stream
-            a.refill_cursor = ctx->refill_cursor + (ctx->refill_seq & 1) * (REFILL_STRIPES * REFILL_CURSOR_STRIDE);
-            a.refill_cursor_next = ctx->refill_cursor + ((ctx->refill_seq + 1) & 1) * (REFILL_STRIPES * REFILL_CURSOR_STRIDE);
-            ctx->refill_seq += 1;
+            a.refill_cursor = ctx->refill_cursor;
+            a.refill_done = ctx->refill_cursor + REFILL_STRIPES * REFILL_CURSOR_STRIDE;
         }
         stg_dispatch_step_rk45_refill(a, p.thermal, p.multi != 0, ctx->axis_z_llgs, act_f64, st);
     } else {

@@ -78,8 +78,8 @@ struct StepArgs {
     int32_t records;              // STG_OUT_RECORDS: `obs` is the record array [K or 1][N][STG_RECORD_BYTES], reward/term/trunc unused
     int32_t refill, refill_check; // lane-refill launch (stg_step_refill_kernel): != 0 selects it; attempts between refill points
     int32_t refill_nw;            // ... and its number of (persistent) wavefronts
-    unsigned long long* refill_cursor;   // ... the cursors of its global queue's stripes (all 0 when the launch starts)
-    unsigned long long* refill_cursor_next;   // ... and the cursors of the NEXT refill launch, which this launch zeroes (two sets alternate)
+    unsigned long long* refill_cursor;   // ... the cursors of its global queue's stripes: all 0 when the launch starts, and all 0 again when it ends
+    unsigned long long* refill_done;     // ... and its retire counters (refill_retire), likewise
     int32_t hybrid;               // wave-specialised launch of 1024 workgroups over more than 1024 blocks: number of producer/consumer pairs + 1
                                   // (the other workgroups integrate two blocks with the normals inline); 0: every workgroup is a pair.
                                   // See stg_hybrid_block
@@ -617,6 +617,35 @@ __device__ __forceinline__ void env_step_tail(const StepArgs& a, int64_t i, int6
 constexpr int REFILL_STRIPES = 64;            // interleaved stripes of the refill queue, one cursor each
 constexpr int REFILL_CURSOR_STRIDE = 16;      // u64 between two cursors (a 128-byte line each)
 
+constexpr int REFILL_DONE_TOP = 8;            // the top retire counter: the other half of stripe 0's line of refill_done
+
+// The retire ticket of a refill launch.  A launch leaves its cursors as it found them -- all 0 -- so the next launch on the same set needs
+// nothing from the host and nothing in front of its kernel: a captured launch is replayed as it is, any number of times, between eager
+// launches or not.  Wavefront w of the nw counts itself off in stripe w % REFILL_STRIPES (a counter in a line of its own: nw / 64 atomics
+// on one address, not nw); the wavefront that completes its stripe counts the stripe off in the top counter; the one that completes the
+// last stripe -- every wavefront of the launch has made its last cursor access by then -- zeroes the cursors and the counters.  All of it
+// with RELAXED agent-scope atomics, as every other access to the cursors: they are performed at one place, the wavefront has the
+// results of all its cursor atomics in registers before it leaves its loop (the loop's exit depends on them), and nothing else is
+// published through the counters -- a release here would write the L2 back once per wavefront (measured: the 1 048 576-env short-pulse
+// launch 0.107 -> 0.162 ms).
+__device__ __forceinline__ void refill_retire(const StepArgs& a, int64_t w, int64_t nw, int lane) {
+    static_assert(REFILL_STRIPES == 64, "one lane per stripe when the last wavefront zeroes the cursors");
+    bool last = false;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");          // (for the compiler: the counters come after the loop's cursor accesses)
+    if (lane == 0) {
+        const int s = (int)(w % REFILL_STRIPES);
+        const unsigned long long members = (unsigned long long)((nw - s + REFILL_STRIPES - 1) / REFILL_STRIPES);       // wavefronts of stripe s
+        if (__hip_atomic_fetch_add(a.refill_done + s * REFILL_CURSOR_STRIDE, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1ull == members) {
+            const unsigned long long stripes = (unsigned long long)(nw < REFILL_STRIPES ? nw : REFILL_STRIPES);       // stripes that have a wavefront
+            last = __hip_atomic_fetch_add(a.refill_done + REFILL_DONE_TOP, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1ull == stripes;
+        }
+    }
+    if (__ballot(last) == 0ull) return;
+    __hip_atomic_store(a.refill_cursor + lane * REFILL_CURSOR_STRIDE, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(a.refill_done + lane * REFILL_CURSOR_STRIDE, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0) __hip_atomic_store(a.refill_done + REFILL_DONE_TOP, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // The refill loop of ONE persistent wavefront (see stg_step_refill_kernel below, which is this loop for every wavefront of a launch).  The
 // queue holds the blocks [blk0, blk0 + nblk_q) of the rank-major order; this is wavefront w of the nw that share it.  (A device function
 // of its own since round 4's experiment of running it in the non-pair workgroups of the hybrid launch: profiles/EXPERIMENTS.md.)
@@ -625,8 +654,6 @@ __device__ __forceinline__ void refill_wave(const StepArgs& a, int64_t w, int64_
                                             unsigned long long& c_steps, unsigned long long& c_sub, unsigned long long& c_noop) {
     const int64_t N = a.N;
     const int64_t tiles = (N + TILE_ENVS - 1) / TILE_ENVS;
-    // (the next refill launch's cursors: nobody reads them during this launch)
-    if (w == 0 && lane < REFILL_STRIPES) a.refill_cursor_next[lane * REFILL_CURSOR_STRIDE] = 0ull;
     const AT* act = (const AT*)a.actions;
     const Recorder norec{};
     const LlgsEnergyK noek{};
@@ -983,8 +1010,8 @@ stg_step_kernel(const StepArgs a) {
 // the lane that runs it, so results are bit-identical whatever the order the entries are taken in (tested).
 //  * Queue entry p = slot p % 64 of block p / 64 of the rank-major order; entries [0, nw * 64) are the initial envs, the blocks behind
 //    them are dealt over 64 interleaved stripes with a cursor each: ONE atomic per wavefront and refill point (the wavefront's takers
-//    get consecutive entries of its current stripe; an empty stripe sends it to the next).  Two sets of cursors alternate between
-//    launches: a launch finds its own at 0 and zeroes the next one's (no memset between launches).
+//    get consecutive entries of its current stripe; an empty stripe sends it to the next).  A launch finds its cursors at 0 and
+//    its last retiring wavefront puts them back to 0 (refill_retire: no memset between launches, nothing the host counts).
 //  * A refill point -- finish the env (tail of the env-step, stores), take the next entry (state load, action, the solve's
 //    prologue: two RHS calls, initial step) -- is ~2700 instructions of lane-divergent code that the whole wavefront waits for; it
 //    is entered at most every `refill_check` attempts (lanes that finished within that window go together) or when no lane is
@@ -1007,6 +1034,7 @@ __global__ void __launch_bounds__(WGW * 64) stg_step_refill_kernel(const StepArg
     if (w >= nw) return;
     unsigned long long c_steps = 0, c_sub = 0, c_noop = 0;
     refill_wave<THERMAL, MULTI, AXIS_Z, AT, IDS>(a, w, nw, 0, nblk, lane, s_tab, c_steps, c_sub, c_noop);
+    refill_retire(a, w, nw, lane);
     record_retired(a.placement, wave, lane, c_sub);
     wave_add3(a.counters + (size_t)((blockIdx.x * WGW + wave) % COUNTER_STRIPES) * COUNTER_STRIDE, s_cnt + wave * 3, c_steps, c_sub, c_noop);
 }

@@ -615,6 +615,7 @@ def test_step_is_hip_graph_capturable(stg, layout):
         a_static = acts.clone()
         if use_graph:
             st0 = {k: v.clone() for k, v in b.get_state().items()}     # pristine state (counters at 0)
+            torch.cuda.synchronize()                              # (read before the side stream steps it)
             s = torch.cuda.Stream()
             with torch.cuda.stream(s):
                 b.step(a_static)                                  # warm-up on the side stream (loads the code objects)
@@ -623,6 +624,7 @@ def test_step_is_hip_graph_capturable(stg, layout):
                 with torch.cuda.graph(g, stream=s):
                     b.step(a_static)
             b.set_state(st0); torch.cuda.synchronize()
+            b.counters(reset=True)                                # (the warm-up launch counted)
             for _ in range(3):
                 g.replay()
         else:
@@ -632,6 +634,7 @@ def test_step_is_hip_graph_capturable(stg, layout):
         res.append((b.obs.clone(), b.get_state()["m"].clone(), b.counters()["env_steps"]))
         b.close()
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
+    assert res[0][2] == res[1][2] == 3 * n                     # every replay stepped every env (the counters are part of the pristine state)
 
 
 def test_config5_shard_size_and_ragged_batches(stg):
