@@ -16,7 +16,7 @@
  *   - per-env arrays are structure-of-arrays: component-major, env index fastest (m is [3][N], obs is [12][N]),
  *     so that lane i of a wavefront touches element i of each row (coalesced).
  *   - all work is enqueued asynchronously on `stream` (a hipStream_t passed as void*; NULL = default stream);
- *     nothing synchronises with the host except stg_create, stg_destroy and stg_set_params (stg_get_state / stg_set_state enqueue copies on `stream`).
+ *     nothing synchronises with the host except stg_create, stg_destroy, stg_set_params and stg_set_pulse_shape (stg_get_state / stg_set_state enqueue copies on `stream`).
  *   - return value 0 = success, negative = error (STG_E_*); stg_last_error() returns a thread-local message.
  *   - one context per GPU; a context is not thread-safe.  Contexts are independent (no global state).
  *   - IEEE fp64 state and arithmetic (the reference's NumPy float64); observations are rounded to fp32 last,
@@ -70,7 +70,7 @@ enum { STG_OUT_SOA = 0, STG_OUT_RECORDS = 1 };
 
 #define STG_MAX_TARGETS 8
 #define STG_MAX_CLASSES 64
-#define STG_MAX_KNOTS 32          /* knots of one piecewise-linear waveform (stg_solve_wave) */
+#define STG_MAX_KNOTS 32          /* knots of one piecewise-linear waveform (stg_solve_wave, stg_step_wave, stg_set_pulse_shape) */
 
 /* SpinTorqueEnv.__init__ keyword arguments + solver constructor arguments
  * (spin_torque_env.py:36-53,93-102; llgs_solver.py:24-31; simple_solver.py:24-31) */
@@ -398,6 +398,54 @@ int stg_solve_wave(stg_ctx* ctx, const double* m0, const double* J, const double
 int stg_step_wave(stg_ctx* ctx, const void* actions, int32_t act_f64, int32_t autoreset, int32_t kj, const double* tj,
                   const double* jk, int32_t kh, const double* th, const double* hk, float* obs, float* final_obs, float* reward,
                   double* reward_f64, double* energy, uint8_t* terminated, uint8_t* truncated, uint8_t* status, void* stream);
+
+/* The env-level drive of stg_step_shaped / stg_step_shaped_ids: ONE pulse shape and ONE field table for every env and every step of the
+ * context, in place of stg_step_wave's per-env tables.  All pointers [host]:
+ *   tau, scale double[kj]: normalised knot times in [0, 1], strictly increasing, and factors on the action's current density -- with a
+ *                          step's parsed action (J, T) the env's current table is the knots (tau_j * T, J * s_j);
+ *   th double[kh]:         knot times of the field in seconds, strictly increasing, t = 0 at the start of every pulse;
+ *   hk double[kh][3]:      field values in A/m.
+ * Each of kj and kh is 0 (absent) or 2 ... STG_MAX_KNOTS.  kj = 0: the rectangular J while t <= T; kh = 0: zero field; kj = kh = 0
+ * clears the shape (the shaped step entries then return STG_E_STATE).
+ * Checked on the host, before anything else: knot counts, missing pointers, finite values, tau strictly increasing within [0, 1], th
+ * strictly increasing.  A violation returns STG_E_INVALID and the previously set shape stays in force.
+ * The context keeps a device copy of 6 * STG_MAX_KNOTS doubles.  Synchronises as stg_set_params does (a blocking copy, after the
+ * device's work in flight): not for use during graph capture; launches captured earlier read the new shape when replayed. */
+int stg_set_pulse_shape(stg_ctx* ctx, int32_t kj, const double* tau, const double* scale, int32_t kh, const double* th,
+                        const double* hk);
+
+/* K consecutive env steps in ONE launch under the shape set by stg_set_pulse_shape, state in registers between the steps: the fused
+ * rollout of stg_step_many with the drive of stg_step_wave.
+ * Signature, shapes (actions [K][2][N], outputs with a leading [K] or [1]), out_every, autoreset / final_obs, cfg.out_layout,
+ * cfg.skip_done, alignment rules and status values are those of stg_step_many.
+ * The drive of env i at step k is the shape applied to that step's parsed action (J, T):
+ *   current table (kj > 0): knots (tau_j * T, J * s_j), each ONE rounded fp64 product (no contraction) -- what
+ *                           spin_torque_gym_amd.envs.pulse_tables builds for stg_step_wave;  kj = 0: the rectangular J while t <= T;
+ *   field table (kh > 0):   (th, hk) as set, the same for every env and step;  kh = 0: zero field.
+ * Everything else is stg_step_wave as stated above: the value rule, no built-in t <= T gate, the energy ((R A) * (R A)) / R * I with
+ * the closed-form I.  An env gets, bit for bit, what K calls of stg_step_wave with those tables give it (state, every output,
+ * counters, thermal stream).  Products of adjacent tau can tie after rounding (or J * s_j overflow): a lane whose scaled current table
+ * is not strictly increasing and finite takes stg_step_wave's bad-table path for that step only -- STG_STATUS_NOOP, m unchanged,
+ * energy 0, the step still counts.
+ * Limits, each a checked error with nothing launched: no shape set -> STG_E_STATE; per-env parameter records -> STG_E_STATE;
+ * cfg.torque_model = 1 -> STG_E_INVALID; K < 1 or a missing mandatory pointer -> STG_E_INVALID.
+ * One kernel, one env per lane in env order (no lane sort, no wave specialisation, no refill); the shape is staged in LDS, so no table
+ * is read from HBM and nothing is built on the host per step.  Enqueues that kernel only -- no synchronisation, no allocation, none of
+ * the context's launch scratch (the counters take atomics): the call can be captured in a graph.  stg_get_placement does not see these
+ * launches. */
+int stg_step_shaped(stg_ctx* ctx, int32_t K, const void* actions, int32_t act_f64, int32_t out_every, int32_t autoreset,
+                    float* obs, float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated,
+                    uint8_t* truncated, uint8_t* status, void* stream);
+
+/* stg_step_shaped with K = 1 for the M envs env_ids[0..M) only, under every rule of stg_step_ids: env_ids [dev] uint32[M], actions
+ * [2][M] in list order, compact outputs in list order; an id >= n_envs is never dereferenced and reports STG_STATUS_BAD_ID with zero
+ * outputs; every other env's state stays bit for bit as it was; duplicate ids give unspecified results for those envs.  The same
+ * concurrency contract: launches on different streams may overlap if each has its own outputs and their id sets are disjoint and
+ * pair-closed at 128-byte lines (envs 2k and 2k+1).  No workspace: the schedule is identity order, there is nothing to stage.
+ * M < 0 -> STG_E_INVALID; M = 0 launches nothing.  Limits and graph capture as stg_step_shaped. */
+int stg_step_shaped_ids(stg_ctx* ctx, int64_t M, const uint32_t* env_ids, const void* actions, int32_t act_f64, int32_t autoreset,
+                        float* obs, float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated,
+                        uint8_t* truncated, uint8_t* status, void* stream);
 
 /* ---- device-class formulas (opt-in torque model) ------------------------------------------- */
 

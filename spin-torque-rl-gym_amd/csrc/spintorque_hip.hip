@@ -375,6 +375,9 @@ struct stg_ctx {
     int32_t env_layout = ENV_LAYOUT_CORE;
     uint8_t* env_type = nullptr;      // [N]: the device kind by itself, for the plan kernel (read in env order)
     bool per_env = false;
+    // the pulse shape of stg_step_shaped (stg_set_pulse_shape): device copy in the slab, knot counts (both 0: none set)
+    double* shape = nullptr;          // [STG_SHAPE_DOUBLES]: tau, scale, th, hk
+    int32_t shape_kj = 0, shape_kh = 0;
 };
 
 static EnvParams env_params_of(const stg_ctx* ctx) {
@@ -448,7 +451,7 @@ int stg_create(stg_ctx** out, int device_id, int64_t n_envs, int64_t env_id0, co
     const size_t rp = al(sizeof(uint32_t) * PLACEMENT_RING * PLACEMENT_WORDS);
     const size_t rc = al(2 * REFILL_STRIPES * REFILL_CURSOR_STRIDE * sizeof(unsigned long long));
     const size_t total = rs + r4 + ra + rp + rc + al(sizeof(double) * STG_MAX_CLASSES * C_COUNT) +
-                         COUNTER_STRIPES * COUNTER_STRIDE * sizeof(unsigned long long);
+                         COUNTER_STRIPES * COUNTER_STRIDE * sizeof(unsigned long long) + al(sizeof(double) * STG_SHAPE_DOUBLES);
     hipError_t e = hipMalloc(&c->slab, total);
     if (e != hipSuccess) { delete c; return fail(STG_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
     e = hipMemset(c->slab, 0, total);
@@ -461,6 +464,7 @@ int stg_create(stg_ctx** out, int device_id, int64_t n_envs, int64_t env_id0, co
     c->act_sorted = (void*)p; p += ra;
     c->placement = (uint32_t*)p; p += rp;
     c->refill_cursor = (unsigned long long*)p; p += rc;
+    c->shape = (double*)p; p += al(sizeof(double) * STG_SHAPE_DOUBLES);
     *out = c;
     return STG_OK;
 }
@@ -764,6 +768,93 @@ int stg_step_wave(stg_ctx* ctx, const void* actions, int32_t act_f64, int32_t au
     stg_step_wave_launch(w, ctx->cfg.solver, thermal, ctx->ncls > 1, act_f64, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return STG_OK;
+}
+
+// The env-level drive of stg_step_shaped: everything is checked here, on the host, before the context is looked at -- a refused call
+// leaves the shape that was set in force.
+int stg_set_pulse_shape(stg_ctx* ctx, int32_t kj, const double* tau, const double* scale, int32_t kh, const double* th, const double* hk) {
+    if (kj != 0 && (kj < 2 || kj > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kj must be 0 or 2 ... STG_MAX_KNOTS");
+    if (kh != 0 && (kh < 2 || kh > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kh must be 0 or 2 ... STG_MAX_KNOTS");
+    if (kj != 0 && (!tau || !scale)) return fail(STG_E_INVALID, "tau/scale must not be NULL with kj > 0");
+    if (kh != 0 && (!th || !hk)) return fail(STG_E_INVALID, "th/hk must not be NULL with kh > 0");
+    for (int32_t j = 0; j < kj; ++j) {
+        if (!std::isfinite(tau[j]) || !std::isfinite(scale[j])) return fail(STG_E_INVALID, "tau/scale must be finite");
+        if (tau[j] < 0.0 || tau[j] > 1.0) return fail(STG_E_INVALID, "tau is normalised time: every knot must lie in [0, 1]");
+        if (j > 0 && !(tau[j] > tau[j - 1])) return fail(STG_E_INVALID, "tau must be strictly increasing");
+    }
+    for (int32_t j = 0; j < kh; ++j) {
+        if (!std::isfinite(th[j]) || !std::isfinite(hk[3 * j]) || !std::isfinite(hk[3 * j + 1]) || !std::isfinite(hk[3 * j + 2]))
+            return fail(STG_E_INVALID, "th/hk must be finite");
+        if (j > 0 && !(th[j] > th[j - 1])) return fail(STG_E_INVALID, "th must be strictly increasing");
+    }
+    if (!ctx) return fail(STG_E_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (kj != 0 || kh != 0) {
+        double h[STG_SHAPE_DOUBLES] = {};
+        for (int32_t j = 0; j < kj; ++j) { h[j] = tau[j]; h[STG_MAX_KNOTS + j] = scale[j]; }
+        for (int32_t j = 0; j < kh; ++j) {
+            h[2 * STG_MAX_KNOTS + j] = th[j];
+            for (int c = 0; c < 3; ++c) h[3 * STG_MAX_KNOTS + 3 * j + c] = hk[3 * j + c];
+        }
+        // (a launch that still reads the old shape finishes first: streams created non-blocking do not wait for the copy by themselves)
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(ctx->shape, h, sizeof(h), hipMemcpyHostToDevice));
+    }
+    ctx->shape_kj = kj; ctx->shape_kh = kh;
+    return STG_OK;
+}
+
+// what stg_step_shaped and stg_step_shaped_ids share: the checks that need no list, then the one kernel (stg_step_shaped.hip).  `a`
+// arrives with N (slots), K, out_every, autoreset, actions, ids / n_state and the outputs.  Identity order, so none of the context's
+// launch scratch is used and the placement ring is left alone.
+static int shaped_checks(const stg_ctx* ctx, const char* who) {
+    if (!ctx) return fail(STG_E_INVALID, "ctx is NULL");
+    if (!ctx->have_params || !ctx->have_state) return fail(STG_E_STATE, std::string("stg_set_params and stg_reset must precede ") + who);
+    if (ctx->per_env) return fail(STG_E_STATE, std::string(who) + " works on the class table (stg_set_params), not on per-env parameters");
+    if (ctx->cfg.torque_model == 1) return fail(STG_E_INVALID, std::string(who) + " implements the reference torque model (cfg.torque_model = 0)");
+    if (ctx->shape_kj == 0 && ctx->shape_kh == 0) return fail(STG_E_STATE, std::string("stg_set_pulse_shape must precede ") + who);
+    return STG_OK;
+}
+static int enqueue_shaped(stg_ctx* ctx, ShapedStepArgs& w, int32_t act_f64, hipStream_t st) {
+    StepArgs& a = w.s;
+    HIP_TRY(hipSetDevice(ctx->device));
+    a.s = ctx->s; a.c = cfg_view(ctx->cfg); a.env_id0 = ctx->env_id0;
+    a.ctab = ctx->ctab; a.cls = ctx->cls; a.ncls = ctx->ncls;
+    a.counters = ctx->counters;
+    w.kj = ctx->shape_kj; w.kh = ctx->shape_kh; w.shape = ctx->shape;
+    const bool rk45 = ctx->cfg.solver == STG_SOLVER_RK45;
+    const bool thermal = rk45 ? ctx->cfg.thermal != 0 : (ctx->cfg.thermal && ctx->cfg.temperature > 0);
+    stg_step_shaped_launch(w, ctx->cfg.solver, thermal, ctx->ncls > 1, act_f64, st);
+    HIP_TRY(hipGetLastError());
+    return STG_OK;
+}
+
+int stg_step_shaped(stg_ctx* ctx, int32_t K, const void* actions, int32_t act_f64, int32_t out_every, int32_t autoreset, float* obs,
+                    float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated, uint8_t* truncated,
+                    uint8_t* status, void* stream) {
+    if (int rc = shaped_checks(ctx, "stg_step_shaped")) return rc;
+    if (K < 1) return fail(STG_E_INVALID, "K must be >= 1");
+    if (!actions || !obs) return fail(STG_E_INVALID, "actions/obs must not be NULL");
+    ShapedStepArgs w{};
+    StepArgs& a = w.s;
+    if (int rc = step_outputs(ctx, a, obs, final_obs, reward, reward_f64, energy, terminated, truncated, status)) return rc;
+    a.N = ctx->N; a.actions = actions; a.K = K; a.out_every = out_every ? 1 : 0; a.autoreset = autoreset ? 1 : 0;
+    return enqueue_shaped(ctx, w, act_f64, (hipStream_t)stream);
+}
+
+int stg_step_shaped_ids(stg_ctx* ctx, int64_t M, const uint32_t* env_ids, const void* actions, int32_t act_f64, int32_t autoreset, float* obs,
+                        float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated, uint8_t* truncated,
+                        uint8_t* status, void* stream) {
+    if (int rc = shaped_checks(ctx, "stg_step_shaped_ids")) return rc;
+    if (M < 0 || M > 0xFFFFFFFFll) return fail(STG_E_INVALID, "M must be in [0, 2^32)");
+    if (!env_ids || !actions || !obs) return fail(STG_E_INVALID, "env_ids/actions/obs must not be NULL");
+    ShapedStepArgs w{};
+    StepArgs& a = w.s;
+    if (int rc = step_outputs(ctx, a, obs, final_obs, reward, reward_f64, energy, terminated, truncated, status)) return rc;
+    if (M == 0) return STG_OK;                         // an empty list: nothing to launch
+    a.N = M; a.ids = env_ids; a.n_state = ctx->N;
+    a.actions = actions; a.K = 1; a.out_every = 1; a.autoreset = autoreset ? 1 : 0;
+    return enqueue_shaped(ctx, w, act_f64, (hipStream_t)stream);
 }
 
 extern "C++" {

@@ -6,29 +6,6 @@
 // A translation unit of its own: the step kernels, stg_solve_kernel and the array kernels are compiled without it.
 #include "stg_wave.hpp"
 
-// I = the integral of j(t)^2 over [0, T] of one lane's current table, in closed form and in knot order (include/spintorque_hip.h,
-// stg_step_wave: the same formula, which tests/wave_step_ref.py restates): a head piece where the first value holds, one piece per
-// segment that overlaps [0, T], a tail piece where the last value holds.  No contraction, so NumPy gives the same bits.
-__device__ __forceinline__ double pulse_sq_integral(const Pwl<1>& c, double T) {
-#pragma clang fp contract(off)
-    double t0 = c.time_at(0), v0 = c.value_at(0, 0);
-    double I = 0.0;
-    if (t0 > 0.0) I = fmin(t0, T) * (v0 * v0);
-    for (int32_t k = 0; k + 1 < c.K; ++k) {
-        const double t1 = c.time_at(k + 1), v1 = c.value_at(k + 1, 0);
-        const double lo = fmax(t0, 0.0), hi = fmin(t1, T);
-        if (hi > lo) {
-            const double sl = (v1 - v0) / (t1 - t0);
-            const double ja = lo == t0 ? v0 : v0 + (lo - t0) * sl;
-            const double jb = hi == t1 ? v1 : v0 + (hi - t0) * sl;
-            I = I + ((hi - lo) * ((ja * ja + ja * jb) + jb * jb)) / 3.0;
-        }
-        t0 = t1; v0 = v1;
-    }
-    if (T > t0) I = I + (T - fmax(t0, 0.0)) * (v0 * v0);
-    return I;
-}
-
 template <int SOLVER, bool THERMAL, bool MULTI, typename AT>
 __global__ void __launch_bounds__(64) stg_step_wave_kernel(const WaveStepArgs w) {
     // the env-step arithmetic around the solver has no contraction, as in stg_step_kernel

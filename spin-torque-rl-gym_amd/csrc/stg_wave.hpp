@@ -4,16 +4,18 @@
 // The solvers of the reference take current_func(t) and field_func(t); a Python callable cannot run in a kernel, a table of knots can.
 // This header holds the waveform variants of the functions of stg_physics.hpp that take J as a per-solve constant (simple_solve, the
 // llgs_lane_* family); the functions in which the drive enters as an argument -- llgs_rhs, validation, the RK45 controller pieces, the
-// recorder, the normal stream -- are reused as they are.  Only stg_solve_wave.hip and stg_step_wave.hip instantiate anything in here: the
-// step kernels, stg_solve_kernel and the array kernels do not see this file's device code (profiles/waveform_existing_kernels_unchanged.txt,
-// profiles/step_wave_existing_kernels_unchanged.txt).
+// recorder, the normal stream -- are reused as they are.  Only stg_solve_wave.hip, stg_step_wave.hip and stg_step_shaped.hip instantiate
+// anything in here: the step kernels, stg_solve_kernel and the array kernels do not see this file's device code
+// (profiles/waveform_existing_kernels_unchanged.txt, profiles/step_wave_existing_kernels_unchanged.txt,
+// profiles/step_shaped_existing_kernels_unchanged.txt).
 //
 // Waveform semantics (the C header states them for callers; physics.PiecewiseLinear and tests/waveform_ref.py use the same arithmetic):
 //   K knots, 2 <= K <= STG_MAX_KNOTS, times tk[0] < ... < tk[K-1] finite, values vk (a scalar, or three field components).
 //   t <= tk[0] -> vk[0];  t >= tk[K-1] -> vk[K-1];  otherwise k = the largest index with tk[k] <= t (k <= K-2) and
 //   v = vk[k] + (t - tk[k]) * ((vk[k+1] - vk[k]) / (tk[k+1] - tk[k])):  the quotient is rounded first, then the product, then the
 //   sum; no FMA contraction.  Each field component is evaluated separately.
-// Tables are per problem and lane-coalesced: times double[K][N], values double[K][C][N].
+// Tables are per problem and lane-coalesced: times double[K][N], values double[K][C][N] (GlobalKnots) -- or, for the env-level pulse
+// shape of stg_step_shaped, one table for all lanes in LDS, scaled per lane (SharedKnots).  The solvers are templates over the source.
 #pragma once
 
 #include "stg_kernels.hpp"
@@ -40,22 +42,59 @@ struct WaveStepArgs {
 // defined in stg_step_wave.hip: enqueues the one kernel of a waveform step
 void stg_step_wave_launch(const WaveStepArgs& a, int solver, bool thermal, bool multi, int act_f64, hipStream_t st);
 
+// K env steps under the context's pulse shape (stg_step_shaped, stg_step_shaped_ids): the step launch's arguments (K, out_every, and for
+// the id form ids / n_state) plus the shape, which is the same for every env and every step
+constexpr int STG_SHAPE_DOUBLES = 6 * STG_MAX_KNOTS;      // tau, scale, th [STG_MAX_KNOTS] each, hk [STG_MAX_KNOTS][3]
+struct ShapedStepArgs {
+    StepArgs s;
+    int32_t kj, kh;               // knot counts; 0: rectangular J while t <= T / zero field (not both 0)
+    const double* shape;          // [STG_SHAPE_DOUBLES] on the device (stg_set_pulse_shape)
+};
+
+// defined in stg_step_shaped.hip: enqueues the one kernel of a shaped step launch (s.ids != nullptr: the id form)
+void stg_step_shaped_launch(const ShapedStepArgs& a, int solver, bool thermal, bool multi, int act_f64, hipStream_t st);
+
 namespace stg {
+
+// Where a table's knots come from.  GlobalKnots: this lane's column of a per-problem table in HBM (stg_solve_wave, stg_step_wave).
+// SharedKnots: ONE table for every lane, staged in LDS by the kernel (stg_step_shaped) -- with SCALED, knot time j is tk[j] * st and
+// knot value j is sv * vk[j], each one rounded product: an env-level pulse shape (tau_j, s_j) under this lane's parsed action
+// (st = T, sv = J) gives the knots (tau_j T, J s_j) that envs.pulse_tables writes into a global table, bit for bit.
+template <int C>
+struct GlobalKnots {
+    const double* tk;
+    const double* vk;
+    int64_t N, i;
+    __device__ __forceinline__ double time_at(int32_t j) const { return tk[(int64_t)j * N + i]; }
+    __device__ __forceinline__ double value_at(int32_t j, int c) const { return vk[((int64_t)j * C + c) * N + i]; }
+};
+template <int C, bool SCALED>
+struct SharedKnots {
+    const double* tk;             // [K] (LDS)
+    const double* vk;             // [K][C] (LDS)
+    double st, sv;
+    // (The index goes through an empty asm, so a knot is read where the source says so -- when a cursor opens or crosses one -- and the
+    // load is not moved or merged across the sub-step loop: an LDS load cannot fault, so the compiler is otherwise free to.  Worth 4
+    // VGPRs in the fixed-step kernels of stg_step_shaped.hip, profiles/NOTEBOOK.md, round 14.  A volatile load pins it too but loses
+    // the LDS address space: flat loads.)
+    __device__ __forceinline__ double knot(const double* p, int32_t j) const {
+        asm volatile("" : "+v"(j));
+        return p[j];
+    }
+    __device__ __forceinline__ double time_at(int32_t j) const { return SCALED ? mul_x(knot(tk, j), st) : knot(tk, j); }
+    __device__ __forceinline__ double value_at(int32_t j, int c) const { return SCALED ? mul_x(sv, knot(vk, j * C + c)) : knot(vk, j * C + c); }
+};
 
 // One lane's view of one table, with the segment cursor: k is the segment [tk[k], tk[k+1]] the last query fell into (or the first / last
 // one for a query outside the table), its two knots and its slope are held in registers.  Time only moves forward between queries of one
 // cursor (seek), so a query costs a compare unless it crosses a knot; the slope is recomputed then.
-template <int C>
-struct Pwl {
-    const double* tk;
-    const double* vk;
-    int64_t N, i;
+template <int C, class KNOTS = GlobalKnots<C>>
+struct Pwl : KNOTS {
+    using KNOTS::time_at;
+    using KNOTS::value_at;
     int32_t K, k;
     double t0, tn;                // tk[k], tk[k+1]
     double v0[C], vn[C], sl[C];   // vk[k], vk[k+1], (vk[k+1] - vk[k]) / (tk[k+1] - tk[k])
-
-    __device__ __forceinline__ double time_at(int32_t j) const { return tk[(int64_t)j * N + i]; }
-    __device__ __forceinline__ double value_at(int32_t j, int c) const { return vk[((int64_t)j * C + c) * N + i]; }
 
     // the table as the C-ABI wants it: finite, times strictly increasing
     __device__ __forceinline__ bool valid() const {
@@ -110,9 +149,10 @@ struct WaveDrive {
 
 // The drive of one solve: the two cursors, or -- no current table -- the rectangular pulse J while t <= T of stg_solve.  `has_j` and
 // `has_h` are kernel-uniform.
-struct WaveSource {
-    Pwl<1> cj;
-    Pwl<3> ch;
+template <class PJ, class PH>
+struct WaveSourceT {
+    PJ cj;
+    PH ch;
     bool has_j, has_h;
     double J, T;
     double t_evt;       // the earliest time at which one of the cursors has to move on (+inf: never again)
@@ -137,6 +177,31 @@ struct WaveSource {
         return d;
     }
 };
+using WaveSource = WaveSourceT<Pwl<1>, Pwl<3>>;      // per-problem tables in HBM
+
+// I = the integral of j(t)^2 over [0, T] of one lane's current table, in closed form and in knot order (include/spintorque_hip.h,
+// stg_step_wave: the same formula, which tests/wave_step_ref.py restates): a head piece where the first value holds, one piece per
+// segment that overlaps [0, T], a tail piece where the last value holds.  No contraction, so NumPy gives the same bits.
+template <class PJ>
+__device__ __forceinline__ double pulse_sq_integral(const PJ& c, double T) {
+#pragma clang fp contract(off)
+    double t0 = c.time_at(0), v0 = c.value_at(0, 0);
+    double I = 0.0;
+    if (t0 > 0.0) I = fmin(t0, T) * (v0 * v0);
+    for (int32_t k = 0; k + 1 < c.K; ++k) {
+        const double t1 = c.time_at(k + 1), v1 = c.value_at(k + 1, 0);
+        const double lo = fmax(t0, 0.0), hi = fmin(t1, T);
+        if (hi > lo) {
+            const double sl = (v1 - v0) / (t1 - t0);
+            const double ja = lo == t0 ? v0 : v0 + (lo - t0) * sl;
+            const double jb = hi == t1 ? v1 : v0 + (hi - t0) * sl;
+            I = I + ((hi - lo) * ((ja * ja + ja * jb) + jb * jb)) / 3.0;
+        }
+        t0 = t1; v0 = v1;
+    }
+    if (T > t0) I = I + (T - fmax(t0, 0.0)) * (v0 * v0);
+    return I;
+}
 
 // simple_rhs (general easy axis) with h_applied: G gains -g' h_applied (simple_solver.py:364-367,388), i.e. p = m x G gains
 // q = m x (-g' h_applied).  A stage whose field is exactly zero keeps p as it is (a select per lane, not a branch): q is then a signed
@@ -168,10 +233,10 @@ __device__ __forceinline__ V3 simple_rhs_wave(const V3& m, const SimpleK& k, dou
 // simple_solve with the drive evaluated per RHS call at that call's own time (simple_solver.py:290-293,324-326,364-367): stage times
 // t_i = i dt (np.linspace), t_i + dt/2, t_i + dt, in exactly those roundings.  One env per lane, normals inline, reference torque model.
 // ngeff = -gamma/(1+alpha^2).
-template <int METHOD, bool THERMAL, bool RECORD>
+template <int METHOD, bool THERMAL, bool RECORD, class WS>
 __device__ __forceinline__ SolveOut simple_solve_wave(const V3& m0, double T, const SimpleK& k, double ngeff, double pol, double msv,
                                                       bool class_valid, double temperature, double max_step, const RngKey& rk,
-                                                      const Recorder& rec, InlineNormals& ns, double inv_tau, WaveSource& src) {
+                                                      const Recorder& rec, InlineNormals& ns, double inv_tau, WS& src) {
 #pragma clang fp contract(off)
     SolveOut o{m0, 0, 0, 0, false};
     // robust_solver.py:152-190 (_validate_inputs); any failure ends in the fallback result (:140-150)
@@ -287,7 +352,8 @@ struct LlgsWaveK {
     double bJ_rect, bpJ_rect;     // the rectangular form's products, formed once as llgs_lane_begin forms them
     double mu0msv;                // mu_0 Ms V of the Zeeman energy (llgs_solver.py:250)
 };
-__device__ __forceinline__ LlgsDrive llgs_drive(WaveSource& src, const LlgsWaveK& wk, double t) {
+template <class WS>
+__device__ __forceinline__ LlgsDrive llgs_drive(WS& src, const LlgsWaveK& wk, double t) {
 #pragma clang fp contract(off)
     const WaveDrive d = src.at(t);
     LlgsDrive r;
@@ -313,8 +379,8 @@ __device__ __forceinline__ V3 llgs_fun_wave(bool has_h, const LlgsDrive& d, cons
 // llgs_lane_emit with the by-products taken at the point's own time: energy includes the Zeeman term -mu0 Ms V m.h_applied
 // (llgs_solver.py:250), torques use current(t) (llgs_solver.py:161,169-172).  `src` is the solve's own cursor pair, which stands at or
 // before L.t.
-template <bool RECORD>
-__device__ __forceinline__ void llgs_lane_emit_wave(LlgsLane& L, V3& out_m, const Recorder& rec, const LlgsEnergyK& ek, WaveSource& src,
+template <bool RECORD, class WS>
+__device__ __forceinline__ void llgs_lane_emit_wave(LlgsLane& L, V3& out_m, const Recorder& rec, const LlgsEnergyK& ek, WS& src,
                                                     const LlgsWaveK& wk) {
     const double inv = rsqrt_fast(dot(L.y, L.y));
     out_m = V3{L.y.x * inv, L.y.y * inv, L.y.z * inv};
@@ -327,10 +393,10 @@ __device__ __forceinline__ void llgs_lane_emit_wave(LlgsLane& L, V3& out_m, cons
 }
 
 // llgs_lane_begin: f(t0, y0) sees the drive at t0 = 0, select_initial_step's second call the drive at t0 + h0 (common.py:117-118)
-template <bool THERMAL, bool RECORD>
+template <bool THERMAL, bool RECORD, class WS>
 __device__ __forceinline__ void llgs_lane_begin_wave(LlgsLane& L, V3& out_m, const V3& m0, double T, const LlgsK& k, double rtol, double atol,
                                                      double max_step, const RngKey& rk, const Recorder& rec, const LlgsEnergyK& ek,
-                                                     InlineNormals& ns, WaveSource& src, const LlgsWaveK& wk) {
+                                                     InlineNormals& ns, WS& src, const LlgsWaveK& wk) {
     L.bJ = 0.0; L.bpJ = 0.0;               // (unused here: the drive is per call)
     L.m0 = m0;
     L.T = T;
@@ -353,7 +419,7 @@ __device__ __forceinline__ void llgs_lane_begin_wave(LlgsLane& L, V3& out_m, con
         h0 = fmin(h0, T);
         const V3 y1{y.x + h0 * f.x, y.y + h0 * f.y, y.z + h0 * f.z};
         // (a scratch copy of the cursors: the solve's own stay at t0 for the first attempt)
-        WaveSource probe = src;
+        WS probe = src;
         const V3 f1 = llgs_fun_wave<THERMAL, true>(src.has_h, llgs_drive(probe, wk, h0), k, y1, llgs_draw<THERMAL>(ns, k, false));
         const double d2 = rms3(V3{(f1.x - f.x) * isc.x, (f1.y - f.y) * isc.y, (f1.z - f.z) * isc.z}) * rcp_fast(h0);
         const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : fifth_root(0.01 * rcp_fast(fmax(d1, d2)));
@@ -372,10 +438,10 @@ __device__ __forceinline__ void llgs_lane_begin_wave(LlgsLane& L, V3& out_m, con
 // 4/5, 8/9, 1 and -- f_new -- t + h (rk.py:64-68).  A rejected attempt retries from the same t with a smaller h, so the solve's cursors
 // (`src`) only ever move to the attempt's START time; the stage times are looked up with a copy that scans forward from there and is
 // dropped afterwards.
-template <bool THERMAL, bool RECORD>
+template <bool THERMAL, bool RECORD, class WS>
 __device__ __forceinline__ void llgs_lane_attempt_wave(LlgsLane& L, LlgsMasks& M, V3& out_m, const LlgsK& k, const Dp5Tab& tb, double rtol,
                                                        double atol, double max_step, const Recorder& rec, const LlgsEnergyK& ek,
-                                                       InlineNormals& ns, WaveSource& src, const LlgsWaveK& wk) {
+                                                       InlineNormals& ns, WS& src, const LlgsWaveK& wk) {
     constexpr double A21 = 1.0 / 5;
     constexpr double A31 = 3.0 / 40, A32 = 9.0 / 40;
     constexpr double A41 = 44.0 / 45, A42 = -56.0 / 15, A43 = 32.0 / 9;
@@ -389,7 +455,7 @@ __device__ __forceinline__ void llgs_lane_attempt_wave(LlgsLane& L, LlgsMasks& M
     const V3 y = L.y;
     const double t = L.t;
     src.seek(t);
-    WaveSource stg_at = src;            // this attempt's forward scan
+    WS stg_at = src;                    // this attempt's forward scan
     L.attempts += active ? 1 : 0;
     const double t_new = fmin(add_x(t, L.h_abs), T);                       // rk.py:135-138
     const double h = sub_x(t_new, t);
@@ -436,10 +502,10 @@ __device__ __forceinline__ void llgs_lane_attempt_wave(LlgsLane& L, LlgsMasks& M
 }
 
 // llgs_solve with waveforms: begin / gate / attempt / finish as there, one env per lane from start to end
-template <bool THERMAL, bool RECORD>
+template <bool THERMAL, bool RECORD, class WS>
 __device__ __forceinline__ SolveOut llgs_solve_wave(const V3& m0, double T, const LlgsK& k, double rtol, double atol, double max_step,
                                                     int64_t max_attempts, const RngKey& rk, const Recorder& rec, const LlgsEnergyK& ek,
-                                                    InlineNormals& ns, WaveSource& src, const LlgsWaveK& wk) {
+                                                    InlineNormals& ns, WS& src, const LlgsWaveK& wk) {
     const Dp5Tab tb = make_dp5_tab();
     LlgsLane L;
     V3 out_m = m0;

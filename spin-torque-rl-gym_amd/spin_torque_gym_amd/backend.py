@@ -317,6 +317,35 @@ class HipBackend:
 
     def step_many(self, actions, out_every=True, autoreset=False):
         """actions: [K,2,N]; returns tensors with a leading K (out_every) or 1 dimension."""
+        return self._many(self.lib.stg_step_many, actions, out_every, autoreset)
+
+    def set_pulse_shape(self, shape, field_knots):
+        """The env-level drive of step_shaped_many / step_shaped_ids (stg_set_pulse_shape): shape = a scalar physics.PiecewiseLinear
+        over normalised time (times tau in [0, 1], values = factors on the action's current density) or None (the rectangular pulse);
+        field_knots = (times [K] in seconds, values [K,3] in A/m) or None (zero field).  Both None clears the shape.  The library copies
+        the knots; called once per context, not per step."""
+        def host(x, shape_):
+            x = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+            if x.shape != shape_:
+                raise ValueError(f"expected shape {shape_}, got {x.shape}")
+            return x
+        kj = 0 if shape is None else int(len(shape.times))
+        kh = 0 if field_knots is None else int(len(field_knots[0]))
+        tau = scale = th = hk = None
+        if kj:
+            tau, scale = host(shape.times, (kj,)), host(shape.values, (kj,))
+        if kh:
+            th, hk = host(field_knots[0], (kh,)), host(field_knots[1], (kh, 3))
+        hp = lambda x: None if x is None else C.c_void_p(x.ctypes.data)               # noqa: E731
+        _lib.check(self.lib.stg_set_pulse_shape(self._ctx, kj, hp(tau), hp(scale), kh, hp(th), hp(hk)))
+
+    def step_shaped_many(self, actions, out_every=True, autoreset=False):
+        """step_many under the shape of set_pulse_shape (stg_step_shaped): K env steps in one launch, the drive of each env at each step
+        being the shape applied to that step's parsed action.  Arguments, buffers and return values are step_many's."""
+        return self._many(self.lib.stg_step_shaped, actions, out_every, autoreset)
+
+    def _many(self, entry, actions, out_every, autoreset):
+        """What step_many and step_shaped_many share (their C-ABI entries have one signature): buffers, the call, the views."""
         a = torch.as_tensor(actions)
         f64 = a.dtype == torch.float64
         K = int(a.shape[0])
@@ -338,9 +367,8 @@ class HipBackend:
         status = torch.empty((ko, n), dtype=torch.uint8, device=dev) if diag else (record_views(rec)[4] if self.records_layout else None)
         self.energy_many = torch.empty((ko, n), dtype=torch.float64, device=dev) if diag else None
         fbuf, self.final_obs_many = alloc_final_obs((ko,), n, dev, self.cfg.out_layout) if autoreset else (None, None)
-        _lib.check(self.lib.stg_step_many(self._ctx, K, _ptr(a), int(f64), int(bool(out_every)), int(bool(autoreset)),
-                                          *self._out_ptrs(out_ptr, fbuf, reward, reward64, self.energy_many, term, trunc, status),
-                                          self._stream()))
+        _lib.check(entry(self._ctx, K, _ptr(a), int(f64), int(bool(out_every)), int(bool(autoreset)),
+                         *self._out_ptrs(out_ptr, fbuf, reward, reward64, self.energy_many, term, trunc, status), self._stream()))
         self._keep = (a,)
         return obs, reward, reward64, term, trunc, status
 
@@ -373,6 +401,15 @@ class HipBackend:
         workspace: from ids_workspace(M' >= M), or None for a new one.  stream: a torch.cuda.Stream to launch on -- it first waits for
         the current stream (which produced the inputs) and the new arrays belong to it -- or None for the current stream.  Launches
         on different streams may overlap only under the header's concurrency contract (own workspace, pair-closed disjoint id sets)."""
+        return self._ids(False, actions, env_ids, autoreset, workspace, out, stream)
+
+    def step_shaped_ids(self, actions, env_ids, autoreset=False, out=None, stream=None):
+        """step_ids under the shape of set_pulse_shape (stg_step_shaped_ids): one shaped env step of the envs env_ids only.  Arguments,
+        outputs (alloc_ids_outputs) and the stream rules are step_ids's; there is no workspace (identity order: nothing is staged)."""
+        return self._ids(True, actions, env_ids, autoreset, None, out, stream)
+
+    def _ids(self, shaped, actions, env_ids, autoreset, workspace, out, stream):
+        """What step_ids and step_shaped_ids share: inputs and outputs on the launch's stream, the call."""
         cur = torch.cuda.current_stream(self.device)
         s = cur if stream is None else stream
         if s is not cur:
@@ -386,13 +423,16 @@ class HipBackend:
             if s is not cur:
                 a.record_stream(s)
                 ids.record_stream(s)
-            ws = self.ids_workspace(m) if workspace is None else workspace
+            ws = None if shaped else (self.ids_workspace(m) if workspace is None else workspace)
             if out is None:
                 out = self.alloc_ids_outputs(m, autoreset)
-            _lib.check(self.lib.stg_step_ids(self._ctx, m, _ptr(ids), _ptr(a), int(f64), int(bool(autoreset)), _ptr(ws),
-                                             *self._out_ptrs(out["buf"], out["final_buf"] if autoreset else None, out["reward"],
-                                                             out["reward64"], out["energy"], out["terminated"], out["truncated"],
-                                                             out["status"]), C.c_void_p(s.cuda_stream)))
+            outs = self._out_ptrs(out["buf"], out["final_buf"] if autoreset else None, out["reward"], out["reward64"], out["energy"],
+                                  out["terminated"], out["truncated"], out["status"])
+            head = (self._ctx, m, _ptr(ids), _ptr(a), int(f64), int(bool(autoreset)))
+            if shaped:
+                _lib.check(self.lib.stg_step_shaped_ids(*head, *outs, C.c_void_p(s.cuda_stream)))
+            else:
+                _lib.check(self.lib.stg_step_ids(*head, _ptr(ws), *outs, C.c_void_p(s.cuda_stream)))
         out["_keep"] = (a, ids, ws)           # inputs stay alive while the launch may still read them
         return out
 

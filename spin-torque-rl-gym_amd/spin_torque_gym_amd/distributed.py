@@ -77,7 +77,8 @@ class ShardedSpinTorqueVecEnv:
                  **env_kwargs):
         if env_kwargs.get("pulse_shape") is not None or env_kwargs.get("applied_field") is not None:
             raise NotImplementedError("ShardedSpinTorqueVecEnv is not implemented with pulse_shape or applied_field: shaped pulses and "
-                                      "an applied field run on SpinTorqueVecEnv.step() only (stg_step_wave has no sharded variant yet)")
+                                      "an applied field run on SpinTorqueVecEnv (step, step_many, step_ids, send / recv); the sharded "
+                                      "env does not hand the shape to its shards yet")
         if not dist.is_initialized():
             raise RuntimeError("torch.distributed must be initialised (backend 'nccl' = RCCL on ROCm, or 'gloo')")
         if gather_algo not in ("all_gather", "p2p"):

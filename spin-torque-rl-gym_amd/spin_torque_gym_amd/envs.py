@@ -185,9 +185,10 @@ def assemble_state(pieces, lo: int, hi: int, tile: bool = True):
     return out
 
 
-# -- shaped pulses and an applied field on the step path (stg_step_wave) ------------------------------------------------------------
-_WAVE_LIMIT = ("{what} is not implemented while pulse_shape or applied_field is set: shaped pulses and an applied field run on "
-               "step() only (stg_step_wave has no fused K-step, subset, send/recv or sharded variant yet)")
+# -- shaped pulses and an applied field on the step path (stg_step_wave, stg_step_shaped) --------------------------------------------
+_WAVE_LIMIT = ("{what} is not implemented on this backend while pulse_shape or applied_field is set: step() runs them everywhere "
+               "(stg_step_wave); step_many, step_ids and async_reset / send / recv need a backend with the shaped entries "
+               "(HipBackend.step_shaped_many / step_shaped_ids: stg_step_shaped, stg_step_shaped_ids), and there is no sharded variant yet")
 
 
 def check_pulse_shape(shape):
@@ -256,12 +257,14 @@ class SpinTorqueVecEnv:
     (``info['status']`` is then the records' status byte).
     Subsets and asynchronous stepping: ``step_ids(actions, env_ids)`` steps the listed envs only (outputs compact, in list order);
     ``async_reset`` / ``recv`` / ``send`` are the EnvPool contract on top of it (in-flight batches on a small pool of streams).
-    Shaped pulses and an applied field (``step()`` only): ``pulse_shape`` -- a scalar ``physics.PiecewiseLinear`` over normalised time
+    Shaped pulses and an applied field: ``pulse_shape`` -- a scalar ``physics.PiecewiseLinear`` over normalised time
     tau in [0, 1]: with the parsed action (J, T) the current is the table of knots (tau_k T, J s_k), last value held beyond the last
     knot -- and ``applied_field`` -- a constant 3-vector in A/m, or a ``PiecewiseLinear`` with [K,3] values in absolute seconds, the
     same for every env, restarted at t = 0 of every pulse.  The step's energy is then (R A)^2 / R times the integral of j(t)^2 over the
     pulse (include/spintorque_hip.h, stg_step_wave).  Class tables work; ``per_env_params`` and ``torque_model='device'`` are refused by
-    the library; ``step_many``, ``step_ids`` and ``send`` / ``recv`` raise NotImplementedError while either is set.
+    the library.  ``step()`` runs on stg_step_wave with tables built from the actions; ``step_many``, ``step_ids`` and ``async_reset`` /
+    ``send`` / ``recv`` run on stg_step_shaped / stg_step_shaped_ids, which hold the shape on chip (handed to the backend once) and give
+    every env the bits ``step()`` gives it.  Only ``ShardedSpinTorqueVecEnv`` still refuses a shape or a field.
     """
 
     def __init__(self, num_envs: int, device_type: Union[str, Sequence[str]] = "stt_mram",
@@ -351,7 +354,14 @@ class SpinTorqueVecEnv:
                                                             self._per_env_params))
         else:
             b.set_params([flatten_params(d) for d in self.devices], self._class_index)
+        if self._wave_on and self._shaped(b):
+            b.set_pulse_shape(self.pulse_shape, self._field_knots)           # once per context: the fused / subset entries read it
         return b
+
+    @staticmethod
+    def _shaped(backend):
+        """Does the backend offer the shaped fused / subset entries?  (HipBackend does; a test seam may offer step_wave only.)"""
+        return getattr(backend, "step_shaped_many", None) is not None
 
     # -- Gymnasium VectorEnv-shaped API ---------------------------------------------------------------
     def reset(self, seed: Optional[int] = None, options: Optional[Dict[str, Any]] = None):
@@ -422,7 +432,7 @@ class SpinTorqueVecEnv:
         return wave
 
     def _no_wave(self, what):
-        if self._wave_on:
+        if self._wave_on and not self._shaped(self.backend):
             raise NotImplementedError(_WAVE_LIMIT.format(what=what))
 
     def step_many(self, actions, out_every: bool = True, actions_soa: bool = False):
@@ -433,7 +443,8 @@ class SpinTorqueVecEnv:
         if not actions_soa:
             a = a.transpose(1, 2)
         t0 = time.perf_counter()
-        obs, rew, rew64, term, trunc, status = self.backend.step_many(a, out_every=out_every, autoreset=self.autoreset)
+        launch = self.backend.step_shaped_many if self._wave_on else self.backend.step_many
+        obs, rew, rew64, term, trunc, status = launch(a, out_every=out_every, autoreset=self.autoreset)
         self.profiler.add("step_many", time.perf_counter() - t0)
         info = {} if status is None else {"status": status}
         if self.autoreset:
@@ -573,11 +584,14 @@ class SpinTorqueVecEnv:
         self._no_wave("step_ids")
         ids = self._check_ids(env_ids)
         a = self._ids_actions(actions, ids.size)
-        if self._ids_ws is None:
+        if self._ids_ws is None and not self._wave_on:
             self._ids_ws = self.backend.ids_workspace(self.num_envs)
         env_id = torch.as_tensor(ids).to(self.backend.device)
         t0 = time.perf_counter()
-        out = self.backend.step_ids(a, env_id, autoreset=self.autoreset, workspace=self._ids_ws)
+        if self._wave_on:
+            out = self.backend.step_shaped_ids(a, env_id, autoreset=self.autoreset)
+        else:
+            out = self.backend.step_ids(a, env_id, autoreset=self.autoreset, workspace=self._ids_ws)
         self.profiler.add("step_ids", time.perf_counter() - t0)
         return self._ids_result(out, env_id)
 
@@ -627,15 +641,16 @@ class SpinTorqueVecEnv:
 
 class _AsyncPool:
     """Bookkeeping of SpinTorqueVecEnv's async mode: which envs are in flight, which are received and held by the caller, and the
-    in-flight launches (oldest first) with their completion events.  Each stream has its own stg_step_ids workspace; the output arrays of
-    a launch are its own (they stay valid for as long as the caller holds them)."""
+    in-flight launches (oldest first) with their completion events.  Each stream has its own stg_step_ids workspace (none with a pulse
+    shape or an applied field: stg_step_shaped_ids stages nothing); the output arrays of a launch are its own (they stay valid for as
+    long as the caller holds them)."""
 
     def __init__(self, env, batch_size, num_streams, reset_obs):
         self.env = env
         b = env.backend
         n = env.num_envs
         self.streams = b.make_streams(num_streams)
-        self.workspaces = [b.ids_workspace(n) for _ in self.streams]
+        self.workspaces = [None if env._wave_on else b.ids_workspace(n) for _ in self.streams]
         self.next_stream = 0
         self.held = np.zeros(n, dtype=bool)           # received, not sent since
         self.inflight = []                            # [(ids host int64, event or None, result or None, outputs, env_id)], in send order
@@ -684,7 +699,10 @@ class _AsyncPool:
         self.next_stream = (k + 1) % len(self.streams)
         b = env.backend
         env_id = torch.as_tensor(ids).to(b.device)
-        out = b.step_ids(a, env_id, autoreset=env.autoreset, workspace=self.workspaces[k], stream=self.streams[k])
+        if env._wave_on:
+            out = b.step_shaped_ids(a, env_id, autoreset=env.autoreset, stream=self.streams[k])
+        else:
+            out = b.step_ids(a, env_id, autoreset=env.autoreset, workspace=self.workspaces[k], stream=self.streams[k])
         ev = b.record_event(self.streams[k])
         self.held[ids] = False
         self.inflight.append((ids, ev, None, out, env_id))
