@@ -1,5 +1,5 @@
-"""NumPy restatement of ONE env step with piecewise-linear current and field waveforms (stg_step_wave; RK4 and Euler, no thermal field,
-STT-MRAM device classes), vectorised over envs: the action parse, the solve (tests/waveform_ref.py), the energy of the pulse, the state
+"""NumPy restatement of ONE env step with piecewise-linear current and field waveforms (stg_step_wave; RK4 and Euler, the thermal field of
+tests/waveform_ref.py, STT / SOT / VCMA device classes under the reference torque model), vectorised over envs: the action parse, the solve (tests/waveform_ref.py), the energy of the pulse, the state
 update, observation, reward and flags.  Written from the definitions in include/spintorque_hip.h and the env-step arithmetic of the
 reference env (spin_torque_env.py:310-407, 474-520); tests/test_wave_step_host.py pins it against the C oracle's rectangular step (no
 tables) and against the steps the reference env itself computed under shaped pulses (tests/golden/G23_wave_step.npz).
@@ -12,7 +12,7 @@ import waveform_ref
 STATUS_OK, STATUS_NOOP, STATUS_RESET, STATUS_INACTIVE = 0, 1, 2, 3
 
 DEFAULT_CFG = dict(max_current=2e6, max_duration=5e-9, success_threshold=0.9, energy_penalty_weight=0.1, max_steps=100, temperature=300.0,
-                   max_step=1e-12, skip_done=False)
+                   max_step=1e-12, skip_done=False, gamma=2.21e5, target_states=None)
 
 
 def parse_actions(a, max_current, max_duration):
@@ -56,11 +56,21 @@ def pulse_sq_integral(tk, vk, T):
     return np.where(T > t0, I + (T - np.maximum(t0, 0.0)) * (v0 * v0), I)
 
 
-def resistance(m, p):
-    """STTMRAMDevice.compute_resistance (stt_mram.py:78-97) per row of m [N,3]"""
+def resistance(m, p, device_type="stt_mram"):
+    """compute_resistance of the device classes per row of m [N,3]: STTMRAMDevice (stt_mram.py:78-97), SOTMRAMDevice (sot_mram.py:196-228:
+    the junction plus a tenth of the heavy-metal line, floor 1 Ohm) and VCMAMRAMDevice (vcma_mram.py:236-257: floor 1 Ohm).  The SOT and
+    VCMA forms take m as it is; tests/test_wave_config_host.py pins all three against oracle.resistance."""
     r_p, r_ap = p["resistance_parallel"], p["resistance_antiparallel"]
     ref = np.asarray(p.get("reference_magnetization", [0, 0, 1]), dtype=float)
     ref = ref / np.sqrt((ref[0] * ref[0] + ref[1] * ref[1]) + ref[2] * ref[2])
+    if device_type != "stt_mram":
+        cos = (m[:, 0] * ref[0] + m[:, 1] * ref[1]) + m[:, 2] * ref[2]
+        r = r_p + (r_ap - r_p) * (1.0 - cos) / 2
+        if device_type == "sot_mram":
+            thickness = p.get("thickness", 1e-9)
+            area = p.get("area", p.get("volume", 1e-24) / thickness)
+            r = r + (p.get("heavy_metal_resistivity", 2e-7) / p.get("heavy_metal_thickness", 5e-9)) / (area * 1e-12) * 0.1
+        return np.maximum(r, 1.0)
     mn = m / np.sqrt((m[:, 0] * m[:, 0] + m[:, 1] * m[:, 1]) + m[:, 2] * m[:, 2])[:, None]
     tmr = (r_ap - r_p) / r_p
     cos = (mn[:, 0] * ref[0] + mn[:, 1] * ref[1]) + mn[:, 2] * ref[2]
@@ -79,12 +89,17 @@ def observation(m, target, r, p, cfg, step_count, total_energy, J, T):
         return np.nan_to_num(np.stack(cols, axis=1).astype(np.float32), nan=0.0, posinf=1e6, neginf=-1e6)
 
 
-def step(state, actions, params, method="rk4", current=None, field=None, cfg=None, cls=None, done=None):
+def step(state, actions, params, method="rk4", current=None, field=None, cfg=None, cls=None, done=None, dev_types=None, thermal=None):
     """One env step of N envs (autoreset off).
     state: dict(m [N,3], target [N,3], total_energy [N], step_count [N]); actions [N,2] float32 / float64;
     params: one device-parameter dict, or a list of them with cls [N] (class index per env);
     current = (tj [N,K], jk [N,K]) or None (the rectangular parsed J); field = (th [N,K], hk [N,K,3]) or None (zero field);
     done [N] bool with cfg['skip_done']: those envs are not stepped (STATUS_INACTIVE).
+    cfg: DEFAULT_CFG's keys; gamma and max_step go to the solve; target_states (a list of rows, normalised here as the env does) only
+    says which targets an env may hold: every row of state['target'] must be one of them.
+    dev_types: the device type of each class ('stt_mram' | 'sot_mram' | 'vcma_mram'; None: all STT); it selects the resistance form.
+    thermal = None or dict(oracle, seed, env_id0, rng_step [N], noise 'white' | 'ou', corr_time): the thermal field at cfg's temperature
+    on the stream (seed, env_id0 + i, rng_step[i]), strength per class from oracle.thermal_strength (waveform_ref.thermal_field).
     Returns dict(m, total_energy, step_count, obs [N,12] float32, reward [N] float64, terminated, truncated, energy, status, J, T, n_sub)."""
     cfg = dict(DEFAULT_CFG, **(cfg or {}))
     m0 = np.array(state["m"], dtype=float)
@@ -93,6 +108,11 @@ def step(state, actions, params, method="rk4", current=None, field=None, cfg=Non
     steps = np.array(state["step_count"], dtype=np.int64)
     N = len(m0)
     plist = [params] if isinstance(params, dict) else list(params)
+    dev_types = ["stt_mram"] * len(plist) if dev_types is None else list(dev_types)
+    if cfg["target_states"] is not None:
+        allowed = np.array(cfg["target_states"], dtype=float)
+        allowed = allowed / np.linalg.norm(allowed, axis=1, keepdims=True)
+        assert (np.abs(target[:, None, :] - allowed[None]).max(axis=2).min(axis=1) <= 5e-16).all(), "a target that is not in cfg['target_states']"
     cls = np.zeros(N, dtype=np.int64) if cls is None else np.asarray(cls, dtype=np.int64)
     J, T = parse_actions(actions, cfg["max_current"], cfg["max_duration"])
     ok_tab = np.ones(N, dtype=bool)
@@ -106,14 +126,18 @@ def step(state, actions, params, method="rk4", current=None, field=None, cfg=Non
         sel = np.nonzero((cls == c))[0]
         if not len(sel):
             continue
-        r_before[sel] = resistance(m0[sel], p)
+        r_before[sel] = resistance(m0[sel], p, dev_types[c])
         run = sel[ok_tab[sel] & stepped[sel]]
         if not len(run):
             continue
         cur = None if current is None else (np.asarray(current[0])[run], np.asarray(current[1])[run])
         fld = None if field is None else (np.asarray(field[0])[run], np.asarray(field[1])[run])
         res = waveform_ref.solve(m0[run], T[run], p, method, current=cur, J=J[run] if current is None else None, field=fld,
-                                 max_step=cfg["max_step"], temperature=cfg["temperature"])
+                                 max_step=cfg["max_step"], temperature=cfg["temperature"], gamma=cfg["gamma"],
+                                 thermal=None if thermal is None else waveform_ref.thermal_field(
+                                     thermal["oracle"], p, dev_types[c], cfg["gamma"], cfg["temperature"], thermal["seed"],
+                                     thermal.get("env_id0", 0) + run, np.asarray(thermal["rng_step"])[run], thermal.get("noise", "white"),
+                                     thermal.get("corr_time", 1e-12)))
         success[run], n_sub[run] = res["success"], res["n_steps"]
         mf = res["m_final"]
         mf = mf / np.sqrt((mf[:, 0] * mf[:, 0] + mf[:, 1] * mf[:, 1]) + mf[:, 2] * mf[:, 2])[:, None]      # spin_torque_env.py:461-464
@@ -144,7 +168,7 @@ def step(state, actions, params, method="rk4", current=None, field=None, cfg=Non
     for c, p in enumerate(plist):
         sel = np.nonzero(cls == c)[0]
         if len(sel):
-            obs[sel] = observation(m_new[sel], target[sel], resistance(m_new[sel], p), p, cfg, steps[sel], etot[sel], J[sel], T[sel])
+            obs[sel] = observation(m_new[sel], target[sel], resistance(m_new[sel], p, dev_types[c]), p, cfg, steps[sel], etot[sel], J[sel], T[sel])
     return dict(m=m_new, total_energy=etot, step_count=steps, obs=obs, reward=reward, terminated=is_success, truncated=truncated,
                 energy=energy, status=status, J=J, T=T, n_sub=np.where(stepped, n_sub, 0), alignment=align)
 
