@@ -16,7 +16,7 @@
  *   - per-env arrays are structure-of-arrays: component-major, env index fastest (m is [3][N], obs is [12][N]),
  *     so that lane i of a wavefront touches element i of each row (coalesced).
  *   - all work is enqueued asynchronously on `stream` (a hipStream_t passed as void*; NULL = default stream);
- *     nothing synchronises with the host except stg_create, stg_destroy, stg_set_params and stg_set_pulse_shape (stg_get_state / stg_set_state enqueue copies on `stream`).
+ *     nothing synchronises with the host except stg_create, stg_destroy, stg_set_params, stg_set_pulse_shape and stg_set_pulse_knots (stg_get_state / stg_set_state enqueue copies on `stream`).
  *   - return value 0 = success, negative = error (STG_E_*); stg_last_error() returns a thread-local message.
  *   - one context per GPU; a context is not thread-safe.  Contexts are independent (no global state).
  *   - IEEE fp64 state and arithmetic (the reference's NumPy float64); observations are rounded to fp32 last,
@@ -70,7 +70,7 @@ enum { STG_OUT_SOA = 0, STG_OUT_RECORDS = 1 };
 
 #define STG_MAX_TARGETS 8
 #define STG_MAX_CLASSES 64
-#define STG_MAX_KNOTS 32          /* knots of one piecewise-linear waveform (stg_solve_wave, stg_step_wave, stg_set_pulse_shape) */
+#define STG_MAX_KNOTS 32          /* knots of one piecewise-linear waveform (stg_solve_wave, stg_step_wave, stg_set_pulse_shape, stg_set_pulse_knots) */
 
 /* SpinTorqueEnv.__init__ keyword arguments + solver constructor arguments
  * (spin_torque_env.py:36-53,93-102; llgs_solver.py:24-31; simple_solver.py:24-31) */
@@ -446,6 +446,54 @@ int stg_step_shaped(stg_ctx* ctx, int32_t K, const void* actions, int32_t act_f6
 int stg_step_shaped_ids(stg_ctx* ctx, int64_t M, const uint32_t* env_ids, const void* actions, int32_t act_f64, int32_t autoreset,
                         float* obs, float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated,
                         uint8_t* truncated, uint8_t* status, void* stream);
+
+/* The knot times of stg_step_knots / stg_step_knots_ids: the action of those entries is [J, T, s_0 ... s_{P-1}] -- the agent chooses the
+ * pulse's knot amplitudes per env and per step; the knot times, the clamp of an amplitude and the field table are fixed here, once, for
+ * every env and every step of the context.  All pointers [host]:
+ *   tau double[P]:     normalised knot times in [0, 1], strictly increasing and finite, 2 <= P <= STG_MAX_KNOTS;
+ *   s_limit:           finite and > 0: an amplitude is clamped to [-s_limit, +s_limit];
+ *   th double[kh], hk double[kh][3]: the field table with the rules of stg_set_pulse_shape; kh is 0 (zero field) or 2 ... STG_MAX_KNOTS.
+ * P = 0 clears the knots (the knot step entries then return STG_E_STATE).
+ * Everything is checked on the host, before anything else; a violation returns STG_E_INVALID and what was set before stays in force.
+ * The context keeps a device copy of 5 * STG_MAX_KNOTS doubles and synchronises as stg_set_pulse_shape does (a blocking copy, after the
+ * device's work in flight): not for use during graph capture; launches captured earlier read the new knots when replayed.
+ * Independent of stg_set_pulse_shape: a context may hold both, and each step entry reads its own. */
+int stg_set_pulse_knots(stg_ctx* ctx, int32_t P, const double* tau, double s_limit, int32_t kh, const double* th, const double* hk);
+
+/* K consecutive env steps in ONE launch whose actions carry the pulse's knot amplitudes, state in registers between the steps.
+ * Signature, outputs (a leading [K] or [1]), out_every, autoreset / final_obs, cfg.out_layout, cfg.skip_done, alignment rules and status
+ * values are those of stg_step_shaped; actions are [dev] [K][2 + P][N], float or double (act_f64), env index fastest.
+ * Action parse, per env and per step, in this order:
+ *   1. rows 0 and 1 go through parse_action exactly as in stg_step (safety clamp, NaN/Inf -> (0, 1e-12), clips to cfg.max_current /
+ *      cfg.max_duration), giving (J, T);
+ *   2. amplitude row j is converted to fp64, then clamped  s < -s_limit ? -s_limit : (s > s_limit ? s_limit : s),  which keeps NaN
+ *      (and takes +-Inf to +-s_limit);
+ *   3. if any amplitude of the lane is NaN the whole action is void: J = 0, T = 1e-12 and every s_j = 0 -- the values stg_step gives a
+ *      NaN action;
+ *   4. the lane's current table is the knots (tau_j * T, J * s_j), each ONE rounded fp64 product without contraction.
+ * obs[10], obs[11] and the last-action fields hold the parsed (J, T) as today; the observation stays 12 floats.
+ * Everything else is stg_step_wave as stated above: the value rule, no built-in t <= T gate, the energy ((R A) * (R A)) / R * I with the
+ * closed-form I, the bad-table path for a lane whose scaled table ties or overflows (STG_STATUS_NOOP, m unchanged, energy 0, the step
+ * still counts), autoreset with final_obs, cfg.skip_done, both output layouts, the counters, the thermal stream position.
+ * Contract: an env gets, bit for bit, what K calls of stg_step_wave give it with the tables tj = tau_j * T, jk = J * s_j built from the
+ * parsed action and the field table replicated.
+ * Limits, each a checked error with nothing launched: knots not set -> STG_E_STATE; per-env parameter records -> STG_E_STATE;
+ * cfg.torque_model = 1 -> STG_E_INVALID; K < 1 or a missing mandatory pointer -> STG_E_INVALID.
+ * One kernel, one env per lane in env order; tau and the field table are staged in LDS, and so are the lane's parsed amplitudes at the top
+ * of each step (8 * 64 * P bytes of dynamic LDS per 64-env block).  Enqueues that kernel only -- no synchronisation, no allocation, none of
+ * the context's launch scratch (the counters take atomics): the call can be captured in a graph.  stg_get_placement does not see these
+ * launches. */
+int stg_step_knots(stg_ctx* ctx, int32_t K, const void* actions, int32_t act_f64, int32_t out_every, int32_t autoreset,
+                   float* obs, float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated,
+                   uint8_t* truncated, uint8_t* status, void* stream);
+
+/* stg_step_knots with K = 1 for the M envs env_ids[0..M) only, under every rule of stg_step_shaped_ids: env_ids [dev] uint32[M], actions
+ * [2 + P][M] in list order, compact outputs in list order; an id >= n_envs is never dereferenced and reports STG_STATUS_BAD_ID with zero
+ * outputs; every other env's state stays bit for bit as it was; the concurrency contract of stg_step_shaped_ids applies.
+ * M < 0 -> STG_E_INVALID; M = 0 launches nothing and returns 0.  Limits and graph capture as stg_step_knots. */
+int stg_step_knots_ids(stg_ctx* ctx, int64_t M, const uint32_t* env_ids, const void* actions, int32_t act_f64, int32_t autoreset,
+                       float* obs, float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated,
+                       uint8_t* truncated, uint8_t* status, void* stream);
 
 /* ---- device-class formulas (opt-in torque model) ------------------------------------------- */
 

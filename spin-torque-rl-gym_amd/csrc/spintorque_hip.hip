@@ -378,6 +378,10 @@ struct stg_ctx {
     // the pulse shape of stg_step_shaped (stg_set_pulse_shape): device copy in the slab, knot counts (both 0: none set)
     double* shape = nullptr;          // [STG_SHAPE_DOUBLES]: tau, scale, th, hk
     int32_t shape_kj = 0, shape_kh = 0;
+    // the knot times of stg_step_knots (stg_set_pulse_knots): device copy in the slab, knot counts (knots_P 0: none set), amplitude clamp
+    double* knots = nullptr;          // [STG_KNOTS_DOUBLES]: tau, th, hk
+    int32_t knots_P = 0, knots_kh = 0;
+    double knots_limit = 0.0;
 };
 
 static EnvParams env_params_of(const stg_ctx* ctx) {
@@ -451,7 +455,8 @@ int stg_create(stg_ctx** out, int device_id, int64_t n_envs, int64_t env_id0, co
     const size_t rp = al(sizeof(uint32_t) * PLACEMENT_RING * PLACEMENT_WORDS);
     const size_t rc = al(2 * REFILL_STRIPES * REFILL_CURSOR_STRIDE * sizeof(unsigned long long));
     const size_t total = rs + r4 + ra + rp + rc + al(sizeof(double) * STG_MAX_CLASSES * C_COUNT) +
-                         COUNTER_STRIPES * COUNTER_STRIDE * sizeof(unsigned long long) + al(sizeof(double) * STG_SHAPE_DOUBLES);
+                         COUNTER_STRIPES * COUNTER_STRIDE * sizeof(unsigned long long) + al(sizeof(double) * STG_SHAPE_DOUBLES) +
+                         al(sizeof(double) * STG_KNOTS_DOUBLES);
     hipError_t e = hipMalloc(&c->slab, total);
     if (e != hipSuccess) { delete c; return fail(STG_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
     e = hipMemset(c->slab, 0, total);
@@ -465,6 +470,7 @@ int stg_create(stg_ctx** out, int device_id, int64_t n_envs, int64_t env_id0, co
     c->placement = (uint32_t*)p; p += rp;
     c->refill_cursor = (unsigned long long*)p; p += rc;
     c->shape = (double*)p; p += al(sizeof(double) * STG_SHAPE_DOUBLES);
+    c->knots = (double*)p; p += al(sizeof(double) * STG_KNOTS_DOUBLES);
     *out = c;
     return STG_OK;
 }
@@ -855,6 +861,95 @@ int stg_step_shaped_ids(stg_ctx* ctx, int64_t M, const uint32_t* env_ids, const 
     a.N = M; a.ids = env_ids; a.n_state = ctx->N;
     a.actions = actions; a.K = 1; a.out_every = 1; a.autoreset = autoreset ? 1 : 0;
     return enqueue_shaped(ctx, w, act_f64, (hipStream_t)stream);
+}
+
+// The knot times and the field table of stg_step_knots: everything is checked here, on the host, before the context is looked at -- a
+// refused call leaves what was set in force.
+int stg_set_pulse_knots(stg_ctx* ctx, int32_t P, const double* tau, double s_limit, int32_t kh, const double* th, const double* hk) {
+    if (P != 0 && (P < 2 || P > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "P must be 0 or 2 ... STG_MAX_KNOTS");
+    if (kh != 0 && (kh < 2 || kh > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kh must be 0 or 2 ... STG_MAX_KNOTS");
+    if (P != 0 && !tau) return fail(STG_E_INVALID, "tau must not be NULL with P > 0");
+    if (P != 0 && kh != 0 && (!th || !hk)) return fail(STG_E_INVALID, "th/hk must not be NULL with kh > 0");
+    if (P != 0 && !(std::isfinite(s_limit) && s_limit > 0.0)) return fail(STG_E_INVALID, "s_limit must be finite and positive");
+    for (int32_t j = 0; j < P; ++j) {
+        if (!std::isfinite(tau[j])) return fail(STG_E_INVALID, "tau must be finite");
+        if (tau[j] < 0.0 || tau[j] > 1.0) return fail(STG_E_INVALID, "tau is normalised time: every knot must lie in [0, 1]");
+        if (j > 0 && !(tau[j] > tau[j - 1])) return fail(STG_E_INVALID, "tau must be strictly increasing");
+    }
+    for (int32_t j = 0; P != 0 && j < kh; ++j) {
+        if (!std::isfinite(th[j]) || !std::isfinite(hk[3 * j]) || !std::isfinite(hk[3 * j + 1]) || !std::isfinite(hk[3 * j + 2]))
+            return fail(STG_E_INVALID, "th/hk must be finite");
+        if (j > 0 && !(th[j] > th[j - 1])) return fail(STG_E_INVALID, "th must be strictly increasing");
+    }
+    if (!ctx) return fail(STG_E_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (P == 0) {                                          // cleared: the step entries return STG_E_STATE until knots are set again
+        ctx->knots_P = 0; ctx->knots_kh = 0; ctx->knots_limit = 0.0;
+        return STG_OK;
+    }
+    double h[STG_KNOTS_DOUBLES] = {};
+    for (int32_t j = 0; j < P; ++j) h[j] = tau[j];
+    for (int32_t j = 0; j < kh; ++j) {
+        h[STG_MAX_KNOTS + j] = th[j];
+        for (int c = 0; c < 3; ++c) h[2 * STG_MAX_KNOTS + 3 * j + c] = hk[3 * j + c];
+    }
+    // (a launch that still reads the old knots finishes first: streams created non-blocking do not wait for the copy by themselves)
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(ctx->knots, h, sizeof(h), hipMemcpyHostToDevice));
+    ctx->knots_P = P; ctx->knots_kh = kh; ctx->knots_limit = s_limit;
+    return STG_OK;
+}
+
+// what stg_step_knots and stg_step_knots_ids share, as shaped_checks / enqueue_shaped above: the checks that need no list, then the one
+// kernel (stg_step_knots.hip)
+static int knots_checks(const stg_ctx* ctx, const char* who) {
+    if (!ctx) return fail(STG_E_INVALID, "ctx is NULL");
+    if (!ctx->have_params || !ctx->have_state) return fail(STG_E_STATE, std::string("stg_set_params and stg_reset must precede ") + who);
+    if (ctx->per_env) return fail(STG_E_STATE, std::string(who) + " works on the class table (stg_set_params), not on per-env parameters");
+    if (ctx->cfg.torque_model == 1) return fail(STG_E_INVALID, std::string(who) + " implements the reference torque model (cfg.torque_model = 0)");
+    if (ctx->knots_P == 0) return fail(STG_E_STATE, std::string("stg_set_pulse_knots must precede ") + who);
+    return STG_OK;
+}
+static int enqueue_knots(stg_ctx* ctx, KnotsStepArgs& w, int32_t act_f64, hipStream_t st) {
+    StepArgs& a = w.s;
+    HIP_TRY(hipSetDevice(ctx->device));
+    a.s = ctx->s; a.c = cfg_view(ctx->cfg); a.env_id0 = ctx->env_id0;
+    a.ctab = ctx->ctab; a.cls = ctx->cls; a.ncls = ctx->ncls;
+    a.counters = ctx->counters;
+    w.P = ctx->knots_P; w.kh = ctx->knots_kh; w.s_limit = ctx->knots_limit; w.knots = ctx->knots;
+    const bool rk45 = ctx->cfg.solver == STG_SOLVER_RK45;
+    const bool thermal = rk45 ? ctx->cfg.thermal != 0 : (ctx->cfg.thermal && ctx->cfg.temperature > 0);
+    stg_step_knots_launch(w, ctx->cfg.solver, thermal, ctx->ncls > 1, act_f64, st);
+    HIP_TRY(hipGetLastError());
+    return STG_OK;
+}
+
+int stg_step_knots(stg_ctx* ctx, int32_t K, const void* actions, int32_t act_f64, int32_t out_every, int32_t autoreset, float* obs,
+                   float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated, uint8_t* truncated,
+                   uint8_t* status, void* stream) {
+    if (int rc = knots_checks(ctx, "stg_step_knots")) return rc;
+    if (K < 1) return fail(STG_E_INVALID, "K must be >= 1");
+    if (!actions || !obs) return fail(STG_E_INVALID, "actions/obs must not be NULL");
+    KnotsStepArgs w{};
+    StepArgs& a = w.s;
+    if (int rc = step_outputs(ctx, a, obs, final_obs, reward, reward_f64, energy, terminated, truncated, status)) return rc;
+    a.N = ctx->N; a.actions = actions; a.K = K; a.out_every = out_every ? 1 : 0; a.autoreset = autoreset ? 1 : 0;
+    return enqueue_knots(ctx, w, act_f64, (hipStream_t)stream);
+}
+
+int stg_step_knots_ids(stg_ctx* ctx, int64_t M, const uint32_t* env_ids, const void* actions, int32_t act_f64, int32_t autoreset, float* obs,
+                       float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated, uint8_t* truncated,
+                       uint8_t* status, void* stream) {
+    if (int rc = knots_checks(ctx, "stg_step_knots_ids")) return rc;
+    if (M < 0 || M > 0xFFFFFFFFll) return fail(STG_E_INVALID, "M must be in [0, 2^32)");
+    if (!env_ids || !actions || !obs) return fail(STG_E_INVALID, "env_ids/actions/obs must not be NULL");
+    KnotsStepArgs w{};
+    StepArgs& a = w.s;
+    if (int rc = step_outputs(ctx, a, obs, final_obs, reward, reward_f64, energy, terminated, truncated, status)) return rc;
+    if (M == 0) return STG_OK;                         // an empty list: nothing to launch
+    a.N = M; a.ids = env_ids; a.n_state = ctx->N;
+    a.actions = actions; a.K = 1; a.out_every = 1; a.autoreset = autoreset ? 1 : 0;
+    return enqueue_knots(ctx, w, act_f64, (hipStream_t)stream);
 }
 
 extern "C++" {

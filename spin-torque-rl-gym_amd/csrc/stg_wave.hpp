@@ -4,10 +4,10 @@
 // The solvers of the reference take current_func(t) and field_func(t); a Python callable cannot run in a kernel, a table of knots can.
 // This header holds the waveform variants of the functions of stg_physics.hpp that take J as a per-solve constant (simple_solve, the
 // llgs_lane_* family); the functions in which the drive enters as an argument -- llgs_rhs, validation, the RK45 controller pieces, the
-// recorder, the normal stream -- are reused as they are.  Only stg_solve_wave.hip, stg_step_wave.hip and stg_step_shaped.hip instantiate
-// anything in here: the step kernels, stg_solve_kernel and the array kernels do not see this file's device code
-// (profiles/waveform_existing_kernels_unchanged.txt, profiles/step_wave_existing_kernels_unchanged.txt,
-// profiles/step_shaped_existing_kernels_unchanged.txt).
+// recorder, the normal stream -- are reused as they are.  Only stg_solve_wave.hip, stg_step_wave.hip, stg_step_shaped.hip and
+// stg_step_knots.hip instantiate anything in here: the step kernels, stg_solve_kernel and the array kernels do not see this file's device
+// code (profiles/waveform_existing_kernels_unchanged.txt, profiles/step_wave_existing_kernels_unchanged.txt,
+// profiles/step_shaped_existing_kernels_unchanged.txt, profiles/step_knots_existing_kernels_unchanged.txt).
 //
 // Waveform semantics (the C header states them for callers; physics.PiecewiseLinear and tests/waveform_ref.py use the same arithmetic):
 //   K knots, 2 <= K <= STG_MAX_KNOTS, times tk[0] < ... < tk[K-1] finite, values vk (a scalar, or three field components).
@@ -15,7 +15,8 @@
 //   v = vk[k] + (t - tk[k]) * ((vk[k+1] - vk[k]) / (tk[k+1] - tk[k])):  the quotient is rounded first, then the product, then the
 //   sum; no FMA contraction.  Each field component is evaluated separately.
 // Tables are per problem and lane-coalesced: times double[K][N], values double[K][C][N] (GlobalKnots) -- or, for the env-level pulse
-// shape of stg_step_shaped, one table for all lanes in LDS, scaled per lane (SharedKnots).  The solvers are templates over the source.
+// shape of stg_step_shaped, one table for all lanes in LDS, scaled per lane (SharedKnots) -- or, for the agent-shaped pulse of
+// stg_step_knots, shared times and the lane's own amplitudes, both in LDS (LaneKnots).  The solvers are templates over the source.
 #pragma once
 
 #include "stg_kernels.hpp"
@@ -54,6 +55,19 @@ struct ShapedStepArgs {
 // defined in stg_step_shaped.hip: enqueues the one kernel of a shaped step launch (s.ids != nullptr: the id form)
 void stg_step_shaped_launch(const ShapedStepArgs& a, int solver, bool thermal, bool multi, int act_f64, hipStream_t st);
 
+// K env steps whose actions carry the pulse's knot amplitudes (stg_step_knots, stg_step_knots_ids): the step launch's arguments plus the
+// knot times and the field table, which are the same for every env and every step (stg_set_pulse_knots)
+constexpr int STG_KNOTS_DOUBLES = 5 * STG_MAX_KNOTS;      // tau, th [STG_MAX_KNOTS] each, hk [STG_MAX_KNOTS][3]
+struct KnotsStepArgs {
+    StepArgs s;
+    int32_t P, kh;                // amplitude knots (2 ... STG_MAX_KNOTS); field knots, 0: zero field
+    double s_limit;               // the clamp of an amplitude
+    const double* knots;          // [STG_KNOTS_DOUBLES] on the device (stg_set_pulse_knots)
+};
+
+// defined in stg_step_knots.hip: enqueues the one kernel of an agent-shaped step launch (s.ids != nullptr: the id form)
+void stg_step_knots_launch(const KnotsStepArgs& a, int solver, bool thermal, bool multi, int act_f64, hipStream_t st);
+
 namespace stg {
 
 // Where a table's knots come from.  GlobalKnots: this lane's column of a per-problem table in HBM (stg_solve_wave, stg_step_wave).
@@ -83,6 +97,21 @@ struct SharedKnots {
     }
     __device__ __forceinline__ double time_at(int32_t j) const { return SCALED ? mul_x(knot(tk, j), st) : knot(tk, j); }
     __device__ __forceinline__ double value_at(int32_t j, int c) const { return SCALED ? mul_x(sv, knot(vk, j * C + c)) : knot(vk, j * C + c); }
+};
+
+// LaneKnots: the times as SharedKnots<1, true> has them -- tk[j] * st from one table in LDS --, the values sv * vk[j * 64] from THIS
+// lane's column of a [K][64] block in LDS, which the kernel fills from the lane's action at the top of each step (stg_step_knots: st = T,
+// sv = J, vk = the parsed amplitudes).  A lane reads only what it wrote itself, so no barrier stands between the fill and the reads.
+struct LaneKnots {
+    const double* tk;             // [K] (LDS)
+    const double* vk;             // this lane's column: knot j at vk[j * 64] (LDS)
+    double st, sv;
+    __device__ __forceinline__ double knot(const double* p, int32_t j) const {      // (as SharedKnots::knot)
+        asm volatile("" : "+v"(j));
+        return p[j];
+    }
+    __device__ __forceinline__ double time_at(int32_t j) const { return mul_x(knot(tk, j), st); }
+    __device__ __forceinline__ double value_at(int32_t j, int) const { return mul_x(sv, knot(vk, j * 64)); }
 };
 
 // One lane's view of one table, with the segment cursor: k is the segment [tk[k], tk[k+1]] the last query fell into (or the first / last

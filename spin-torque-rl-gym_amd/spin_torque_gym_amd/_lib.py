@@ -83,6 +83,9 @@ SYMBOLS = {
     "stg_set_pulse_shape": (C.c_int, [_VP, C.c_int32, _VP, _VP, C.c_int32, _VP, _VP]),
     "stg_step_shaped": (C.c_int, [_VP, C.c_int32, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "stg_step_shaped_ids": (C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "stg_set_pulse_knots": (C.c_int, [_VP, C.c_int32, _VP, C.c_double, C.c_int32, _VP, _VP]),
+    "stg_step_knots": (C.c_int, [_VP, C.c_int32, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "stg_step_knots_ids": (C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "stg_thermal_strength": (C.c_int, [_VP, C.c_int32, C.POINTER(C.c_double)]),
     "stg_thermal_normals": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_int32, _VP, _VP]),
     "stg_array_create": (C.c_int, [C.POINTER(_VP), C.c_int, C.c_int64, C.c_int64, C.POINTER(StgArrayConfig),

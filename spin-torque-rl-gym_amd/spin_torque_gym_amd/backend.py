@@ -162,6 +162,7 @@ class HipBackend:
         abi = cfg.to_abi()
         _lib.check(self.lib.stg_create(C.byref(self._ctx), device_index, self.n, self.env_id0, C.byref(abi)))
         self._cls = None
+        self.n_knots = 0               # P of set_pulse_knots (0: none set)
         n = self.n
         dev = self.device
         # (obs, reward, terminated, truncated) live in ONE buffer; the tensors below are views of it.  'soa': 54 B/env,
@@ -344,12 +345,37 @@ class HipBackend:
         being the shape applied to that step's parsed action.  Arguments, buffers and return values are step_many's."""
         return self._many(self.lib.stg_step_shaped, actions, out_every, autoreset)
 
-    def _many(self, entry, actions, out_every, autoreset):
-        """What step_many and step_shaped_many share (their C-ABI entries have one signature): buffers, the call, the views."""
+    def set_pulse_knots(self, tau, amplitude_limit, field_knots):
+        """The knot times of step_knots_many / step_knots_ids (stg_set_pulse_knots): tau = [P] normalised knot times in [0, 1], strictly
+        increasing; amplitude_limit = the clamp of an action's amplitudes; field_knots = (times [K] in seconds, values [K,3] in A/m) or
+        None (zero field).  tau = None clears the knots.  The library copies them; called once per context, not per step."""
+        def host(x, shape_):
+            x = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+            if x.shape != shape_:
+                raise ValueError(f"expected shape {shape_}, got {x.shape}")
+            return x
+        p = 0 if tau is None else int(len(tau))
+        kh = 0 if field_knots is None else int(len(field_knots[0]))
+        tau = host(tau, (p,)) if p else None
+        th = hk = None
+        if kh:
+            th, hk = host(field_knots[0], (kh,)), host(field_knots[1], (kh, 3))
+        hp = lambda x: None if x is None else C.c_void_p(x.ctypes.data)               # noqa: E731
+        _lib.check(self.lib.stg_set_pulse_knots(self._ctx, p, hp(tau), float(amplitude_limit), kh, hp(th), hp(hk)))
+        self.n_knots = p
+
+    def step_knots_many(self, actions, out_every=True, autoreset=False):
+        """step_many with actions [K, 2+P, N] that carry the pulse's knot amplitudes (stg_step_knots; P knots set by set_pulse_knots):
+        K env steps in one launch.  Buffers and return values are step_shaped_many's."""
+        return self._many(self.lib.stg_step_knots, actions, out_every, autoreset, rows=2 + self.n_knots)
+
+    def _many(self, entry, actions, out_every, autoreset, rows=2):
+        """What step_many, step_shaped_many and step_knots_many share (their C-ABI entries have one signature): buffers, the call, the
+        views.  rows: the rows of one step's action block."""
         a = torch.as_tensor(actions)
         f64 = a.dtype == torch.float64
         K = int(a.shape[0])
-        a = self._dev(a, torch.float64 if f64 else torch.float32, (K, 2, self.n))
+        a = self._dev(a, torch.float64 if f64 else torch.float32, (K, rows, self.n))
         ko = K if out_every else 1
         n, dev = self.n, self.device
         if self.records_layout:
@@ -408,8 +434,14 @@ class HipBackend:
         outputs (alloc_ids_outputs) and the stream rules are step_ids's; there is no workspace (identity order: nothing is staged)."""
         return self._ids(True, actions, env_ids, autoreset, None, out, stream)
 
-    def _ids(self, shaped, actions, env_ids, autoreset, workspace, out, stream):
-        """What step_ids and step_shaped_ids share: inputs and outputs on the launch's stream, the call."""
+    def step_knots_ids(self, actions, env_ids, autoreset=False, out=None, stream=None):
+        """step_ids with actions [2+P, M] that carry the pulse's knot amplitudes (stg_step_knots_ids).  Arguments, outputs
+        (alloc_ids_outputs) and the stream rules are step_shaped_ids's."""
+        return self._ids(True, actions, env_ids, autoreset, None, out, stream, entry=self.lib.stg_step_knots_ids, rows=2 + self.n_knots)
+
+    def _ids(self, shaped, actions, env_ids, autoreset, workspace, out, stream, entry=None, rows=2):
+        """What step_ids, step_shaped_ids and step_knots_ids share: inputs and outputs on the launch's stream, the call.  shaped: an
+        entry without a workspace (stg_step_shaped_ids, or `entry`, which has its signature); rows: the rows of an action block."""
         cur = torch.cuda.current_stream(self.device)
         s = cur if stream is None else stream
         if s is not cur:
@@ -418,7 +450,7 @@ class HipBackend:
             a = torch.as_tensor(actions)
             f64 = a.dtype == torch.float64
             m = int(a.shape[-1])
-            a = self._dev(a, torch.float64 if f64 else torch.float32, (2, m))
+            a = self._dev(a, torch.float64 if f64 else torch.float32, (rows, m))
             ids = self._dev(env_ids, torch.int32, (m,))        # (the kernel reads uint32: same bits for ids < 2^31)
             if s is not cur:
                 a.record_stream(s)
@@ -430,7 +462,7 @@ class HipBackend:
                                   out["terminated"], out["truncated"], out["status"])
             head = (self._ctx, m, _ptr(ids), _ptr(a), int(f64), int(bool(autoreset)))
             if shaped:
-                _lib.check(self.lib.stg_step_shaped_ids(*head, *outs, C.c_void_p(s.cuda_stream)))
+                _lib.check((entry or self.lib.stg_step_shaped_ids)(*head, *outs, C.c_void_p(s.cuda_stream)))
             else:
                 _lib.check(self.lib.stg_step_ids(*head, _ptr(ws), *outs, C.c_void_p(s.cuda_stream)))
         out["_keep"] = (a, ids, ws)           # inputs stay alive while the launch may still read them

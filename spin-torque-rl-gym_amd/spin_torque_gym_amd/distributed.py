@@ -79,6 +79,10 @@ class ShardedSpinTorqueVecEnv:
             raise NotImplementedError("ShardedSpinTorqueVecEnv is not implemented with pulse_shape or applied_field: shaped pulses and "
                                       "an applied field run on SpinTorqueVecEnv (step, step_many, step_ids, send / recv); the sharded "
                                       "env does not hand the shape to its shards yet")
+        if env_kwargs.get("pulse_knots") is not None:
+            raise NotImplementedError("ShardedSpinTorqueVecEnv is not implemented with pulse_knots: agent-shaped pulses run on "
+                                      "SpinTorqueVecEnv (step, step_many, step_ids, send / recv); the sharded env does not hand the "
+                                      "knots to its shards yet")
         if not dist.is_initialized():
             raise RuntimeError("torch.distributed must be initialised (backend 'nccl' = RCCL on ROCm, or 'gloo')")
         if gather_algo not in ("all_gather", "p2p"):

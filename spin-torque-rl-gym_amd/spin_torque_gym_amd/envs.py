@@ -221,6 +221,48 @@ def field_knots(applied_field, max_duration):
     return np.array([0.0, float(max_duration) if max_duration > 0 else 1.0]), np.stack([h, h])
 
 
+_KNOTS_LIMIT = ("{what} is not implemented on this backend while pulse_knots is set: step() runs everywhere (stg_step_wave on tables "
+                "built from the actions); step_many, step_ids and async_reset / send / recv need a backend with the knot entries "
+                "(HipBackend.step_knots_many / step_knots_ids: stg_step_knots, stg_step_knots_ids), and there is no sharded variant yet")
+
+
+def check_pulse_knots(tau, amplitude_limit):
+    """pulse_knots= and amplitude_limit= of the envs -> (tau float64 [P], limit): normalised knot times in [0, 1], finite and strictly
+    increasing, 2 <= P <= STG_MAX_KNOTS; the limit finite and > 0 (tau None passes as (None, limit))."""
+    if tau is None:
+        return None, float(amplitude_limit)
+    tau = np.array(tau, dtype=np.float64)
+    if tau.ndim != 1 or not 2 <= tau.shape[0] <= _lib.STG_MAX_KNOTS:
+        raise ValueError(f"pulse_knots takes 2 ... {_lib.STG_MAX_KNOTS} knot times [P], got shape {tau.shape}")
+    if not np.isfinite(tau).all() or not (np.diff(tau) > 0).all():
+        raise ValueError("pulse_knots must be finite and strictly increasing")
+    if float(tau[0]) < 0.0 or float(tau[-1]) > 1.0:
+        raise ValueError("pulse_knots times are normalised: every tau must lie in [0, 1] (tau * pulse duration is the knot time)")
+    limit = float(amplitude_limit)
+    if not (np.isfinite(limit) and limit > 0.0):
+        raise ValueError("amplitude_limit must be finite and > 0")
+    return tau, limit
+
+
+def parse_knot_actions_fp64(a: torch.Tensor, max_current: float, max_duration: float, amplitude_limit: float):
+    """The action parse of stg_step_knots restated in torch, for actions [2+P,N] float32 or float64: rows 0 and 1 as parse_actions_fp64;
+    the amplitude rows in fp64, clamped to +-amplitude_limit (NaN kept); a NaN amplitude voids its env's action to J = 0, T = 1e-12 and
+    zero amplitudes.  Returns (J [N], T [N], s [P,N]) float64 -- the values the kernel parses from the same actions, bit for bit."""
+    J, T = parse_actions_fp64(a[:2], max_current, max_duration)
+    s = a[2:].double().clamp(-amplitude_limit, amplitude_limit)              # (clamp keeps NaN and takes +-Inf to the limit)
+    void = torch.isnan(s).any(dim=0)
+    J = torch.where(void, torch.zeros_like(J), J)
+    T = torch.where(void, torch.full_like(T, 1e-12), T)
+    return J, T, torch.where(void[None, :], torch.zeros_like(s), s)
+
+
+def knot_tables(tau, J: torch.Tensor, T: torch.Tensor, s: torch.Tensor):
+    """(tj [P,N], jk [P,N]) of the parsed knot action (J [N], T [N], s [P,N]): knot times tau_j * T, knot values J * s_j, each ONE
+    rounded fp64 product."""
+    tau = torch.as_tensor(tau, dtype=torch.float64, device=T.device)
+    return (tau[:, None] * T[None, :]).contiguous(), (J[None, :] * s).contiguous()
+
+
 def parse_actions_fp64(a: torch.Tensor, max_current: float, max_duration: float):
     """The kernels' action parse restated in torch, for actions [2,N] float32 or float64: the safety clamp in the action's own dtype
     (current to +-1e8, duration to [1e-12, 1e-6], NaN kept), NaN / Inf in either -> (0, 1e-12), then in fp64 the clips to max_current and
@@ -265,6 +307,11 @@ class SpinTorqueVecEnv:
     the library.  ``step()`` runs on stg_step_wave with tables built from the actions; ``step_many``, ``step_ids`` and ``async_reset`` /
     ``send`` / ``recv`` run on stg_step_shaped / stg_step_shaped_ids, which hold the shape on chip (handed to the backend once) and give
     every env the bits ``step()`` gives it.  Only ``ShardedSpinTorqueVecEnv`` still refuses a shape or a field.
+    Agent-shaped pulses: ``pulse_knots=tau`` (P normalised knot times in [0, 1]) widens the action to ``[J, T, s_0 ... s_{P-1}]`` -- the
+    policy chooses the knot amplitudes per env and per step, clamped to +-``amplitude_limit``; the current is the table of knots
+    (tau_j T, J s_j) (include/spintorque_hip.h, stg_step_knots, states the parse: a NaN amplitude voids the action).  Not together with
+    ``pulse_shape``; ``applied_field`` works as above.  Actions are [N, 2+P], [K, N, 2+P] for ``step_many`` and [M, 2+P] for
+    ``step_ids`` / ``send``; every entry point runs on stg_step_knots / stg_step_knots_ids.
     """
 
     def __init__(self, num_envs: int, device_type: Union[str, Sequence[str]] = "stt_mram",
@@ -277,12 +324,18 @@ class SpinTorqueVecEnv:
                  max_attempts: int = 200_000, lane_sort: Optional[bool] = None, wave_spec: Optional[bool] = None, torque_model: str = "reference",
                  noise_model: str = "white", correlation_time: float = 1e-12,
                  per_env_params: Optional[Dict[str, Any]] = None, out_layout: str = "records",
-                 diagnostics: bool = False, lane_refill: Optional[int] = None, backend=None, pulse_shape=None, applied_field=None):
+                 diagnostics: bool = False, lane_refill: Optional[int] = None, backend=None, pulse_shape=None, applied_field=None,
+                 pulse_knots=None, amplitude_limit: float = 1.0):
         self.num_envs = int(num_envs)
         self.pulse_shape = check_pulse_shape(pulse_shape)
+        if pulse_knots is not None and pulse_shape is not None:
+            raise ValueError("pulse_knots and pulse_shape exclude each other: the action carries the amplitudes, or the shape is fixed")
+        self.pulse_knots, self.amplitude_limit = check_pulse_knots(pulse_knots, amplitude_limit)
+        self._knots_on = self.pulse_knots is not None
+        self._act_w = 2 + (len(self.pulse_knots) if self._knots_on else 0)          # width of one env's action
         self.applied_field = applied_field
         self._field_knots = field_knots(applied_field, max_duration)
-        self._wave_on = self.pulse_shape is not None or self._field_knots is not None
+        self._wave_on = self.pulse_shape is not None or self._field_knots is not None or self._knots_on
         self._field_tab = None                # the field table on the device, [K,N] / [K,3,N], built on the first shaped step
         factory = DeviceFactory()
         types = [device_type] if isinstance(device_type, str) else list(device_type)
@@ -321,7 +374,9 @@ class SpinTorqueVecEnv:
             raise ValueError("per_env_params with several base device classes needs class_index (the base of each env)")
         self.profiler = _TimerTable()
         self.backend = self._make_backend()
-        self.single_action_space = _box([-max_current, 0.0], [max_current, max_duration], dtype=np.float32)
+        n_amp = self._act_w - 2
+        self.single_action_space = _box([-max_current, 0.0] + [-self.amplitude_limit] * n_amp,
+                                        [max_current, max_duration] + [self.amplitude_limit] * n_amp, dtype=np.float32)
         self.single_observation_space = _box(-np.inf, np.inf, shape=(12,), dtype=np.float32)
         self._needs_reset = True
         self._pool = None                     # the send/recv pool while in async mode (async_reset ... reset)
@@ -354,14 +409,17 @@ class SpinTorqueVecEnv:
                                                             self._per_env_params))
         else:
             b.set_params([flatten_params(d) for d in self.devices], self._class_index)
-        if self._wave_on and self._shaped(b):
+        if self._knots_on:
+            if self._shaped(b):
+                b.set_pulse_knots(self.pulse_knots, self.amplitude_limit, self._field_knots)      # once per context
+        elif self._wave_on and self._shaped(b):
             b.set_pulse_shape(self.pulse_shape, self._field_knots)           # once per context: the fused / subset entries read it
         return b
 
-    @staticmethod
-    def _shaped(backend):
-        """Does the backend offer the shaped fused / subset entries?  (HipBackend does; a test seam may offer step_wave only.)"""
-        return getattr(backend, "step_shaped_many", None) is not None
+    def _shaped(self, backend):
+        """Does the backend offer the fused / subset entries of this env's drive -- the knot entries with pulse_knots, the shaped ones
+        otherwise?  (HipBackend does; a test seam may offer step_wave only.)"""
+        return getattr(backend, "step_knots_many" if self._knots_on else "step_shaped_many", None) is not None
 
     # -- Gymnasium VectorEnv-shaped API ---------------------------------------------------------------
     def reset(self, seed: Optional[int] = None, options: Optional[Dict[str, Any]] = None):
@@ -392,11 +450,30 @@ class SpinTorqueVecEnv:
         a = torch.as_tensor(actions)
         if not actions_soa:
             a = a.t()
+        if self._knots_on and (a.dim() != 2 or a.shape[0] != self._act_w):
+            raise ValueError(f"actions must be [N, {self._act_w}] (J, T and {self._act_w - 2} knot amplitudes), got {tuple(torch.as_tensor(actions).shape)}")
         t0 = time.perf_counter()
+        if self._knots_on and self._shaped(self.backend):
+            if out is not None:
+                raise NotImplementedError("step(out=) is not implemented with pulse_knots")
+            obs, rew, rew64, term, trunc, status = (None if x is None else x[0] for x in
+                                                    self.backend.step_knots_many(a.unsqueeze(0), out_every=True, autoreset=self.autoreset))
+            self.profiler.add("step", time.perf_counter() - t0)
+            info = {} if status is None else {"status": status}
+            if self.autoreset:
+                info["final_obs"] = self.backend.final_obs_many[0].t()
+            if self.diagnostics:
+                info.update(reward_f64=rew64, energy=self.backend.energy_many[0])
+            return obs.t(), rew, term.bool(), trunc.bool(), info
         if self._wave_on:
             a = a.to(device=self.backend.device, dtype=torch.float64 if a.dtype == torch.float64 else torch.float32)
             kw = {} if out is None else {"out": out}
-            obs, rew, rew64, term, trunc, status = self.backend.step_wave(a, self._wave_tables(a), autoreset=self.autoreset, **kw)
+            wave = self._wave_tables(a)
+            if self._knots_on:
+                # stg_step_wave parses rows 0 and 1 itself: a void action goes in as a NaN current, which it parses to (0, 1e-12)
+                void = torch.isnan(a[2:]).any(dim=0)
+                a = torch.stack([torch.where(void, torch.full_like(a[0], float("nan")), a[0]), a[1]])
+            obs, rew, rew64, term, trunc, status = self.backend.step_wave(a, wave, autoreset=self.autoreset, **kw)
         elif out is None:
             obs, rew, rew64, term, trunc, status = self.backend.step(a, autoreset=self.autoreset)
         else:
@@ -419,6 +496,9 @@ class SpinTorqueVecEnv:
         """The tables of one shaped step for actions a [2,N] on the device (the `wave` of HipBackend.step_wave): a few elementwise
         ops on [K,N].  The current table follows the parsed action; the field table is the same at every step."""
         wave = {"current": None, "field": None}
+        if self._knots_on:
+            J, T, s = parse_knot_actions_fp64(a, self.cfg.max_current, self.cfg.max_duration, self.amplitude_limit)
+            wave["current"] = knot_tables(self.pulse_knots, J, T, s)
         if self.pulse_shape is not None:
             J, T = parse_actions_fp64(a, self.cfg.max_current, self.cfg.max_duration)
             wave["current"] = pulse_tables(self.pulse_shape, J, T)
@@ -433,17 +513,19 @@ class SpinTorqueVecEnv:
 
     def _no_wave(self, what):
         if self._wave_on and not self._shaped(self.backend):
-            raise NotImplementedError(_WAVE_LIMIT.format(what=what))
+            raise NotImplementedError((_KNOTS_LIMIT if self._knots_on else _WAVE_LIMIT).format(what=what))
 
     def step_many(self, actions, out_every: bool = True, actions_soa: bool = False):
-        """K env steps in one launch.  actions [K,N,2] (or [K,2,N] with actions_soa)."""
+        """K env steps in one launch.  actions [K,N,2] (or [K,2,N] with actions_soa); with pulse_knots the 2 is 2+P."""
         self._no_pool("step_many")
         self._no_wave("step_many")
         a = torch.as_tensor(actions)
         if not actions_soa:
             a = a.transpose(1, 2)
         t0 = time.perf_counter()
-        launch = self.backend.step_shaped_many if self._wave_on else self.backend.step_many
+        if self._knots_on and (a.dim() != 3 or a.shape[1] != self._act_w):
+            raise ValueError(f"actions must be [K, N, {self._act_w}], got {tuple(torch.as_tensor(actions).shape)}")
+        launch = self.backend.step_knots_many if self._knots_on else (self.backend.step_shaped_many if self._wave_on else self.backend.step_many)
         obs, rew, rew64, term, trunc, status = launch(a, out_every=out_every, autoreset=self.autoreset)
         self.profiler.add("step_many", time.perf_counter() - t0)
         info = {} if status is None else {"status": status}
@@ -482,6 +564,9 @@ class SpinTorqueVecEnv:
         if self._wave_on:                     # (only then: a plain env's dict stays what it was)
             d["pulse_shape"] = None if self.pulse_shape is None else [self.pulse_shape.times.tolist(), self.pulse_shape.values.tolist()]
             d["applied_field"] = None if self._field_knots is None else [x.tolist() for x in self._field_knots]
+        if self._knots_on:
+            d["pulse_knots"] = self.pulse_knots.tolist()
+            d["amplitude_limit"] = self.amplitude_limit
         return d
 
     def state_dict(self):
@@ -559,8 +644,9 @@ class SpinTorqueVecEnv:
 
     def _ids_actions(self, actions, m):
         a = torch.as_tensor(actions)
-        if a.dim() != 2 or tuple(a.shape) != (m, 2):
-            raise ValueError(f"actions must be [M, 2] = [{m}, 2], got {tuple(a.shape)}")
+        w = self._act_w
+        if a.dim() != 2 or tuple(a.shape) != (m, w):
+            raise ValueError(f"actions must be [M, {w}] = [{m}, {w}], got {tuple(a.shape)}")
         return a.t()
 
     def _ids_result(self, out, env_id):
@@ -588,7 +674,9 @@ class SpinTorqueVecEnv:
             self._ids_ws = self.backend.ids_workspace(self.num_envs)
         env_id = torch.as_tensor(ids).to(self.backend.device)
         t0 = time.perf_counter()
-        if self._wave_on:
+        if self._knots_on:
+            out = self.backend.step_knots_ids(a, env_id, autoreset=self.autoreset)
+        elif self._wave_on:
             out = self.backend.step_shaped_ids(a, env_id, autoreset=self.autoreset)
         else:
             out = self.backend.step_ids(a, env_id, autoreset=self.autoreset, workspace=self._ids_ws)
@@ -699,7 +787,9 @@ class _AsyncPool:
         self.next_stream = (k + 1) % len(self.streams)
         b = env.backend
         env_id = torch.as_tensor(ids).to(b.device)
-        if env._wave_on:
+        if env._knots_on:
+            out = b.step_knots_ids(a, env_id, autoreset=env.autoreset, stream=self.streams[k])
+        elif env._wave_on:
             out = b.step_shaped_ids(a, env_id, autoreset=env.autoreset, stream=self.streams[k])
         else:
             out = b.step_ids(a, env_id, autoreset=env.autoreset, workspace=self.workspaces[k], stream=self.streams[k])
@@ -733,7 +823,8 @@ class SpinTorqueEnv(_EnvBase):
                  reward_components: Optional[Dict[str, Dict]] = None, action_mode: str = "continuous",
                  observation_mode: str = "vector", success_threshold: float = 0.9, energy_penalty_weight: float = 0.1,
                  render_mode: Optional[str] = None, seed: Optional[int] = None, solver: str = "rk4",
-                 device_index: int = 0, backend=None, pulse_shape=None, applied_field=None):
+                 device_index: int = 0, backend=None, pulse_shape=None, applied_field=None, pulse_knots=None,
+                 amplitude_limit: float = 1.0):
         if reward_components is not None:
             raise NotImplementedError("custom reward callables are arbitrary Python and stay on the reference "
                                       "(SURVEY.md section 2); the GPU path implements the default 4-component reward")
@@ -753,12 +844,12 @@ class SpinTorqueEnv(_EnvBase):
                                      max_duration, temperature, include_thermal_fluctuations, success_threshold,
                                      energy_penalty_weight, solver, seed, False, False,
                                      device_index, 0, diagnostics=True, backend=backend, pulse_shape=pulse_shape,
-                                     applied_field=applied_field)
+                                     applied_field=applied_field, pulse_knots=pulse_knots, amplitude_limit=amplitude_limit)
         self.device = self._vec.devices[0]
         self.target_states = self._vec.target_states
         self.solver_name = solver
         if action_mode == "continuous":
-            self.action_space = _box([-max_current, 0.0], [max_current, max_duration], dtype=np.float32)
+            self.action_space = self._vec.single_action_space          # Box(2,), or Box(2+P,) with pulse_knots
         else:
             self.current_levels = np.linspace(-max_current, max_current, 5)
             self.duration_levels = np.array([0.1e-9, 0.5e-9, 1.0e-9, 2.0e-9])
@@ -822,8 +913,9 @@ class SpinTorqueEnv(_EnvBase):
                 # H8: the reference's safety wrapper rejects these modes' inputs and the catch-all takes over
                 raise TypeError("only length-1 arrays can be converted to Python scalars")
             a = action if isinstance(action, np.ndarray) else np.array(action, dtype=np.float32)
-            if a.shape != (2,):                     # monitoring.py:300-302
-                a = np.array([0.0, 1e-12], dtype=np.float32)
+            w = self._vec._act_w
+            if a.shape != (w,):                     # monitoring.py:300-302
+                a = np.array([0.0, 1e-12] + [0.0] * (w - 2), dtype=np.float32)
             if a.dtype not in (np.float32, np.float64):
                 a = a.astype(np.float32)
             prev_alignment = float(np.dot(self.current_magnetization, self.target_magnetization))
@@ -839,7 +931,9 @@ class SpinTorqueEnv(_EnvBase):
             self._solve_time = [dt_step, self._solve_time[1] + dt_step]
             self.profiler.add("env_step", dt_step)
             # the kernel's parsed action comes back through the observation; recompute it in fp64 for `info`
-            J, T = _parse_action_host(a, self.max_current, self.max_duration)
+            J, T = _parse_action_host(a[:2], self.max_current, self.max_duration)
+            if np.isnan(a[2:]).any():               # a NaN amplitude voids the action (stg_step_knots)
+                J, T = 0.0, 1e-12
             self.last_action = np.array([J, T])
             alignment = float(np.dot(self.current_magnetization, self.target_magnetization))
             terminated, truncated = bool(term[0]), bool(trunc[0])
@@ -899,6 +993,9 @@ class SpinTorqueEnv(_EnvBase):
         v = self._vec
         if not v._wave_on:
             return {}
+        if v._knots_on:
+            return {"pulse_knots": v.pulse_knots.tolist(), "amplitude_limit": v.amplitude_limit,
+                    "applied_field": None if v._field_knots is None else {"times": v._field_knots[0].tolist(), "values": v._field_knots[1].tolist()}}
         return {"pulse_shape": None if v.pulse_shape is None else {"tau": v.pulse_shape.times.tolist(), "scale": v.pulse_shape.values.tolist()},
                 "applied_field": None if v._field_knots is None else {"times": v._field_knots[0].tolist(), "values": v._field_knots[1].tolist()}}
 
