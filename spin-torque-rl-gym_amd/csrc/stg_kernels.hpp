@@ -918,9 +918,10 @@ stg_step_kernel(const StepArgs a) {
 
     if (producer) {
         // per env-step: wait for the stream positions (H1), then stay one chunk ahead of integrating wavefront `cw`.
-        // Normals per chunk: RK45 6 (initial step) then 18 per attempt; the fixed-step solvers SHARED_CHUNK_FIXED = 24: two RK4
-        // sub-steps with the white field, or eight sub-steps of Euler / of the Ornstein-Uhlenbeck field (3 each)
-        constexpr int n_first = SOLVER == STG_SOLVER_RK45 ? 6 : SHARED_CHUNK_FIXED;     // (Euler / OU: SHARED_SUBS3 sub-steps of 3)
+        // Normals per chunk: RK45 12 (initial step: 6, then z2 / z3 of attempt 1) then 18 per attempt (its z4 ... z7, then z2 / z3 of the next);
+        // the fixed-step solvers SHARED_CHUNK_FIXED = 24: two RK4 sub-steps with the white field, or eight sub-steps of Euler / of the
+        // Ornstein-Uhlenbeck field (3 each)
+        constexpr int n_first = SOLVER == STG_SOLVER_RK45 ? SHARED_FIRST_RK45 : SHARED_CHUNK_FIXED;     // (Euler / OU: SHARED_SUBS3 sub-steps of 3)
         static_assert(3 * SHARED_SUBS3 == SHARED_CHUNK_FIXED, "chunk size of the 3-normal sub-steps");
         constexpr int n_chunk = SOLVER == STG_SOLVER_RK45 ? SHARED_CHUNK_RK45 : n_first;
         const double ghs = FIELD ? load_llgs(row).ghs : 0.0;

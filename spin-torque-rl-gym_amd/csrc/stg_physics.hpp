@@ -354,8 +354,9 @@ struct InlineNormals {
     __device__ __forceinline__ int32_t chunk_end_go(int32_t go) { return go; }
 };
 
-// A chunk of the shared stream (one rendezvous of an integrating wavefront with its producer): an RK45 attempt (18 normals; the
-// prologue's chunk 0 holds 6), or -- fixed-step solvers -- SHARED_SUBS_RK4 RK4 sub-steps with the white field (12 normals each) =
+// A chunk of the shared stream (one rendezvous of an integrating wavefront with its producer): 18 normals of the RK45 stream -- the
+// fields z4 ... z7 of attempt c, then z2, z3 of attempt c + 1; the prologue's chunk 0 holds its 6 and z2, z3 of attempt 1, see
+// SharedNormalsT --, or -- fixed-step solvers -- SHARED_SUBS_RK4 RK4 sub-steps with the white field (12 normals each) =
 // SHARED_SUBS3 sub-steps of the forms that draw 3 per sub-step (Euler, the Ornstein-Uhlenbeck field).  Two RK4 sub-steps per chunk
 // instead of one (round 4): RK4 + thermal 32 768 envs 0.518 -> 0.489 ms, 65 536 envs 0.544 -> 0.534, Euler 0.339 -> 0.330; four per
 // chunk with a ring of two chunks: worse (0.546 / 0.570); a ring of 8 two-sub-step chunks no longer fits four workgroups per CU.
@@ -363,6 +364,8 @@ constexpr int SHARED_SUBS_RK4 = 2;
 constexpr int SHARED_SUBS3 = 4 * SHARED_SUBS_RK4;
 constexpr int SHARED_CHUNK_FIXED = 12 * SHARED_SUBS_RK4;     // normals per chunk of the fixed-step solvers
 constexpr int SHARED_CHUNK_RK45 = 18;
+constexpr int SHARED_TAIL_RK45 = 6;         // of which the last two fields belong to the NEXT attempt
+constexpr int SHARED_FIRST_RK45 = 6 + SHARED_TAIL_RK45;      // chunk 0: the prologue's two fields, then z2, z3 of attempt 1
 constexpr int PC_STOP = 1 << 30;
 constexpr int PC_SPIN_CAP = 1 << 22;
 
@@ -390,6 +393,28 @@ __device__ __forceinline__ void pc_store(int* p, int v) {
 // T = float: raw normals (fixed-step solvers, whose producer is the critical wavefront and should do no extra work);
 // T = double, SCALED: the finished thermal field c * z (RK45: the integrating wavefront saves the conversions and the
 // scaling of every RHS call).  DEPTH = chunks in the ring (a power of two; 2 with BARRIER).
+//
+// The RK45 ring (BARRIER, SCALED).  The stream of a solve is cut two fields behind the attempt boundary:
+//   chunk 0     = the prologue's 6 values + z2, z3 of attempt 1 (12 values; the last six stand at positions 12..17 of slot 0),
+//   chunk c >= 1 = z4 ... z7 of attempt c + z2, z3 of attempt c + 1 (18 values), in slot c & 1,
+// so that the rendezvous for chunk c stands INSIDE attempt c, between the RHS call that consumed z2 and the fetch of z4 (chunk_meet),
+// where nothing of the pair's is in flight, instead of at the loop's back edge, where the flag's LDS write, the barrier and the fetch of
+// z2 / z3 were serial with the step-size controller's dependency chain.  z2 / z3 of attempt c + 1 are fetched under the last RHS call of
+// attempt c.  Flag copy c & 1 says whether there is an attempt c + 1; it is written when that is known (before the loop for c = 0, at the
+// end of attempt c otherwise: chunk_end_go) and no rendezvous follows a 1 -- the one that publishes it is chunk_meet of attempt c + 1 --
+// while a 0 is followed by the closing rendezvous at once.
+// Rendezvous per solve, integrating wavefront: H2, then for a solve of n attempts chunk_meet in each of them, then the closing one:
+//   n = 0: H2 + 1 (flag copy 0 = 0, closing)        n = 1: H2 + 2 (meet in attempt 1; flag copy 1 = 0, closing)        n: H2 + n + 1.
+// Producer (produce_normals): H2, then per round k = 1, 2, ...: fill chunk k, rendezvous, read flag copy (k - 1) & 1, return on 0.  Its
+// round k rendezvous is chunk_meet of attempt k if there is one -- then flag copy (k - 1) & 1 was written 1 at the end of attempt k - 1,
+// before that barrier, and it goes on -- and the closing one if k = n + 1 -- flag copy n & 1 is 0 and it returns: H2 + n + 1 as well, for
+// n = 0 (one round), n = 1 (two rounds) and any n.  With K fused env-steps every env-step adds H1 (stg_step_kernel) on both sides and,
+// where the wavefront integrates at all, one such solve: K * H1 + sum over those env-steps of (H2 + n_k + 1) on both sides.
+// What a barrier orders: slot k & 1 held chunk k - 2, whose last values (z2 / z3 of attempt k - 1) the integrating wavefront has waited for
+// (batch_ready) before rendezvous k - 1, after which the producer fills it; the producer's writes of chunk k precede rendezvous k, after
+// which the integrating wavefront reads it.  Flag copy c & 1 is rewritten at the end of attempt c + 2, behind rendezvous c + 2, which the
+// producer reaches only after it has read the copy in round c + 1.  When the solve ends the producer may have filled a chunk nobody
+// reads: a stream is re-seeded per (env, env-step).
 template <typename T, bool SCALED, int DEPTH, bool BARRIER>
 struct SharedNormalsT {
     static constexpr int CHUNK = SCALED ? SHARED_CHUNK_RK45 : SHARED_CHUNK_FIXED;    // (the RK45 kernels hand over finished fields)
@@ -417,6 +442,16 @@ struct SharedNormalsT {
         idx += 3;
         return V3{(double)b[0], (double)b[64], (double)b[128]};
     }
+    // RK45 ring: the rendezvous for the next chunk, inside an attempt -- behind the wait for z2 / z3 (the last values read from the slot
+    // the producer fills next), in front of the first read of z4; then the read position is the start of the other slot
+    __device__ __forceinline__ void chunk_meet() {
+        // (only the RK45 ring, kToggle, comes here: the other forms instantiate the RK45 solve in a branch that is never taken)
+        __syncthreads();
+        slot_b ^= CHUNK * 64 * (int)sizeof(T);
+        idx = 0;
+    }
+    // (... and the read position of the chunk's last two fields, z2 / z3 of the next attempt; chunk 0 keeps them there too)
+    __device__ __forceinline__ void seek_tail() { idx = CHUNK - SHARED_TAIL_RK45; }
     // an early look at the producer's count (relaxed: nothing waits for it here), so that chunk_end usually finds the
     // next chunk published without an LDS round trip of its own
     __device__ __forceinline__ void peek() {
@@ -431,13 +466,16 @@ struct SharedNormalsT {
     // branch a scalar compare, where a bool becomes a lane mask, a select and a mask test)
     __device__ __forceinline__ int32_t chunk_end_go(int32_t go) {
         const bool mine = go != 0;
+        if (kToggle) {
+            // RK45 ring: the flag is published here, the rendezvous that carries a 1 is the one INSIDE the next attempt (chunk_meet); a 0
+            // closes the solve at once
+            *(volatile lds_int*)((volatile __attribute__((address_space(3))) char*)lds_flag(hs) + flag_b) = go;
+            flag_b ^= (int)sizeof(int);
+            if (!mine) __syncthreads();
+            return go;
+        }
         if (BARRIER) {
-            if (kToggle) {
-                *(volatile lds_int*)((volatile __attribute__((address_space(3))) char*)lds_flag(hs) + flag_b) = go;
-                flag_b ^= (int)sizeof(int); slot_b ^= CHUNK * 64 * (int)sizeof(T);
-            } else {
-                lds_flag(hs)[it & 1] = go;
-            }
+            lds_flag(hs)[it & 1] = go;
             __syncthreads();
             ++it;
             idx = 0;
@@ -478,13 +516,23 @@ __device__ __forceinline__ void produce_normals(T* buf, int* hs, int lane, const
             b[(j + 0) * 64] = (T)z.x; b[(j + 1) * 64] = (T)z.y; b[(j + 2) * 64] = (T)z.z;
         }
     };
-    fill(0, n_first);
+    if constexpr (BARRIER && SCALED) {
+        // RK45 ring: chunk 0 ends with z2, z3 of attempt 1, and keeps them where every later chunk has the next attempt's z2, z3: the
+        // prologue's values go to positions 0.., the tail to the slot's last SHARED_TAIL_RK45 (slot "0" of a ring that starts there)
+        fill(0, n_first - SHARED_TAIL_RK45);
+        T* ring = buf;
+        buf += (SHARED_CHUNK_RK45 - SHARED_TAIL_RK45) * 64;
+        fill(0, SHARED_TAIL_RK45);
+        buf = ring;
+    } else {
+        fill(0, n_first);
+    }
     if (!BARRIER) pc_store(hs, 1);
     __syncthreads();                                   // H2: chunk 0 ready (the integrating wavefront waits here too)
     if (BARRIER) {
         for (int k = 1;; ++k) {
             fill(k & 1, n_chunk);                      // chunk k, while the integrating wavefront works on chunk k - 1
-            __syncthreads();                           // = the integrating wavefront's chunk_end rendezvous
+            __syncthreads();                           // = the integrating wavefront's rendezvous k (Euler: chunk_end; RK45: chunk_meet, or the closing one)
             if (lds_flag(hs)[(k - 1) & 1] == 0) return;
         }
     }
@@ -1070,7 +1118,7 @@ __device__ __forceinline__ int32_t attempt_loop_next(lanemask& active, lanemask 
 // M: the loop's flags.  UNIFORM_IT: the caller's loop is one env per lane and takes arrived lanes out of M.active itself.
 template <bool THERMAL, bool RECORD, bool AXIS_Z, bool UNIFORM_IT, class NSRC>
 __device__ __forceinline__ void llgs_lane_attempt(LlgsLane& L, LlgsMasks& M, V3& out_m, const LlgsK& k, const Dp5Tab& tb, double rtol,
-                                                  double atol, double max_step, const Recorder& rec, const LlgsEnergyK& ek, NSRC& ns, V3 z2, V3 z3) {
+                                                  double atol, double max_step, const Recorder& rec, const LlgsEnergyK& ek, NSRC& ns, V3& z2, V3& z3) {
     constexpr double A21 = 1.0 / 5;
     constexpr double A31 = 3.0 / 40, A32 = 9.0 / 40;
     constexpr double A41 = 44.0 / 45, A42 = -56.0 / 15, A43 = 32.0 / 9;
@@ -1093,13 +1141,16 @@ __device__ __forceinline__ void llgs_lane_attempt(LlgsLane& L, LlgsMasks& M, V3&
     const bool on_end = add_x(t, h) <= T;
     const V3 k1 = L.f;
     // normal-stream phases alternate per call (k2: even, k3: odd, ...).  Inline source: each field is drawn one call ahead.  Shared source: the
-    // six fields are fetched as three batches of two -- z2 + z3 by the caller, z4 + z5 under k3, z6 + z7 under k5 -- each with one wait in
-    // front of its first use (batch_ready)
+    // six fields are fetched as three batches of two -- z2 + z3 by the previous attempt (behind its last RHS call; the first attempt's by the
+    // caller), z4 + z5 under k3, z6 + z7 under k5 -- each with one wait in front of its first use (batch_ready)
     constexpr bool BATCH = THERMAL && NSRC::kShared;
     if (THERMAL && !NSRC::kShared) { z2 = draw(true); z3 = draw(false); }
     V3 y2{y.x + (k1.x * A21) * h, y.y + (k1.y * A21) * h, y.z + (k1.z * A21) * h};
     if (BATCH) batch_ready(y2.z, z2.x, z2.y, z2.z, z3.x, z3.y, z3.z);
     const V3 k2 = fun(y2, z2, true);
+    // (shared source: z2 / z3 were the last values of the previous chunk and are in registers; this attempt's chunk -- z4 ... z7 and the
+    // next attempt's z2 / z3 -- is met here, with nothing of the pair's in flight: the flag went out at the end of the previous attempt)
+    if constexpr (BATCH) ns.chunk_meet();
     V3 z4 = draw(true), z5{0.0, 0.0, 0.0};
     // (nothing is scheduled across this point: left to itself the compiler sinks a batch's loads to just above its wait)
     if (BATCH) { z5 = draw(false); __builtin_amdgcn_sched_barrier(0); }
@@ -1126,6 +1177,11 @@ __device__ __forceinline__ void llgs_lane_attempt(LlgsLane& L, LlgsMasks& M, V3&
                    y.y + h * (k1.y * B1 + k3.y * B3 + k4.y * B4 + k5.y * B5 + k6.y * B6),
                    y.z + h * (k1.z * B1 + k3.z * B3 + k4.z * B4 + k5.z * B5 + k6.z * B6)};
     const V3 f_new = fun(y_new, z7, on_end);
+    // (shared source: the next attempt's z2 / z3 close this chunk; fetched here, the error norm and the step-size controller -- one long
+    // dependency chain -- ahead of their use: at the top of the next attempt their LDS latency would stand behind that chain.  Not earlier:
+    // under the last RHS call, with z7 and k1 ... k6 live, twelve more registers do not fit)
+    V3 z2n{0.0, 0.0, 0.0}, z3n{0.0, 0.0, 0.0};
+    if constexpr (BATCH) { z2n = draw(true); z3n = draw(false); __builtin_amdgcn_sched_barrier(0); }
     const V3 ev{(k1.x * E1 + k3.x * E3 + k4.x * E4 + k5.x * E5 + k6.x * E6 + f_new.x * E7) * h,
                 (k1.y * E1 + k3.y * E3 + k4.y * E4 + k5.y * E5 + k6.y * E6 + f_new.y * E7) * h,
                 (k1.z * E1 + k3.z * E3 + k4.z * E4 + k5.z * E5 + k6.z * E6 + f_new.z * E7) * h};
@@ -1161,6 +1217,7 @@ __device__ __forceinline__ void llgs_lane_attempt(LlgsLane& L, LlgsMasks& M, V3&
     M.pacc = accm;
     // (the one-env-per-lane loops take the lanes that have arrived out of M.active themselves: attempt_loop_next)
     if (!UNIFORM_IT) M.active &= __ballot(L.t != T);
+    if constexpr (BATCH) { z2 = z2n; z3 = z3n; }
 }
 
 // end of a solve: the final row (the input row when the solve failed), accepted points, attempts
@@ -1188,7 +1245,7 @@ __device__ __forceinline__ SolveOut llgs_solve(const V3& m0, double J, double T,
     LlgsLane L;
     V3 out_m = m0;
     llgs_lane_begin<THERMAL, RECORD, AXIS_Z>(L, out_m, m0, J, T, k, beta, betap, rtol, atol, max_step, rk, rec, ek, ns, enabled);
-    // SharedNormals: the prologue's two RHS calls were chunk 0; every attempt is one further chunk and the loop is
+    // SharedNormals: the prologue's two RHS calls opened chunk 0; every attempt meets one further chunk and the loop is
     // wave-uniform (a finished lane idles until the wavefront's last lane is through)
     LlgsMasks M = llgs_masks_open(L);
     atol = vgpr_const(atol);        // (read next to rtol in one instruction, which takes a single scalar operand: no copy per attempt)
@@ -1197,16 +1254,19 @@ __device__ __forceinline__ SolveOut llgs_solve(const V3& m0, double J, double T,
     asm volatile("" : "+s"(budget));        // (held in a register: as a kernel argument it may be loaded again inside the loop)
     int32_t it = 0;
     bool wave_go = M.active != 0ull;
+    // (shared source: publishes whether there is a first attempt; a 0 closes the solve here, a 1 is met inside attempt 1)
     if (NSRC::kShared) wave_go = ns.chunk_end_wave(wave_go);
+    // (shared source: the first two fields of an attempt are the tail of the chunk before it -- attempt 1's of chunk 0, which H2 certified;
+    // every attempt fetches the next one's itself, see llgs_lane_attempt)
+    V3 z2 = zero, z3 = zero;
+    if constexpr (THERMAL && NSRC::kShared) {
+        if (wave_go) { ns.seek_tail(); z2 = llgs_draw<THERMAL>(ns, k, true); z3 = llgs_draw<THERMAL>(ns, k, false); }
+    }
     if (wave_go)
     for (;;) {
       // The loop is wave-uniform and its body has no lane-divergent control flow (see llgs_lane_attempt).  (The
       // lane-divergent form -- break per lane, exec-masked body -- spent as long on its mask bookkeeping at the top of every
       // iteration as on one RHS.)
-      // (shared source: the first two fields of the attempt are fetched before anything else, their LDS latency runs
-      // under the step-size bookkeeping)
-      V3 z2 = zero, z3 = zero;
-      if (THERMAL && NSRC::kShared) { z2 = llgs_draw<THERMAL>(ns, k, true); z3 = llgs_draw<THERMAL>(ns, k, false); }
       // (should the gate stop the wavefront's last lanes, one attempt runs with nobody active before the test below ends the loop: its
       // selects freeze every lane, counters included)
       llgs_lane_gate<true>(L, M, budget);
