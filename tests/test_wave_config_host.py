@@ -7,6 +7,7 @@ itself pinned here.
     values -- the Ornstein-Uhlenbeck branch, which the reference solvers do not have, is anchored this way;
   * tests/wave_step_ref.py under the non-default episode configuration against the env steps of G24, and its SOT and VCMA resistance
     forms against oracle.resistance;
+  * the builder of the knots cases (tests/test_gpu_knots_config.py) against the shaped case, bit for bit;
   * what G24 holds."""
 import numpy as np
 import pytest
@@ -122,6 +123,33 @@ def test_resistance_forms_are_the_oracles(oracle_mod):
         assert np.all(np.abs(got - want) <= 4e-16 * np.abs(want)), (dtype, np.abs(got - want).max())
     three = [wave_step_ref.resistance(m, p, t) for t, p in zip(wcc.DEV_TYPES, wcc.class_table(False))]
     assert not np.allclose(three[0], three[1]) and not np.allclose(three[0], three[2])
+
+
+@pytest.mark.parametrize("method,noise", wcc.SHAPED_DIRECT)
+def test_knots_builder_reproduces_the_shaped_case_bit_for_bit(oracle_mod, method, noise):
+    """wave_config_cases.with_knots / run_knots_ref against shaped_ref: a knots problem whose knot times are the shape's, whose
+    amplitudes are the shape's values in every env and at every step, and whose limit does not clip them is the shaped problem, and the
+    restatement must give it the same rows, bit for bit.  (float64 actions that hold the float32 (J, T) widened, which parse to the same
+    values: a float32 action cannot carry the value -0.15.)"""
+    s, want = wcc.shaped_ref(method, noise, oracle_mod)
+    assert s["acts"].dtype == np.float32
+    amp = np.broadcast_to(s["shape"].values, s["acts"].shape[:2] + (len(s["shape"].values),))
+    acts = np.concatenate([s["acts"].astype(np.float64), amp], axis=2)
+    p = wcc.with_knots(s, s["shape"].times, 1.0, acts)
+    for k in range(wcc.K_SHAPED):
+        assert np.array_equal(p["cur"][k][0], s["cur"][k][0]) and np.array_equal(p["cur"][k][1], s["cur"][k][1]), k
+    got = wcc.run_knots_ref(p, method, noise, oracle_mod)
+    for k, (a, b) in enumerate(zip(got, want)):
+        assert sorted(a) == sorted(b)
+        for key in a:
+            assert a[key].dtype == b[key].dtype and np.array_equal(a[key].view(np.uint8), b[key].view(np.uint8)), (method, noise, k, key)
+    # and the committed knots case is built by the same two functions from the same shaped problem
+    q, _ = wcc.knots_ref(method, noise, oracle_mod)
+    base = wcc.shaped_problem(method, noise, False, wcc.KNOTS_SEED)
+    assert np.array_equal(q["acts"][:, :, :2], base["acts"]) and repr(q["cfg"]) == repr(base["cfg"]) and repr(q["plist"]) == repr(base["plist"])
+    for key in base["state"]:
+        assert np.array_equal(q["state"][key], base["state"][key]), key
+    assert np.array_equal(q["fk"][0], base["fk"][0]) and np.array_equal(q["fk"][1], base["fk"][1]) and np.array_equal(q["cls"], base["cls"])
 
 
 def test_old_arguments_give_old_results():

@@ -1,5 +1,5 @@
-"""Cases, inputs and restatement answers shared by test_gpu_wave_config.py (the waveform kernels against tests/waveform_ref.py /
-tests/wave_step_ref.py, `-m gpu`) and test_wave_config_conditioning.py (the restatement against itself, CPU): one definition, so that the
+"""Cases, inputs and restatement answers shared by test_gpu_wave_config.py and test_gpu_knots_config.py (the waveform kernels against
+tests/waveform_ref.py / tests/wave_step_ref.py, `-m gpu`) and test_wave_config_conditioning.py (the restatement against itself, CPU): one definition, so that the
 conditioning test sees exactly the inputs the GPU tests use.
 
 Everything runs away from the defaults: max_step in FIXED_MAX_STEPS, gamma 1.9e5 / 2.5e5, temperatures 77 / 450 K, the thermal field off,
@@ -11,7 +11,14 @@ Durations are chosen so that max_step decides the sub-step count: with max_step 
 200); with 2.5e-12 and 1e-10, T / 100 is below them but above the default 1e-12 (n = 100, where a solver stuck at the default would take
 up to 160).  The thermal cases use volume 1e-26 with currents scaled by the volume ratio (tests/golden/make_golden_wave_config.py says
 why): there the thermal field moves m by 1e-7 ... 1e-5, far above the tolerance, so a field that is dropped, misplaced or decayed
-with the wrong dt shows."""
+with the wrong dt shows.
+
+The knots cases (knots_problem, knots_ref; tests/test_gpu_knots_config.py) are the shaped cases with the fixed shape replaced by actions
+[J, T, s_0 ... s_4] that carry the knot amplitudes: the configuration, the class table, the start state, the field knots and the
+(J, T) rows are shaped_problem's, to which come five knot times, the amplitude limit KNOT_LIMIT = 0.25 and amplitudes drawn in
++-1.6 KNOT_LIMIT, so that the clamp works on three amplitudes in eight.  The restatement's answer is wave_step_ref.step under the tables
+tests/knots_ref.py builds from the parsed actions (with_knots, run_knots_ref); tests/test_wave_config_host.py pins these two functions
+against shaped_ref, tests/test_wave_config_conditioning.py checks the conditioning of the cases and that they are not vacuous."""
 import itertools
 
 import numpy as np
@@ -305,6 +312,76 @@ def shaped_ref(method, noise, oracle, ulp=False):
         state = dict(m=r["m"], target=state["target"], total_energy=r["total_energy"], step_count=r["step_count"])
     SHAPED_REF[key] = (s, refs)
     return SHAPED_REF[key]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# stg_step_knots: one launch of K_SHAPED steps whose actions [J, T, s_0 ... s_4] carry the knot amplitudes
+# ---------------------------------------------------------------------------------------------------------------------
+P_KNOTS = 5
+# (at most a quarter, for the reason shaped_problem gives: three steps chain, and the spin torque amplifies a perturbation exponentially
+# in J t)
+KNOT_LIMIT = 0.25
+KNOTS_SEED = 7300
+
+
+def knots_problem(solver, noise, f64, seed):
+    """shaped_problem(solver, noise, f64, seed) -- its configuration, class table, start state, field knots and (J, T) rows -- with the
+    fixed shape replaced by P_KNOTS knot times tau (0, three sorted draws in (0.05, 0.95), 1), the limit KNOT_LIMIT and amplitudes drawn
+    uniform in +-1.6 KNOT_LIMIT per env and per step (three in eight beyond the limit: the clamp is at work), from generator seed + 1.
+    acts [K_SHAPED, N, 2 + P_KNOTS] float32 or float64; cur: the knots (tau_j T, J s_j) of each step's parsed action."""
+    s = shaped_problem(solver, noise, f64, seed)
+    rng = np.random.default_rng(seed + 1)
+    tau = np.concatenate([[0.0], np.sort(rng.uniform(0.05, 0.95, P_KNOTS - 2)), [1.0]])
+    assert (np.diff(tau) > 0).all()
+    amp = rng.uniform(-1.6, 1.6, (K_SHAPED, N, P_KNOTS)) * KNOT_LIMIT
+    acts = np.concatenate([s["acts"].astype(np.float64), amp], axis=2)
+    if f64:
+        assert np.all(amp.astype(np.float32).astype(np.float64) != amp)
+    else:
+        acts = acts.astype(np.float32)                     # (the (J, T) columns were float32 already)
+    return with_knots(s, tau, KNOT_LIMIT, acts)
+
+
+def with_knots(s, tau, limit, acts):
+    """the shaped problem s under knot times tau, the amplitude limit and knot actions acts [K_SHAPED, N, 2 + P] instead of its shape"""
+    import knots_ref as kr
+    p = {k: v for k, v in s.items() if k != "shape"}
+    cfg = s["cfg"]
+    cur = [kr.knot_tables_np(tau, *kr.parse_np(acts[k], cfg["max_current"], cfg["max_duration"], limit)) for k in range(K_SHAPED)]
+    return dict(p, tau=np.asarray(tau, dtype=np.float64), limit=float(limit), acts=acts, cur=cur)
+
+
+def run_knots_ref(p, method, noise, oracle, ulp=False):
+    """the restatement's K_SHAPED steps of a knots problem: wave_step_ref.step under each step's tables p['cur'][k], the (J, T) rows
+    through knots_ref.wave_rows, the field table replicated and the thermal stream keyed as in shaped_ref"""
+    import knots_ref as kr
+    n, cfg = N, p["cfg"]
+    state, refs = dict(p["state"]), []
+    if ulp:
+        state["m"] = ulp_moved(state["m"])
+    fld = (np.tile(p["fk"][0], (n, 1)), np.tile(p["fk"][1], (n, 1, 1)))
+    for k in range(K_SHAPED):
+        th = dict(oracle=oracle, seed=SEED, env_id0=ENV_ID0, rng_step=np.full(n, k), noise=noise, corr_time=CORR_TIME) if noise else None
+        r = wave_step_ref.step(state, kr.wave_rows(p["acts"][k]), p["plist"], method, current=p["cur"][k], field=fld,
+                               cfg=cfg, cls=p["cls"], dev_types=DEV_TYPES, thermal=th)
+        refs.append(r)
+        state = dict(m=r["m"], target=state["target"], total_energy=r["total_energy"], step_count=r["step_count"])
+    return refs
+
+
+KNOTS_REF = {}
+
+
+def knots_ref(method, noise, oracle, ulp=False):
+    """the inputs of a direct knots case and the restatement's K_SHAPED steps, computed once and shared"""
+    key = (method, noise, ulp)
+    if key not in KNOTS_REF:
+        p = knots_problem(method, noise, False, KNOTS_SEED)
+        refs = run_knots_ref(p, method, noise, oracle, ulp)
+        for r in refs:
+            assert (np.abs(r["alignment"] - p["cfg"]["success_threshold"]) > 1e-6).all()        # no flag rests on rounding
+        KNOTS_REF[key] = (p, refs)
+    return KNOTS_REF[key]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
