@@ -112,8 +112,20 @@ typedef struct {
                                        1 = Ornstein-Uhlenbeck, the reference's ThermalFluctuations model
                                        (physics/thermal_model.py:113-137): once per sub-step
                                        x <- d x + sqrt(1 - d^2) xi, d = exp(-dt / noise_corr_time), field = strength * x
-                                       for all stages of the sub-step, x = 0 at the start of every pulse.
-                                       Not available with STG_SOLVER_RK45 (no fixed dt). */
+                                       for all stages of the sub-step, x = 0 at the start of every pulse;
+                                       2 = Brown's field with the 1/sqrt(dt) factor that the reference's lacks:
+                                       per solve c = 1.0 / sqrt(dt) (IEEE square root, then IEEE division; dt as the solver
+                                       forms it, = max_step in the usual case), per sub-step i one draw xi_i of three
+                                       standard normals, taken from the env's stream exactly as model 1 takes its draw (same
+                                       key, call index i, phase alternation and stream position), x_i = c * xi_i (one rounded
+                                       product per component, nothing carried between sub-steps), field = strength * x_i
+                                       for all stages of the sub-step -- the recurrence of model 1 with d = 0, w = c.
+                                       `strength` is what stg_thermal_strength returns (dt-free, as for models 0 and 1), so
+                                       the field's standard deviation per component is strength / sqrt(dt).  With RK4 the
+                                       equilibrium is Boltzmann's to about 2e-3 in <m_z^2> at dt = 1 ps; Euler converges
+                                       at first order only (<m_z^2> = 0.48 against 0.705 at Delta = 4, dt = 1 ps): use RK4.
+                                       noise_corr_time is ignored.
+                                       Models 1 and 2 are not available with STG_SOLVER_RK45 (no fixed dt). */
     int32_t out_layout;             /* layout of a step's RL-facing outputs (obs, reward, terminated, truncated):
                                        STG_OUT_SOA (0, default): four caller arrays, obs component-major float[12][N];
                                        STG_OUT_RECORDS (1): ONE array of STG_RECORD_BYTES-byte records, env index major --

@@ -397,7 +397,7 @@ static CfgView cfg_view(const stg_config& c) {
     v.temperature = c.temperature; v.max_step = c.max_step; v.rtol = c.rtol; v.atol = c.atol;
     v.max_current = c.max_current; v.max_duration = c.max_duration; v.thr = c.success_threshold;
     v.w_energy = c.energy_penalty_weight;
-    v.inv_tau = (c.noise_model == 1 && c.solver != STG_SOLVER_RK45) ? 1.0 / c.noise_corr_time : 0.0;
+    v.inv_tau = c.solver == STG_SOLVER_RK45 ? 0.0 : (c.noise_model == 1 ? 1.0 / c.noise_corr_time : (c.noise_model == 2 ? -1.0 : 0.0));
     v.temp_norm = c.temperature / 300.0; v.inv_max_current = 1.0 / c.max_current; v.inv_max_duration = 1.0 / c.max_duration;
     std::memcpy(v.targets, c.targets, sizeof(v.targets));
     v.seed = c.seed; v.max_attempts = c.max_attempts; v.max_steps = c.max_steps; v.n_targets = c.n_targets;
@@ -413,8 +413,9 @@ static int check_cfg(const stg_config* c) {
     if (c->max_steps < 1) return fail(STG_E_INVALID, "cfg.max_steps must be >= 1");
     if (!(c->max_current > 0) || !(c->max_duration > 0)) return fail(STG_E_INVALID, "cfg.max_current/max_duration must be positive");
     if (c->solver == STG_SOLVER_RK45 && (!(c->rtol > 0) || !(c->atol >= 0))) return fail(STG_E_INVALID, "cfg.rtol/atol invalid");
-    if (c->noise_model != 0 && c->noise_model != 1) return fail(STG_E_INVALID, "cfg.noise_model must be 0 (white) or 1 (Ornstein-Uhlenbeck)");
+    if (c->noise_model < 0 || c->noise_model > 2) return fail(STG_E_INVALID, "cfg.noise_model must be 0 (white), 1 (Ornstein-Uhlenbeck) or 2 (Brown, 1/sqrt(dt))");
     if (c->noise_model == 1 && c->solver == STG_SOLVER_RK45) return fail(STG_E_INVALID, "cfg.noise_model = 1 needs a fixed-step solver (RK4 or Euler)");
+    if (c->noise_model == 2 && c->solver == STG_SOLVER_RK45) return fail(STG_E_INVALID, "cfg.noise_model = 2 needs a fixed-step solver (RK4 or Euler)");
     if (c->noise_model == 1 && !(c->noise_corr_time > 0)) return fail(STG_E_INVALID, "cfg.noise_corr_time must be positive");
     // (the kernels count attempts in 32 bits)
     if (c->solver == STG_SOLVER_RK45 && (c->max_attempts < 1 || c->max_attempts > INT32_MAX)) return fail(STG_E_INVALID, "cfg.max_attempts must be in 1 ... 2^31 - 1");

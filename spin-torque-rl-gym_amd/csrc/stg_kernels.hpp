@@ -37,7 +37,8 @@ struct StateView {
 struct CfgView {
     double temperature, max_step, rtol, atol, max_current, max_duration, thr, w_energy;
     double temp_norm, inv_max_current, inv_max_duration;   // temperature/300, 1/max_current, 1/max_duration (observation)
-    double inv_tau;               // 1/noise_corr_time when the Ornstein-Uhlenbeck field is selected, else 0 (white field)
+    double inv_tau;               // 1/noise_corr_time when the Ornstein-Uhlenbeck field is selected, negative for the Brown field
+                                  // (noise_model 2: the same recurrence with d = 0, w = 1/sqrt(dt)), else 0 (white field)
     double targets[STG_MAX_TARGETS][3];
     uint64_t seed;
     int64_t max_attempts;

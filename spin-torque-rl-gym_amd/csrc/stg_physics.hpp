@@ -777,13 +777,19 @@ __device__ __forceinline__ SolveOut simple_solve(const V3& m0, double J, double 
     if (THERMAL) ns.begin(rk);
     // Ornstein-Uhlenbeck field (ThermalFluctuations._generate_correlated_noise, thermal_model.py:113-137), selected by a
     // wave-uniform inv_tau > 0: one update per sub-step, x <- d x + sqrt(1 - d^2) xi with d = exp(-dt/tau), and the same
-    // x for every stage of the sub-step; the stream hands out three normals per sub-step, alternating phase like Euler's
-    const bool ou_sel = THERMAL && inv_tau > 0.0;
+    // x for every stage of the sub-step; the stream hands out three normals per sub-step, alternating phase like Euler's.
+    // inv_tau < 0 is the Brown field with the 1/sqrt(dt) factor (cfg.noise_model = 2): the same recurrence with d = 0 and
+    // w = 1/sqrt(dt), so x = w xi exactly and nothing is carried from sub-step to sub-step
+    const bool ou_sel = THERMAL && inv_tau != 0.0;
     double ou_d = 0.0, ou_c = 1.0;
     V3 ou_x = zero;
     if (ou_sel) {
-        ou_d = exp(-dt * inv_tau);
-        ou_c = sqrt(1.0 - ou_d * ou_d);
+        if (inv_tau > 0.0) {
+            ou_d = exp(-dt * inv_tau);
+            ou_c = sqrt(1.0 - ou_d * ou_d);
+        } else {
+            ou_c = 1.0 / sqrt(dt);
+        }
     }
     if (RECORD) rec.put(0, 0.0, m, 0.0);
     // per-lane trip count n; with SharedNormals the loop is wave-uniform (lanes past their n idle inside the body).

@@ -286,12 +286,16 @@ __device__ __forceinline__ SolveOut simple_solve_wave(const V3& m0, double T, co
     bool fail = false;
     const V3 zero{0.0, 0.0, 0.0};
     if (THERMAL) ns.begin(rk);
-    const bool ou_sel = THERMAL && inv_tau > 0.0;          // Ornstein-Uhlenbeck field: see simple_solve
+    const bool ou_sel = THERMAL && inv_tau != 0.0;         // Ornstein-Uhlenbeck field, or (inv_tau < 0) the Brown field: see simple_solve
     double ou_d = 0.0, ou_c = 1.0;
     V3 ou_x = zero;
     if (ou_sel) {
-        ou_d = exp(-dt * inv_tau);
-        ou_c = sqrt(1.0 - ou_d * ou_d);
+        if (inv_tau > 0.0) {
+            ou_d = exp(-dt * inv_tau);
+            ou_c = sqrt(1.0 - ou_d * ou_d);
+        } else {
+            ou_c = 1.0 / sqrt(dt);
+        }
     }
     // The drive of one stage time: the Slonczewski term is on iff |current| > 1e-12 there (simple_solver.py:326,330).  The quotient
     // (P current) / (Ms V) is a product with 1 / (Ms V), formed once: an IEEE division per stage costs about as much as half an RHS, and

@@ -19,6 +19,7 @@ STG_NPARAM = 30          # double-valued fields of stg_device_params, in declara
 SOLVERS = {"rk4": 0, "euler": 1, "rk45": 2}
 DEV_TYPES = {"stt_mram": 0, "sot_mram": 1, "vcma_mram": 2}
 OUT_LAYOUTS = {"soa": 0, "records": 1}
+NOISE_MODELS = {"white": 0, "ou": 1, "brown": 2}       # stg_config.noise_model
 RECORD_BYTES = 56        # STG_RECORD_BYTES
 STATUS_OK, STATUS_NOOP, STATUS_RESET, STATUS_INACTIVE, STATUS_BAD_ID = 0, 1, 2, 3, 4
 STG_OK, STG_E_INVALID, STG_E_HIP, STG_E_NOMEM, STG_E_STATE = 0, -1, -2, -3, -4

@@ -37,7 +37,8 @@ class EnvConfig:
     torque_model: str = "reference"           # 'reference' (the env's type-agnostic RHS) | 'device' (opt-in)
     lane_sort: Optional[bool] = None          # duration-sorted lane schedule: None = automatic, True/False = force
     wave_spec: Optional[bool] = None          # producer/consumer wavefront pairs (thermal): None = automatic
-    noise_model: str = "white"                # 'white' (reference solvers) | 'ou' (ThermalFluctuations, fixed-step only)
+    noise_model: str = "white"                # 'white' (reference solvers) | 'ou' (ThermalFluctuations) | 'brown' (the physical field:
+                                              # standard deviation strength / sqrt(dt) per component); 'ou', 'brown': fixed-step only
     correlation_time: float = 1e-12           # ThermalFluctuations.correlation_time, for noise_model='ou'
     out_layout: str = "soa"                   # 'soa': obs [12,N] + reward/terminated/truncated arrays; 'records': one
                                               # [N,56]-byte record array (what the multi-GPU gather moves, copy-free)
@@ -75,9 +76,11 @@ class EnvConfig:
         c.torque_model = int(self.torque_model == "device")
         c.lane_sort = 0 if self.lane_sort is None else (1 if self.lane_sort else -1)
         c.wave_spec = 0 if self.wave_spec is None else (1 if self.wave_spec else -1)
-        if self.noise_model not in ("white", "ou"):
-            raise ValueError("noise_model must be 'white' or 'ou'")
-        c.noise_model = int(self.noise_model == "ou")
+        if self.noise_model not in _lib.NOISE_MODELS:
+            raise ValueError(f"noise_model must be one of {list(_lib.NOISE_MODELS)}")
+        if self.noise_model == "brown" and self.solver == "rk45":
+            raise ValueError("noise_model='brown' needs a fixed-step solver ('rk4' or 'euler'): an adaptive step has no fixed dt")
+        c.noise_model = _lib.NOISE_MODELS[self.noise_model]
         c.noise_corr_time = float(self.correlation_time)
         if self.out_layout not in _lib.OUT_LAYOUTS:
             raise ValueError("out_layout must be 'soa' or 'records'")

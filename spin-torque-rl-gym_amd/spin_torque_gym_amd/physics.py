@@ -166,8 +166,11 @@ class _GpuSolverBase:
     _solver_name = "rk4"
     _validate_params = False        # (RobustLLGSSolver turns the parameter gate on)
 
-    def __init__(self, rtol, atol, max_step, gamma=2.21e5, device_index=0, backend=None, seed=0):
+    def __init__(self, rtol, atol, max_step, gamma=2.21e5, device_index=0, backend=None, seed=0, noise_model="white",
+                 correlation_time=1e-12):
         self.rtol, self.atol, self.max_step, self.gamma = rtol, atol, max_step, gamma
+        # thermal field of the fixed-step solvers (EnvConfig.noise_model): 'white', 'ou' (with correlation_time) or 'brown'
+        self.noise_model, self.correlation_time = noise_model, correlation_time
         self.mu_0 = MU0
         self.device_index = device_index
         self._backend_factory = HipBackend if backend is None else backend
@@ -177,7 +180,7 @@ class _GpuSolverBase:
     def _backend(self, n, device_params, device_type, thermal_noise, temperature):
         cfg = EnvConfig(solver=self._solver_name, include_thermal_fluctuations=bool(thermal_noise),
                         temperature=float(temperature), gamma=self.gamma, max_step=self.max_step, rtol=self.rtol,
-                        atol=self.atol, seed=self._seed)
+                        atol=self.atol, seed=self._seed, noise_model=self.noise_model, correlation_time=self.correlation_time)
         b = self._backend_factory(n, cfg, self.device_index, 0)
         b.set_params([_flat_for(device_params, device_type, self._validate_params)])
         return b
@@ -278,6 +281,45 @@ class SimpleLLGSSolver(_GpuSolverBase):
         return {"t": r["t"][:k, 0], "m": r["m"][:k, 0, :], "success": True,
                 "message": "Integration completed successfully", "solve_time": 0.0, "n_steps": k - 1}
 
+    def switching_probability(self, m_initial, current, duration, device_params: Dict[str, Any], n_trials: int,
+                              target=(0.0, 0.0, -1.0), threshold: float = 0.0, temperature: float = 300.0,
+                              device_type: str = "stt_mram", env_step: int = 0, current_knots=None, field_knots=None) -> Dict[str, Any]:
+        """Monte-Carlo switching probability of G conditions -- the rows of m_initial [G,3], current [G], duration [G] -- with
+        R = n_trials thermal trials each, as ONE solve launch over the G R replicated problems: problem g R + r is trial r of
+        condition g and has its own normal stream through its problem index.  A trial counts as switched when
+        m_final . target > threshold (a failed solve hands back m_initial and is counted by that rule like any other; n_failed says
+        how many there were).  The counts are reduced on the device; no per-trial array reaches the host.  Knots as in solve_batch,
+        one table for all conditions ([K]) or one per condition ([K,G]).  Returns dict(p_switch [G] = n_switched / R, n_switched [G],
+        n_failed [G], stderr [G] = sqrt(p (1 - p) / R)).  The thermal field is on; choose its model with the constructor's
+        noise_model ('brown' is the one whose field can switch a device, see include/spintorque_hip.h)."""
+        m0 = torch.as_tensor(np.asarray(m_initial, dtype=np.float64) if not torch.is_tensor(m_initial) else m_initial).reshape(-1, 3)
+        g, r = int(m0.shape[0]), int(n_trials)
+        if r < 1:
+            raise ValueError("n_trials must be >= 1")
+        wave = None
+        if current_knots is not None or field_knots is not None:
+            wave = {"current": _knot_tables(current_knots, g, 1, "current_knots"), "field": _knot_tables(field_knots, g, 3, "field_knots")}
+            wave = {k: None if v is None else tuple(torch.from_numpy(a).repeat_interleave(r, dim=-1) for a in v) for k, v in wave.items()}
+        if current is None:
+            if current_knots is None:
+                raise ValueError("current is required without current_knots")
+            current = np.zeros(g)
+        rep = lambda x: torch.as_tensor(x, dtype=torch.float64).reshape(g).repeat_interleave(r)          # noqa: E731
+        b = self._backend(g * r, device_params, device_type, True, temperature)
+        try:
+            out = b.solve(m0.to(torch.float64).repeat_interleave(r, dim=0).t().contiguous(), rep(current), rep(duration),
+                          env_step=env_step, **({} if wave is None else {"wave": wave}))
+            mf = out["m_final"]                                          # [3, G R], on the backend's device
+            tx, ty, tz = (float(x) for x in np.asarray(target, dtype=np.float64).reshape(3))
+            proj = mf[0] * tx + mf[1] * ty + mf[2] * tz
+            counts = torch.stack([(proj > float(threshold)).reshape(g, r).sum(1), (out["success"] == 0).reshape(g, r).sum(1)]).cpu().numpy()
+        finally:
+            b.close()
+        self.solve_count += g * r
+        n_sw, n_failed = counts[0].astype(np.int64), counts[1].astype(np.int64)
+        p = n_sw / r
+        return {"p_switch": p, "n_switched": n_sw, "n_failed": n_failed, "stderr": np.sqrt(p * (1.0 - p) / r)}
+
     def get_solver_info(self):
         return {"method": self.method, "solve_count": self.solve_count, "timeout_count": 0, "last_solve_time": 0.0,
                 "timeout_rate": 0.0, "avg_solve_time": 0.0}
@@ -324,6 +366,8 @@ class LLGSSolver(_GpuSolverBase):
                  gamma: float = 2.21e5, **kw):
         if method != "RK45":
             raise NotImplementedError(f"method '{method}': the GPU path implements SciPy's RK45 (Dormand-Prince 5(4))")
+        if kw.get("noise_model", "white") != "white":
+            raise ValueError("LLGSSolver (RK45) has the white thermal field only: 'ou' and 'brown' need a fixed dt (SimpleLLGSSolver)")
         super().__init__(rtol, atol, max_step, gamma, **kw)
         self.method = method
         self.k_b = 1.380649e-23
