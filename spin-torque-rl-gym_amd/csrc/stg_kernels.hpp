@@ -977,6 +977,9 @@ stg_step_kernel(const StepArgs a) {
             __syncthreads();                                       // H1
             if ((WGW == 1) ? mine : any_flag<WGW>(lds_flag(s_go + p))) {
                 if (!BARRIER) s_hs[1] = 0;                         // (the producer is past its last read of the previous solve's value: H1)
+                // (RK45 ring: both copies of the continue flag say 1 for the whole solve but its end; the producer's last read of the
+                // previous solve's copies lies before H1, its first read of these behind the solve's first rendezvous after H2)
+                if constexpr (BARRIER && FIELD) SharedNormalsT<NT, FIELD, DEPTH, BARRIER>::open(s_hs, lane);
                 __syncthreads();                                   // H2
                 so = run_solver<SOLVER, THERMAL, false, AXIS_Z, DEVPHYS>(m, J, T, row, a.c, rk, norec, shared, lane_solves);
             }

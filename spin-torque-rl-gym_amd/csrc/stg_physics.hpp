@@ -343,7 +343,7 @@ struct RngKey {
 //    PC_STOP ends the producer's loop, and a poll budget (PC_SPIN_CAP, ~1 s) turns a protocol error into a failed
 //    solve instead of a hung GPU.  (For RK45 and Euler this form measured 5-10 % slower than the barrier.)
 struct InlineNormals {
-    static constexpr bool kShared = false, kScaled = false;
+    static constexpr bool kShared = false, kScaled = false, kToggle = false;
     NormalStream ns;
     __device__ __forceinline__ void begin(const RngKey& rk) { ns.init(rk.seed, rk.env_id, rk.env_step, 0u); }
     __device__ __forceinline__ V3 draw(bool even) { return even ? ns.draw3_even() : ns.draw3_odd(); }
@@ -400,21 +400,31 @@ __device__ __forceinline__ void pc_store(int* p, int v) {
 // so that the rendezvous for chunk c stands INSIDE attempt c, between the RHS call that consumed z2 and the fetch of z4 (chunk_meet),
 // where nothing of the pair's is in flight, instead of at the loop's back edge, where the flag's LDS write, the barrier and the fetch of
 // z2 / z3 were serial with the step-size controller's dependency chain.  z2 / z3 of attempt c + 1 are fetched under the last RHS call of
-// attempt c.  Flag copy c & 1 says whether there is an attempt c + 1; it is written when that is known (before the loop for c = 0, at the
-// end of attempt c otherwise: chunk_end_go) and no rendezvous follows a 1 -- the one that publishes it is chunk_meet of attempt c + 1 --
-// while a 0 is followed by the closing rendezvous at once.
+// attempt c.
+// The continue flag: two copies, written TWICE per solve.  open() sets both to 1, between the env-step's H1 and H2 (stg_step_kernel); the
+// loop writes nothing; after a solve of n attempts (0 included) close() writes 0 to copy n & 1 and passes the closing rendezvous.
 // Rendezvous per solve, integrating wavefront: H2, then for a solve of n attempts chunk_meet in each of them, then the closing one:
 //   n = 0: H2 + 1 (flag copy 0 = 0, closing)        n = 1: H2 + 2 (meet in attempt 1; flag copy 1 = 0, closing)        n: H2 + n + 1.
-// Producer (produce_normals): H2, then per round k = 1, 2, ...: fill chunk k, rendezvous, read flag copy (k - 1) & 1, return on 0.  Its
-// round k rendezvous is chunk_meet of attempt k if there is one -- then flag copy (k - 1) & 1 was written 1 at the end of attempt k - 1,
-// before that barrier, and it goes on -- and the closing one if k = n + 1 -- flag copy n & 1 is 0 and it returns: H2 + n + 1 as well, for
-// n = 0 (one round), n = 1 (two rounds) and any n.  With K fused env-steps every env-step adds H1 (stg_step_kernel) on both sides and,
-// where the wavefront integrates at all, one such solve: K * H1 + sum over those env-steps of (H2 + n_k + 1) on both sides.
+// Producer (produce_normals): H2, then per round k = 1, 2, ...: fill chunk k, rendezvous k, read flag copy (k - 1) & 1, return on 0.  Its
+// rendezvous k is chunk_meet of attempt k for k <= n and the closing one for k = n + 1: H2 + n + 1 as well, IF it reads 1 in rounds
+// 1 ... n and 0 in round n + 1.  Why one zero per solve is enough:
+//   - the only 0 of a solve goes to copy n & 1, after rendezvous n (the integrating wavefront is behind chunk_meet of attempt n, or
+//     behind H2 for n = 0) and before the closing rendezvous n + 1;
+//   - round n + 1 reads copy n & 1 behind rendezvous n + 1: the 0, and the producer returns;
+//   - round n reads the OTHER copy, (n - 1) & 1, which nothing has written since open(): 1;
+//   - round n - 1 read copy (n - 2) & 1 = n & 1 BEFORE the producer went on to rendezvous n, hence before the 0 was written: 1; every
+//     earlier round likewise reads a copy that open() wrote last.
+//   - open(): the producer's last read of the previous solve's copies (its round n + 1) lies before it arrives at this env-step's H1, and
+//     its first read of this solve's lies behind rendezvous 1, which follows H2; the writes stand between H1 and H2.
+// So no copy is ever written by one wavefront and read by the other between the same two barriers (tests/test_clamp_gate_host.py models
+// the two wavefronts and checks exactly that, with the rendezvous counts, for n = 0 ... 5, fused env-steps, env-steps without a solve
+// and attempt budgets that end the loop early: the loop's exit by the budget is an exit after n attempts like any other).
+// With K fused env-steps every env-step adds H1 (stg_step_kernel) on both sides and, where the wavefront integrates at all, one such
+// solve: K * H1 + sum over those env-steps of (H2 + n_k + 1) on both sides.
 // What a barrier orders: slot k & 1 held chunk k - 2, whose last values (z2 / z3 of attempt k - 1) the integrating wavefront has waited for
 // (batch_ready) before rendezvous k - 1, after which the producer fills it; the producer's writes of chunk k precede rendezvous k, after
-// which the integrating wavefront reads it.  Flag copy c & 1 is rewritten at the end of attempt c + 2, behind rendezvous c + 2, which the
-// producer reaches only after it has read the copy in round c + 1.  When the solve ends the producer may have filled a chunk nobody
-// reads: a stream is re-seeded per (env, env-step).
+// which the integrating wavefront reads it.  When the solve ends the producer may have filled a chunk nobody reads: a stream is re-seeded
+// per (env, env-step).
 template <typename T, bool SCALED, int DEPTH, bool BARRIER>
 struct SharedNormalsT {
     static constexpr int CHUNK = SCALED ? SHARED_CHUNK_RK45 : SHARED_CHUNK_FIXED;    // (the RK45 kernels hand over finished fields)
@@ -424,17 +434,19 @@ struct SharedNormalsT {
     int* hs;                // LDS: the handshake words / BARRIER: the integrator's "continues" flag, two alternating copies
     int lane, it, idx, seen;   // seen: the producer's count as last read (a lane-uniform value in a VGPR)
     bool broken;               // the poll budget ran out (never, unless the protocol is broken): the solve reports failure
-    // The RK45 ring (a barrier per attempt, two slots): where the current slot starts and which flag copy is next are per-lane values that
-    // TOGGLE -- one v_xor_b32 each per attempt -- instead of being rebuilt from `it` (s_bitcmp1 / s_cselect / v_or and s_and / s_lshl / v_mov).
-    // They are BYTE offsets, so that the address needs no shift after the toggle.
+    // The RK45 ring (a barrier per attempt, two slots): where the current slot starts is a per-lane value that TOGGLES -- one v_xor_b32 per
+    // attempt -- instead of being rebuilt from `it` (s_bitcmp1 / s_cselect / v_or).  It is a BYTE offset, so that the address needs no shift
+    // after the toggle.  (The flag copies are not written per attempt: close.)
     static constexpr bool kToggle = BARRIER && SCALED;
-    int slot_b, flag_b;        // kToggle: byte offset of this lane in the current slot (lane, or CHUNK * 64 + lane, times sizeof(T)); 0 / 4
+    int slot_b;                // kToggle: byte offset of this lane in the current slot (lane, or CHUNK * 64 + lane, times sizeof(T))
+    int spare;                 // (unused: where the flag's offset stood.  The struct keeps its size, on which the register numbering of the
+                               // fixed-step pair kernels turned out to hang -- with it they are the machine code they were: tools/isa_identical.py)
     __device__ __forceinline__ void begin(const RngKey&) {
         it = 0; idx = 0; seen = 1; broken = false;                                                         // chunk 0 is there (H2)
         if (kToggle) {
             static_assert(((CHUNK * 64) & 63) == 0, "the slot bit and the lane bits are disjoint");
-            slot_b = lane * (int)sizeof(T); flag_b = 0;
-            asm volatile("" : "+v"(slot_b), "+v"(flag_b));        // (kept in VGPRs)
+            slot_b = lane * (int)sizeof(T);
+            asm volatile("" : "+v"(slot_b));        // (kept in a VGPR)
         }
     }
     __device__ __forceinline__ V3 draw(bool) {
@@ -449,6 +461,14 @@ struct SharedNormalsT {
         __syncthreads();
         slot_b ^= CHUNK * 64 * (int)sizeof(T);
         idx = 0;
+    }
+    // RK45 ring, the continue flag.  open: both copies say 1; the integrating wavefront writes them once per solve (lane l writes copy l & 1: one
+    // ds_write_b32), between the env-step's H1 and H2 (stg_step_kernel).  close: the solve made n attempts (0 included): copy n & 1 says 0, then the closing
+    // rendezvous.  Nothing else writes the copies.
+    static __device__ __forceinline__ void open(int* hs, int lane) { lds_flag(hs)[lane & 1] = 1; }
+    __device__ __forceinline__ void close(int32_t n) {
+        lds_flag(hs)[n & 1] = 0;
+        __syncthreads();
     }
     // (... and the read position of the chunk's last two fields, z2 / z3 of the next attempt; chunk 0 keeps them there too)
     __device__ __forceinline__ void seek_tail() { idx = CHUNK - SHARED_TAIL_RK45; }
@@ -466,14 +486,7 @@ struct SharedNormalsT {
     // branch a scalar compare, where a bool becomes a lane mask, a select and a mask test)
     __device__ __forceinline__ int32_t chunk_end_go(int32_t go) {
         const bool mine = go != 0;
-        if (kToggle) {
-            // RK45 ring: the flag is published here, the rendezvous that carries a 1 is the one INSIDE the next attempt (chunk_meet); a 0
-            // closes the solve at once
-            *(volatile lds_int*)((volatile __attribute__((address_space(3))) char*)lds_flag(hs) + flag_b) = go;
-            flag_b ^= (int)sizeof(int);
-            if (!mine) __syncthreads();
-            return go;
-        }
+        // (the RK45 ring, kToggle, publishes nothing per attempt and does not come here: open / close)
         if (BARRIER) {
             lds_flag(hs)[it & 1] = go;
             __syncthreads();
@@ -1114,6 +1127,18 @@ __device__ __forceinline__ int32_t attempt_loop_next(lanemask& active, lanemask 
         : "scc");
     return go;
 }
+// The same for a loop that needs the answer only as its own back edge (llgs_solve: nothing is published per attempt): three scalar
+// instructions leave the bound, and `it < bound` is the branch's own compare -- no 0/1 value is formed and tested again.
+__device__ __forceinline__ bool attempt_loop_more(lanemask& active, lanemask not_arrived, int32_t& it, int32_t budget) {
+    int32_t bound;
+    asm("s_add_i32 %[it], %[it], 1\n\t"
+        "s_and_b64 %[act], %[act], %[na]\n\t"
+        "s_cselect_b32 %[bd], %[bud], 0"
+        : [act] "+s"(active), [it] "+s"(it), [bd] "=&s"(bound)
+        : [na] "s"(not_arrived), [bud] "s"(budget)
+        : "scc");
+    return it < bound;
+}
 
 // ONE attempted step (rk.py:111-181) of a lane; the body has no lane-divergent control flow: a lane that is through (or
 // never started) walks along with its state frozen by the selects below.  SciPy nests "while not finished: step()" around
@@ -1260,8 +1285,10 @@ __device__ __forceinline__ SolveOut llgs_solve(const V3& m0, double J, double T,
     asm volatile("" : "+s"(budget));        // (held in a register: as a kernel argument it may be loaded again inside the loop)
     int32_t it = 0;
     bool wave_go = M.active != 0ull;
-    // (shared source: publishes whether there is a first attempt; a 0 closes the solve here, a 1 is met inside attempt 1)
-    if (NSRC::kShared) wave_go = ns.chunk_end_wave(wave_go);
+    // (shared source, fixed-step rings: publishes whether there is a first attempt.  The RK45 ring publishes nothing per attempt: its flag
+    // copies say 1 from before H2, and the ONE 0 of the solve follows the loop: close)
+    constexpr bool RING = NSRC::kShared && NSRC::kToggle;
+    if (NSRC::kShared && !RING) wave_go = ns.chunk_end_wave(wave_go);
     // (shared source: the first two fields of an attempt are the tail of the chunk before it -- attempt 1's of chunk 0, which H2 certified;
     // every attempt fetches the next one's itself, see llgs_lane_attempt)
     V3 z2 = zero, z3 = zero;
@@ -1278,8 +1305,14 @@ __device__ __forceinline__ SolveOut llgs_solve(const V3& m0, double J, double T,
       llgs_lane_gate<true>(L, M, budget);
       llgs_lane_attempt<THERMAL, RECORD, AXIS_Z, true>(L, M, out_m, k, tb, rtol, atol, max_step, rec, ek, ns, z2, z3);
       // (at least one attempt is made whatever the budget, as ever: the test follows the attempt)
-      if (!ns.chunk_end_go(attempt_loop_next(M.active, __ballot(L.t != L.T), it, budget))) break;
+      const bool more = attempt_loop_more(M.active, __ballot(L.t != L.T), it, budget);
+      if constexpr (RING || !NSRC::kShared) { if (!more) break; }
+      // (never executed: a shared source that is no RK45 ring meets this solve only in the instantiations of the fixed-step kernels,
+      // whose branch to it is never taken -- as chunk_meet; it keeps their publishing form)
+      else { if (!ns.chunk_end_go(more ? 1 : 0)) break; }
     }
+    // (RK45 ring: `it` attempts were made, 0 included; flag copy it & 1 stops the producer, behind the closing rendezvous)
+    if constexpr (RING) ns.close(it);
     llgs_masks_close(L, M);
     return llgs_lane_finish<RECORD>(L, out_m, rec, ek, ns);
 }
