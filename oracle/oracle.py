@@ -81,6 +81,12 @@ def lib():
         L.stgo_simple_solve.argtypes = [dp, C.c_double, C.POINTER(Params), C.POINTER(Config), C.c_double,
                                         C.c_uint64, C.c_uint32, dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32), dp, C.c_int64]
+        L.stgo_simple_solve_fed.restype = C.c_int
+        L.stgo_simple_solve_fed.argtypes = [dp, C.c_double, C.POINTER(Params), C.POINTER(Config), C.c_double, dp, C.c_int64,
+                                            dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, C.c_int64]
+        L.stgo_env_step_fed.restype = C.c_int
+        L.stgo_env_step_fed.argtypes = [C.POINTER(EnvState), C.c_void_p, C.c_int, C.POINTER(Params), C.POINTER(Config), dp,
+                                        C.c_int64, C.POINTER(StepOut)]
         L.stgo_llgs_solve.restype = C.c_int64
         L.stgo_llgs_solve.argtypes = [dp, C.c_double, C.POINTER(Params), C.POINTER(Config), C.c_double,
                                       C.c_uint64, C.c_uint32, dp, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
@@ -222,6 +228,10 @@ def make_config(solver="rk4", thermal=False, temperature=300.0, gamma=2.21e5, ma
                 atol=1e-9, max_steps=100, max_current=2e6, max_duration=5e-9, success_threshold=0.9,
                 energy_penalty_weight=0.1, seed=0, max_attempts=10_000_000, torque_model=0, noise_model=0,
                 noise_corr_time=1e-12):
+    if int(noise_model) not in (0, 1, 2):
+        raise ValueError("noise_model must be 0 (white), 1 (Ornstein-Uhlenbeck) or 2 (Brown field with 1/sqrt(dt))")
+    if int(noise_model) == 2 and solver == "rk45":
+        raise ValueError("noise_model 2 (the Brown field) needs a fixed-step solver ('rk4' or 'euler'): an adaptive step has no fixed dt")
     c = Config()
     c.solver = {"rk4": 0, "euler": 1, "rk45": 2}[solver]
     c.thermal = int(bool(thermal))
@@ -238,7 +248,19 @@ def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
-def simple_solve(m0, T, p, c, J, env_id=0, env_step=0, want_traj=False):
+def _fed(normals):
+    z = np.ascontiguousarray(normals, dtype=np.float64)
+    if z.ndim != 2 or z.shape[1] != 3:
+        raise ValueError("normals must be [n_sub, 3]")
+    return z
+
+
+_FED_REFUSED = ("the fed-normals solve takes noise_model 1 or 2 with 'rk4' or 'euler' and at least one row of normals per sub-step")
+
+
+def simple_solve(m0, T, p, c, J, env_id=0, env_step=0, want_traj=False, normals=None):
+    """normals [>= n_sub, 3]: sub-step i takes normals[i] in place of the stream's draw (noise_model 1 and 2 only); None: the stream
+    of (c.seed, env_id, env_step)."""
     m0 = np.ascontiguousarray(m0, dtype=np.float64)
     mf = np.zeros(3)
     n = C.c_int32(0)
@@ -249,9 +271,17 @@ def simple_solve(m0, T, p, c, J, env_id=0, env_step=0, want_traj=False):
     if want_traj:
         cap = 5002
         traj = np.zeros((cap, 3))
-    ok = lib().stgo_simple_solve(_dp(m0), float(T), C.byref(p), C.byref(c), float(J), env_id, env_step,
-                                 _dp(mf), C.byref(n), C.byref(zr), C.byref(nr),
-                                 _dp(traj) if traj is not None else None, cap)
+    if normals is None:
+        ok = lib().stgo_simple_solve(_dp(m0), float(T), C.byref(p), C.byref(c), float(J), env_id, env_step,
+                                     _dp(mf), C.byref(n), C.byref(zr), C.byref(nr),
+                                     _dp(traj) if traj is not None else None, cap)
+    else:
+        z = _fed(normals)
+        ok = lib().stgo_simple_solve_fed(_dp(m0), float(T), C.byref(p), C.byref(c), float(J), _dp(z), len(z),
+                                         _dp(mf), C.byref(n), C.byref(zr), C.byref(nr),
+                                         _dp(traj) if traj is not None else None, cap)
+        if ok < 0:
+            raise ValueError(_FED_REFUSED)
     out = dict(success=bool(ok), m_final=mf, n_steps=n.value, first_zero_row=zr.value, n_reset=nr.value)
     if want_traj:
         out["m"] = traj[: n.value + 1].copy()
@@ -400,8 +430,20 @@ def device_field(m, p):
     return h
 
 
-def env_step(state, action, p, c, env_id=0):
+def _env_step_fed(state, a, f64, p, c, normals):
+    z = _fed(normals)
+    out = StepOut()
+    if lib().stgo_env_step_fed(C.byref(state), a.ctypes.data_as(C.c_void_p), int(f64), C.byref(p), C.byref(c), _dp(z), len(z),
+                               C.byref(out)) < 0:
+        raise ValueError(_FED_REFUSED)
+    return out
+
+
+def env_step(state, action, p, c, env_id=0, normals=None):
+    """normals: as in simple_solve (the step's solve takes them in place of the stream at (env_id, state.rng_step))."""
     a = np.ascontiguousarray(action, dtype=np.float32)
+    if normals is not None:
+        return _env_step_fed(state, a, False, p, c, normals)
     out = StepOut()
     lib().stgo_env_step(C.byref(state), a.ctypes.data_as(C.POINTER(C.c_float)), C.byref(p), C.byref(c),
                         env_id, C.byref(out))
@@ -424,9 +466,11 @@ def env_step_batch(states, actions, params, cls, c, env_id0=0, n_threads=0):
     return outs
 
 
-def env_step_f64(state, action, p, c, env_id=0):
+def env_step_f64(state, action, p, c, env_id=0, normals=None):
     """env_step with a float64 action array."""
     a = np.ascontiguousarray(action, dtype=np.float64)
+    if normals is not None:
+        return _env_step_fed(state, a, True, p, c, normals)
     out = StepOut()
     lib().stgo_env_step_f64(C.byref(state), _dp(a), C.byref(p), C.byref(c), env_id, C.byref(out))
     return out

@@ -241,10 +241,12 @@ void stgo_ou_update(double x[3], const double xi[3], double dt, double corr_time
     for (int j = 0; j < 3; ++j) x[j] = decay * x[j] + w * xi[j];
 }
 
-int stgo_simple_solve(const double m0[3], double T, const stgo_params* p, const stgo_config* c,
-                      double J, uint64_t env_id, uint32_t env_step,
-                      double m_final[3], int32_t* n_steps, int32_t* first_zero_row, int32_t* n_reset,
-                      double* traj, int64_t traj_cap_rows) {
+/* zfed != NULL: sub-step i takes the caller's normals zfed[3i .. 3i+2] in place of the stream's draw (the two models that
+ * draw once per sub-step; stgo_simple_solve_fed checks that) */
+static int simple_solve_impl(const double m0[3], double T, const stgo_params* p, const stgo_config* c,
+                             double J, uint64_t env_id, uint32_t env_step,
+                             double m_final[3], int32_t* n_steps, int32_t* first_zero_row, int32_t* n_reset,
+                             double* traj, int64_t traj_cap_rows, const double* zfed, int64_t n_fed) {
     if (n_steps) *n_steps = 0;
     if (first_zero_row) *first_zero_row = -1;
     if (n_reset) *n_reset = 0;
@@ -263,6 +265,7 @@ int stgo_simple_solve(const double m0[3], double T, const stgo_params* p, const 
     int n = (int)q; if (n < 10) n = 10;
     dt = (T - 0.0) / n;
     if (n_steps) *n_steps = n;
+    if (zfed && (int64_t)n > n_fed) return -1;     /* fewer normals than sub-steps: nothing is solved */
     const int thermal = c->thermal && c->temperature > 0;
     const double hs = thermal ? stgo_thermal_strength(p, c->gamma, c->temperature, 0) : 0.0;
     int zero_row = -1;
@@ -270,20 +273,26 @@ int stgo_simple_solve(const double m0[3], double T, const stgo_params* p, const 
      * (spin_torque_env.py:475-477), sets K_eff for VCMA classes */
     const double volt = c->torque_model ? J * stgo_resistance(m0, p) * p->area : 0.0;
     nstream g;
-    if (thermal) ns_init(&g, c->seed, env_id, env_step, 0u);
+    if (thermal && !zfed) ns_init(&g, c->seed, env_id, env_step, 0u);
     if (traj && traj_cap_rows > 0) { traj[0] = m[0]; traj[1] = m[1]; traj[2] = m[2]; }
 
     /* noise_model 1: ThermalFluctuations' correlated field, one update per sub-step (x = 0 when the pulse starts),
      * held for all stages of the sub-step */
     const int ou = thermal && c->noise_model == 1;
+    /* noise_model 2: the Brown field with its 1/sqrt(dt) factor (include/spintorque_hip.h: cfg.noise_model = 2), one draw per
+     * sub-step, field strength * z / sqrt(dt) for all stages, dt the final T / n; nothing is carried between sub-steps */
+    const int brown = thermal && c->noise_model == 2;
+    const double brown_w = 1.0 / sqrt(dt);
     double oux[3] = {0.0, 0.0, 0.0};
     for (int i = 0; i < n; ++i) {
         double t = (double)i * dt + 0.0;           /* np.linspace(0, T, n+1)[i] = i*step + start */
         double k[4][3], y[3], hth[3], z[3];
         const int nstage = (c->solver == 1) ? 1 : 4;
-        if (ou) {
-            ns_draw3(&g, z);
-            stgo_ou_update(oux, z, dt, c->noise_corr_time);
+        if (ou || brown) {
+            if (zfed) { z[0] = zfed[3 * i]; z[1] = zfed[3 * i + 1]; z[2] = zfed[3 * i + 2]; }
+            else ns_draw3(&g, z);
+            if (ou) stgo_ou_update(oux, z, dt, c->noise_corr_time);
+            else { oux[0] = brown_w * z[0]; oux[1] = brown_w * z[1]; oux[2] = brown_w * z[2]; }
             hth[0] = hs * oux[0]; hth[1] = hs * oux[1]; hth[2] = hs * oux[2];
         }
         for (int s = 0; s < nstage; ++s) {
@@ -293,7 +302,7 @@ int stgo_simple_solve(const double m0[3], double T, const stgo_params* p, const 
             else { ts = t + dt; for (int j = 0; j < 3; ++j) y[j] = m[j] + k[2][j]; }
             /* spin_torque_env.py:442-443  current_func(t) = J if t <= T else 0 */
             double Jt = (ts <= T) ? J : 0.0;
-            if (thermal && !ou) {
+            if (thermal && !ou && !brown) {
                 ns_draw3(&g, z);
                 hth[0] = hs * z[0]; hth[1] = hs * z[1]; hth[2] = hs * z[2];
             }
@@ -322,6 +331,27 @@ int stgo_simple_solve(const double m0[3], double T, const stgo_params* p, const 
     if (zero_row >= 0) return 0;
     m_final[0] = m[0]; m_final[1] = m[1]; m_final[2] = m[2];
     return 1;
+}
+
+int stgo_simple_solve(const double m0[3], double T, const stgo_params* p, const stgo_config* c,
+                      double J, uint64_t env_id, uint32_t env_step,
+                      double m_final[3], int32_t* n_steps, int32_t* first_zero_row, int32_t* n_reset,
+                      double* traj, int64_t traj_cap_rows) {
+    return simple_solve_impl(m0, T, p, c, J, env_id, env_step, m_final, n_steps, first_zero_row, n_reset, traj, traj_cap_rows, 0, 0);
+}
+
+int stgo_simple_solve_fed(const double m0[3], double T, const stgo_params* p, const stgo_config* c, double J,
+                          const double* z, int64_t n_z,
+                          double m_final[3], int32_t* n_steps, int32_t* first_zero_row, int32_t* n_reset,
+                          double* traj, int64_t traj_cap_rows) {
+    if (!z || (c->noise_model != 1 && c->noise_model != 2) || c->solver == 2) {
+        if (n_steps) *n_steps = 0;
+        if (first_zero_row) *first_zero_row = -1;
+        if (n_reset) *n_reset = 0;
+        m_final[0] = m0[0]; m_final[1] = m0[1]; m_final[2] = m0[2];
+        return -1;
+    }
+    return simple_solve_impl(m0, T, p, c, J, 0, 0, m_final, n_steps, first_zero_row, n_reset, traj, traj_cap_rows, z, n_z);
 }
 
 /* ------------------------------------------------------------------------------------------------
@@ -617,9 +647,8 @@ void stgo_observation(const stgo_env_state* s, const stgo_params* p, const stgo_
 /* ------------------------------------------------------------------------------------------------
  * A10-A14  SpinTorqueEnv.step
  * ------------------------------------------------------------------------------------------------ */
-static void env_step_parsed(stgo_env_state* s, double J, double T, const stgo_params* p, const stgo_config* c,
-                            uint64_t env_id, stgo_step_out* out) {
-    s->last_action[0] = J; s->last_action[1] = T;
+static int env_step_parsed(stgo_env_state* s, double J, double T, const stgo_params* p, const stgo_config* c,
+                           uint64_t env_id, stgo_step_out* out, const double* zfed, int64_t n_fed) {
     double prev_align = dot3(s->m, s->target);                      /* spin_torque_env.py:338-339 */
     /* _simulate_dynamics (spin_torque_env.py:435-488) */
     double mf[3];
@@ -629,9 +658,13 @@ static void env_step_parsed(stgo_env_state* s, double J, double T, const stgo_pa
         int32_t succ = 0; int64_t att = 0;
         int64_t npts = stgo_llgs_solve(s->m, T, p, c, J, env_id, s->rng_step, mf, &succ, &att, 0, 0, 0, 0, 0);
         ok = succ; nsub = (int32_t)(npts - 1);
+    } else if (zfed) {
+        ok = stgo_simple_solve_fed(s->m, T, p, c, J, zfed, n_fed, mf, &nsub, &zr, &nreset, 0, 0);
+        if (ok < 0) return -1;                                      /* refused: the state is untouched */
     } else {
         ok = stgo_simple_solve(s->m, T, p, c, J, env_id, s->rng_step, mf, &nsub, &zr, &nreset, 0, 0);
     }
+    s->last_action[0] = J; s->last_action[1] = T;
     double m_before[3] = {s->m[0], s->m[1], s->m[2]};
     if (ok) {
         double nn = norm3(mf);                                      /* :462-464 */
@@ -666,20 +699,30 @@ static void env_step_parsed(stgo_env_state* s, double J, double T, const stgo_pa
     out->status = ok ? (nreset > 0 ? 2 : 0) : 1;
     out->energy = energy;
     out->n_sub = nsub;
+    return 0;
 }
 
 void stgo_env_step(stgo_env_state* s, const float action[2], const stgo_params* p, const stgo_config* c,
                    uint64_t env_id, stgo_step_out* out) {
     double J, T;
     stgo_parse_action(action, c, &J, &T);
-    env_step_parsed(s, J, T, p, c, env_id, out);
+    env_step_parsed(s, J, T, p, c, env_id, out, 0, 0);
 }
 
 void stgo_env_step_f64(stgo_env_state* s, const double action[2], const stgo_params* p, const stgo_config* c,
                        uint64_t env_id, stgo_step_out* out) {
     double J, T;
     stgo_parse_action_f64(action, c, &J, &T);
-    env_step_parsed(s, J, T, p, c, env_id, out);
+    env_step_parsed(s, J, T, p, c, env_id, out, 0, 0);
+}
+
+int stgo_env_step_fed(stgo_env_state* s, const void* action, int action_f64, const stgo_params* p, const stgo_config* c,
+                      const double* z, int64_t n_z, stgo_step_out* out) {
+    double J, T;
+    if (!z || c->solver == 2) return -1;
+    if (action_f64) stgo_parse_action_f64((const double*)action, c, &J, &T);
+    else stgo_parse_action((const float*)action, c, &J, &T);
+    return env_step_parsed(s, J, T, p, c, 0, out, z, n_z);
 }
 
 void stgo_env_step_batch_f64(int64_t n, stgo_env_state* s, const double* actions, const stgo_params* params,

@@ -65,7 +65,11 @@ typedef struct {
     int64_t max_attempts;           /* RK45 attempt budget per solve (guard; reference has none) */
     int32_t torque_model;           /* 0 reference RHS; 1 device-physics torque model (include/spintorque_hip.h) */
     int32_t noise_model;            /* fixed-step solvers: 0 white field per RHS call (simple_solver.py:378-388);
-                                       1 Ornstein-Uhlenbeck field per sub-step (physics/thermal_model.py:113-137) */
+                                       1 Ornstein-Uhlenbeck field per sub-step (physics/thermal_model.py:113-137);
+                                       2 the Brown field with its 1/sqrt(dt) factor (include/spintorque_hip.h: one draw z per
+                                         sub-step, field strength * z / sqrt(dt) for all its stages, dt = T / n; nothing carried
+                                         between sub-steps; rk4 and euler only -- with solver 2 the configuration is refused
+                                         where it is made, oracle/oracle.py: make_config) */
     double noise_corr_time;         /* ThermalFluctuations.correlation_time */
 } stgo_config;
 
@@ -104,6 +108,16 @@ int stgo_simple_solve(const double m0[3], double T, const stgo_params* p, const 
                       double J, uint64_t env_id, uint32_t env_step,
                       double m_final[3], int32_t* n_steps, int32_t* first_zero_row, int32_t* n_reset,
                       double* traj, int64_t traj_cap_rows);
+
+/* The same solve with the caller's normals z[n_z][3] in place of the stream: sub-step i takes z[i].  For the two models that draw
+ * once per sub-step (noise_model 1 and 2; rk4 and euler), so that a comparison with the device can be fed the device's own draws
+ * (stg_thermal_normals), which differ from this file's by ~1e-7 relative.  Returns -1, m_final = m0, when the model draws per RHS
+ * call, the solver is RK45, z is NULL or n_z is below the sub-step count; otherwise as stgo_simple_solve.  Fed this file's own
+ * draws (stgo_thermal_normals) it equals stgo_simple_solve bit for bit. */
+int stgo_simple_solve_fed(const double m0[3], double T, const stgo_params* p, const stgo_config* c, double J,
+                          const double* z, int64_t n_z,
+                          double m_final[3], int32_t* n_steps, int32_t* first_zero_row, int32_t* n_reset,
+                          double* traj, int64_t traj_cap_rows);
 
 /* ---- A6: LLGSSolver.solve::llgs_rhs (physics/llgs_solver.py:92-126, 182-237) ---- */
 void stgo_llgs_rhs(const double y[3], const stgo_params* p, double gamma, double J,
@@ -144,6 +158,11 @@ void stgo_env_step(stgo_env_state* s, const float action[2], const stgo_params* 
                    uint64_t env_id, stgo_step_out* out);
 void stgo_env_step_f64(stgo_env_state* s, const double action[2], const stgo_params* p, const stgo_config* c,
                        uint64_t env_id, stgo_step_out* out);
+
+/* one env step on stgo_simple_solve_fed: action is float[2] (action_f64 = 0) or double[2]; returns -1 and leaves the state and
+ * `out` untouched where that solve refuses, else 0.  rng_step advances as in stgo_env_step. */
+int stgo_env_step_fed(stgo_env_state* s, const void* action, int action_f64, const stgo_params* p, const stgo_config* c,
+                      const double* z, int64_t n_z, stgo_step_out* out);
 
 /* batch form used by bench.py's cpu_baseline leg and the gloo tests: env i uses params[cls[i]]
  * (cls == NULL -> params[0]); OpenMP-parallel over envs with n_threads threads (<=0 -> default). */

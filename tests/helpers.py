@@ -16,6 +16,14 @@ import oracle
 RESET_KEY_XOR = 0x9E3779B97F4A7C15
 
 
+def oracle_noise_model(name):
+    """the env's noise_model name -> the oracle's value, through the library's own table; a name the table lacks raises"""
+    from spin_torque_gym_amd._lib import NOISE_MODELS
+    if name not in NOISE_MODELS:
+        raise ValueError(f"noise_model {name!r}: the oracle knows {list(NOISE_MODELS)}")
+    return NOISE_MODELS[name]
+
+
 def oracle_config(cfg):
     """spin_torque_gym_amd.backend.EnvConfig -> oracle.Config"""
     return oracle.make_config(solver=cfg.solver, thermal=cfg.include_thermal_fluctuations, temperature=cfg.temperature,
@@ -24,7 +32,7 @@ def oracle_config(cfg):
                               success_threshold=cfg.success_threshold, energy_penalty_weight=cfg.energy_penalty_weight,
                               seed=cfg.seed, max_attempts=cfg.max_attempts,
                               torque_model=int(getattr(cfg, "torque_model", "reference") == "device"),
-                              noise_model=int(getattr(cfg, "noise_model", "white") == "ou"),
+                              noise_model=oracle_noise_model(getattr(cfg, "noise_model", "white")),
                               noise_corr_time=getattr(cfg, "correlation_time", 1e-12))
 
 

@@ -209,6 +209,80 @@ def test_sharded_env_on_a_subgroup_addresses_peers_by_global_rank(oracle_mod):
         assert torch.equal(o2, obs) and torch.equal(r2, r) and torch.equal(te2, te) and torch.equal(tr2, tr)
 
 
+# ------------------------------------------------------------------------------------------------
+# noise_model='brown' on the oracle: the shards' streams are keyed by the global env index under this model too
+# ------------------------------------------------------------------------------------------------
+BROWN_VOLUME = 1e-26          # (tests/wave_config_cases.py: VOL_THERMAL; currents scaled by the volume ratio)
+
+
+def _brown_kw():
+    from helpers import OracleBackend
+    return dict(device_params=stt_default_params(volume=BROWN_VOLUME), include_thermal_fluctuations=True, seed=77, solver="rk4",
+                noise_model="brown", temperature=450.0, max_current=2e6 * BROWN_VOLUME / 8.75e-11, backend=OracleBackend)
+
+
+def _brown_inputs(n, steps):
+    m0, tgt, acts = _inputs(n, steps)
+    acts[..., 0] *= np.float32(BROWN_VOLUME / 8.75e-11)
+    return m0, tgt, acts
+
+
+def _brown_worker(rank, world, port, n, steps, q):
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    root = os.path.dirname(here)
+    for p in (root, os.path.join(root, "spin-torque-rl-gym_amd"), here):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from spin_torque_gym_amd.distributed import ShardedSpinTorqueVecEnv
+    m0, tgt, acts = _brown_inputs(n, steps)
+    env = ShardedSpinTorqueVecEnv(n, **_brown_kw())
+    assert env.local.backend.ocfg.noise_model == 2 and env.local.env_id0 == rank * n // world
+    obs, _ = env.reset(options={"initial_state": m0, "target_state": tgt})
+    rec = [obs.clone()]
+    for k in range(steps):
+        rec.append(tuple(t.clone() for t in env.step(torch.from_numpy(acts[k]))[:4]))
+    if rank == 0:
+        q.put(_to_numpy(rec))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.timeout(300)
+def test_two_rank_sharded_env_under_the_brown_field_equals_single_process(oracle_mod):
+    """2 ranks, 2 steps, noise_model='brown' on the oracle: the gathered records equal the one-process OracleBackend env's bit for bit,
+    and the Brown field is what ran (the same env under 'white' gives other observations)"""
+    import spin_torque_gym_amd as stg
+    n, steps, world = 16, 2, 2
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_brown_worker, args=(r, world, port, n, steps, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    rec = _from_numpy(q.get(timeout=240))
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    m0, tgt, acts = _brown_inputs(n, steps)
+    last = {}
+    for noise in ("brown", "white"):
+        env = stg.SpinTorqueVecEnv(n, **dict(_brown_kw(), noise_model=noise))
+        obs, _ = env.reset(options={"initial_state": m0, "target_state": tgt})
+        assert torch.equal(rec[0], obs)
+        for k in range(steps):
+            obs, r, te, tr, _ = env.step(torch.from_numpy(acts[k]))
+            if noise == "brown":
+                o2, r2, te2, tr2 = rec[k + 1]
+                assert torch.equal(o2, obs) and torch.equal(r2, r) and torch.equal(te2, te) and torch.equal(tr2, tr)
+        last[noise] = obs.clone()
+        env.close()
+    assert float((last["brown"][:, :3] - last["white"][:, :3]).abs().max()) > 1e-2
+
+
 def test_shard_range_partitions():
     from spin_torque_gym_amd.distributed import shard_range
     for n, w in ((1048576, 8), (10, 3), (7, 8)):
