@@ -373,6 +373,45 @@ int stg_solve_wave(stg_ctx* ctx, const double* m0, const double* J, const double
                    double* t, double* m, double* energy, double* torques, double* m_final, int32_t* n_points, uint8_t* success,
                    void* stream);
 
+/* Monte-Carlo switching statistics, reduced on the device: R thermal trials of each of G conditions, of which only integer counts
+ * reach memory.  A trial is a chain of up to P rectangular-pulse solves ("phases", e.g. equilibrate, pulse, relax) that starts from
+ * the condition's m0 and hands each phase's final m to the next.
+ *
+ * Stream rule: trial r (trial0 <= r < trial0 + R) of condition g IS problem i = g * trial_stride + r of stg_solve -- phase p is the
+ * solve of stg_solve with (m, J[p][g], T[p][g]) at Philox counter word env_step + p on the stream of env id env_id0 + i (env_id0 of
+ * stg_create), with the context's solver, thermal field and class row.  With P = 1 and trial_stride = R the G * R trials are the
+ * problems of ONE stg_solve over the arrays replicated R times per condition, and the counts below equal the host's reduction of
+ * that call's m_final and success exactly.
+ *   A phase with T[p][g] == 0.0 exactly is skipped (m passes through; it is not a failed solve).
+ *   A phase whose solve fails (success = 0 in stg_solve's terms) ends the trial with the m that solve hands back; the trial adds
+ *   one to n_failed[g] and is classified like any other.
+ * Classification of a trial's last m against the condition's target row, in IEEE fp64 without FMA contraction:
+ *   proj = ((m.x * target[0][g]) + (m.y * target[1][g])) + (m.z * target[2][g])
+ *   switched iff proj > threshold                                   (a NaN proj is not switched)
+ *   bin = min(n_bins - 1, max(0, (int)floor((proj + 1.0) * (0.5 * n_bins))))      (a NaN proj goes to bin 0)
+ * i.e. n_bins equal bins over [-1, 1], the outer two open-ended.
+ *
+ * m0, target double[3][G]; J, T double[P][G] (condition index fastest); cond_cls uint8[G] selects each condition's row of the
+ * context's class table (stg_set_params; a value >= n_classes reads class 0, as stg_solve's cls does) or NULL: class 0 for all --
+ * the context's own cls array and n_envs play no part.  1 <= P <= STG_MAX_PHASES, 0 <= n_bins <= STG_MAX_BINS.
+ * The call ADDS to n_switched[G], n_failed[G] and hist[G][n_bins] (NULL iff n_bins == 0); the caller zeroes them.  So chunks of a
+ * trial range (trial0), or ranks of a sharded job, sum to the counts of one call; the counts do not depend on how the library
+ * spreads the trials over wavefronts.  It touches no other memory and nothing beyond those G, G and G * n_bins elements.
+ * Launch: one 64-lane wavefront per workgroup works on one condition; below STG_SWITCH_STATS_WAVES wavefronts in all each lane runs
+ * one trial, above it each lane loops over as many trials as keep the launch at about that many wavefronts.  A single call runs
+ * all R trials in one launch: callers sharing a device should bound R per call (the Python method does).
+ * Enqueues kernels only (no allocation, no synchronisation).  Per-env parameters (stg_set_params_per_env) return STG_E_STATE, as
+ * for stg_solve*.  STG_E_INVALID with nothing launched: a NULL ctx / m0 / J / T / target / n_switched / n_failed, hist NULL with
+ * n_bins > 0 or non-NULL with n_bins == 0, G < 1, R < 0, P or n_bins out of range, trial0 < 0, trial_stride < trial0 + R (the
+ * streams of two conditions would overlap), G * trial_stride (+ env_id0) beyond int64.  R == 0 is valid and does nothing. */
+#define STG_MAX_PHASES 4
+#define STG_MAX_BINS 64
+#define STG_SWITCH_STATS_WAVES 12288       /* 12 per SIMD of a 256-CU device: whole rounds at 2, 3, 4 or 6 resident wavefronts per SIMD */
+int stg_switch_stats(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t P,
+                     const double* m0, const double* J, const double* T, const uint8_t* cond_cls, uint32_t env_step,
+                     const double* target, double threshold, int32_t n_bins, unsigned long long* n_switched,
+                     unsigned long long* n_failed, unsigned long long* hist, void* stream);
+
 /* SpinTorqueEnv.step for all N envs with the drive of stg_solve_wave: current_func(t) and field_func(t) as piecewise-linear tables
  * in place of the rectangular pulse in zero field of stg_step (spin_torque_env.py:442-447).
  *

@@ -13,6 +13,7 @@
 // with per-env parameters each lane derives its constants from its env's record into registers (step kernel, MULTI == 2).
 #include "stg_kernels.hpp"
 #include "stg_wave.hpp"
+#include "stg_switch_stats.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -1025,6 +1026,39 @@ int stg_solve_wave(stg_ctx* ctx, const double* m0, const double* J, const double
     w.kj = kj; w.tj = tj; w.jk = jk; w.kh = kh; w.th = th; w.hk = hk;
     const bool thermal = ctx->cfg.solver == STG_SOLVER_RK45 ? ctx->cfg.thermal != 0 : (ctx->cfg.thermal && ctx->cfg.temperature > 0);
     stg_wave_launch(w, ctx->cfg.solver, thermal, ctx->ncls > 1, record, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return STG_OK;
+}
+
+// Monte-Carlo switching statistics: its kernels live in stg_switch_stats.hip (stg_switch_stats_launch)
+int stg_switch_stats(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t P, const double* m0, const double* J,
+                     const double* T, const uint8_t* cond_cls, uint32_t env_step, const double* target, double threshold, int32_t n_bins,
+                     unsigned long long* n_switched, unsigned long long* n_failed, unsigned long long* hist, void* stream) {
+    if (!ctx) return fail(STG_E_INVALID, "ctx is NULL");
+    if (!ctx->have_params) return fail(STG_E_STATE, "stg_set_params must precede stg_switch_stats");
+    if (ctx->per_env) return fail(STG_E_STATE, "stg_switch_stats works on the class table (stg_set_params), not on per-env parameters");
+    if (!m0 || !J || !T || !target || !n_switched || !n_failed) return fail(STG_E_INVALID, "m0/J/T/target/n_switched/n_failed must not be NULL");
+    if (G < 1) return fail(STG_E_INVALID, "G must be >= 1");
+    if (R < 0) return fail(STG_E_INVALID, "R must be >= 0");
+    if (P < 1 || P > STG_MAX_PHASES) return fail(STG_E_INVALID, "P must be in 1 ... STG_MAX_PHASES");
+    if (n_bins < 0 || n_bins > STG_MAX_BINS) return fail(STG_E_INVALID, "n_bins must be in 0 ... STG_MAX_BINS");
+    if ((hist == nullptr) != (n_bins == 0)) return fail(STG_E_INVALID, "hist must be NULL if and only if n_bins == 0");
+    if (trial0 < 0) return fail(STG_E_INVALID, "trial0 must be >= 0");
+    if (R > INT64_MAX - trial0 || trial_stride < trial0 + R)
+        return fail(STG_E_INVALID, "trial_stride must be >= trial0 + R (the streams of two conditions would overlap)");
+    if (trial_stride > (INT64_MAX - ctx->env_id0) / (int64_t)G) return fail(STG_E_INVALID, "env_id0 + G * trial_stride exceeds int64");
+    if (R == 0) return STG_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    SwitchStatsArgs a{};
+    a.c = cfg_view(ctx->cfg); a.env_id0 = ctx->env_id0;
+    a.R = R; a.trial0 = trial0; a.trial_stride = trial_stride;
+    switch_stats_plan(G, R, &a.L, &a.waves_per_cond);
+    a.G = G; a.P = P; a.n_bins = n_bins; a.ncls = ctx->ncls;
+    a.ctab = ctx->ctab; a.cond_cls = cond_cls;
+    a.m0 = m0; a.J = J; a.T = T; a.target = target; a.threshold = threshold; a.env_step = env_step;
+    a.n_switched = n_switched; a.n_failed = n_failed; a.hist = hist;
+    const bool thermal = ctx->cfg.solver == STG_SOLVER_RK45 ? ctx->cfg.thermal != 0 : (ctx->cfg.thermal && ctx->cfg.temperature > 0);
+    stg_switch_stats_launch(a, ctx->cfg.solver, thermal, ctx->ncls > 1 && cond_cls != nullptr, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return STG_OK;
 }

@@ -14,7 +14,10 @@ LIB_PATH = os.environ.get("STG_HIP_LIBRARY") or os.path.join(_HERE, "libspintorq
 STG_MAX_TARGETS = 8
 STG_MAX_CLASSES = 64
 STG_MAX_KNOTS = 32       # knots of one piecewise-linear waveform (stg_solve_wave, stg_step_wave, stg_set_pulse_shape)
-ABI_VERSION = 5          # STG_ABI_VERSION of include/spintorque_hip.h this binding was written against
+STG_MAX_PHASES = 4       # phases of one trial of stg_switch_stats
+STG_MAX_BINS = 64        # histogram bins of stg_switch_stats
+SWITCH_STATS_WAVES = 12288  # STG_SWITCH_STATS_WAVES: above this many wavefronts in a launch, the lanes of stg_switch_stats loop over trials
+ABI_VERSION = 5         # STG_ABI_VERSION of include/spintorque_hip.h this binding was written against
 STG_NPARAM = 30          # double-valued fields of stg_device_params, in declaration order
 SOLVERS = {"rk4": 0, "euler": 1, "rk45": 2}
 DEV_TYPES = {"stt_mram": 0, "sot_mram": 1, "vcma_mram": 2}
@@ -79,6 +82,8 @@ SYMBOLS = {
     "stg_solve_traj": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "stg_solve_wave": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, _VP, _VP, C.c_int32, _VP, _VP, C.c_uint32, C.c_int32, _VP, _VP, _VP, _VP,
                                  _VP, _VP, _VP, _VP]),
+    "stg_switch_stats": (C.c_int, [_VP, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _VP, _VP, _VP, _VP, C.c_uint32, _VP, C.c_double,
+                                   C.c_int32, _VP, _VP, _VP, _VP]),
     "stg_step_wave": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                 _VP]),
     "stg_set_pulse_shape": (C.c_int, [_VP, C.c_int32, _VP, _VP, C.c_int32, _VP, _VP]),

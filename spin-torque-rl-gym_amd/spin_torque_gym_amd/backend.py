@@ -550,6 +550,34 @@ class HipBackend:
         self._keep = (m0, J, T)
         return out
 
+    def switch_stats(self, m0, J, T, target, n_trials, trial0=0, trial_stride=None, cond_cls=None, env_step=0, threshold=0.0,
+                     n_bins=0, out=None):
+        """Monte-Carlo switching counts reduced on the device (stg_switch_stats): trials trial0 ... trial0 + n_trials - 1 of the G
+        conditions m0 [3,G], J, T [P,G], target [3,G]; cond_cls uint8 [G] picks each condition's class of set_params (None: class 0).
+        Trial r of condition g is problem g * trial_stride + r of `solve` at env_step + p (trial_stride None: trial0 + n_trials).
+        Returns (n_switched [G], n_failed [G], hist [G,n_bins] or None), int64 on the device; the call ADDS to them: `out` = the
+        triple of an earlier call accumulates a chunked trial range, None starts from zero.  Enqueues only."""
+        dev = self.device
+        m0 = self._dev(m0, torch.float64)
+        g = int(m0.shape[-1])
+        m0 = self._dev(m0, torch.float64, (3, g))
+        J, T = self._dev(J, torch.float64), self._dev(T, torch.float64)
+        p = int(J.shape[0])
+        J, T = self._dev(J, torch.float64, (p, g)), self._dev(T, torch.float64, (p, g))
+        target = self._dev(target, torch.float64, (3, g))
+        cond_cls = self._dev(cond_cls, torch.uint8, (g,))
+        r, t0 = int(n_trials), int(trial0)
+        stride = t0 + r if trial_stride is None else int(trial_stride)
+        if out is None:
+            out = (torch.zeros(g, dtype=torch.int64, device=dev), torch.zeros(g, dtype=torch.int64, device=dev),
+                   torch.zeros((g, int(n_bins)), dtype=torch.int64, device=dev) if n_bins > 0 else None)
+        n_sw, n_failed, hist = out
+        _lib.check(self.lib.stg_switch_stats(self._ctx, g, r, t0, stride, p, _ptr(m0), _ptr(J), _ptr(T), _ptr(cond_cls), int(env_step),
+                                             _ptr(target), float(threshold), int(n_bins), _ptr(n_sw), _ptr(n_failed), _ptr(hist),
+                                             self._stream()))
+        self._keep = (m0, J, T, target, cond_cls)
+        return out
+
     def device_terms(self, m, J, volt):
         """Device-class formulas per env: (tau_dl [3,N], tau_fl [3,N], k_eff [N]) for m [3,N], J [N], volt [N]."""
         n, dev = self.n, self.device

@@ -226,6 +226,87 @@ class _GpuSolverBase:
         self.solve_count += n
         return res
 
+    def switching_statistics(self, m_initial, current, duration, device_params, n_trials: int, *, equilibrate=0.0, relax=0.0,
+                             target=(0.0, 0.0, -1.0), threshold: float = 0.0, n_bins: int = 0, temperature: float = 300.0,
+                             device_type="stt_mram", class_index=None, env_step: int = 0, trial_offset: int = 0, trial_stride=None,
+                             max_trials_per_launch: int = 2 ** 22) -> Dict[str, Any]:
+        """Monte-Carlo switching statistics of G conditions with R = n_trials thermal trials each, with the trial loop and the
+        reduction on the GPU (stg_switch_stats): no per-trial array exists, so R is bounded by time, not by memory.
+
+        m_initial [G,3]; current, duration [G] (one pulse) or [P,G] (P phases run back to back, each from the previous one's final
+        m, phase p on Philox counter word env_step + p; a phase of duration exactly 0 is skipped).  equilibrate > 0 (scalar or [G])
+        prepends a phase at J = 0, relax > 0 appends one; at most 4 phases in all.  device_params: one dict, or a list of up to 64
+        dicts with class_index [G] (device_type then a string or a list) for sweeps over device size.  A trial counts as switched
+        when proj = m_final . target > threshold (target [3] or [G,3]); a trial one of whose solves fails ends there with that
+        solve's m, is classified like any other and counted in n_failed.  n_bins > 0 also returns the histogram of proj over n_bins
+        equal bins of [-1, 1] (outer bins open-ended).
+
+        Trial r of condition g has the stream of problem g * trial_stride + trial_offset + r of solve_batch (trial_stride None:
+        trial_offset + n_trials), so disjoint trial ranges -- later calls, other ranks -- are independent and their counts add up.
+        The trials run in launches of at most max_trials_per_launch per condition, which keeps each kernel short on a shared
+        device; the counts do not depend on it.  The thermal field is on (choose its model with the constructor's noise_model).
+
+        Returns dict(p_switch [G] = n_switched / R, wer [G] = 1 - p_switch, n_switched [G], n_failed [G],
+        stderr [G] = sqrt(p (1 - p) / R), hist [G,n_bins], bin_edges [n_bins + 1] (empty without bins))."""
+        m0 = np.asarray(m_initial.cpu() if torch.is_tensor(m_initial) else m_initial, dtype=np.float64).reshape(-1, 3)
+        g, r = int(m0.shape[0]), int(n_trials)
+        if r < 1:
+            raise ValueError("n_trials must be >= 1")
+        if int(max_trials_per_launch) < 1:
+            raise ValueError("max_trials_per_launch must be >= 1")
+        if not 0 <= int(n_bins) <= 64:
+            raise ValueError("n_bins must be in 0 ... 64")
+        J, T = (np.asarray(x, dtype=np.float64) for x in (current, duration))
+        J, T = (np.broadcast_to(x, (g,))[None, :] if x.ndim <= 1 else x for x in (J, T))
+        if J.shape != T.shape or J.ndim != 2 or J.shape[1] != g:
+            raise ValueError(f"current and duration must both have shape [G] or [P,G] with G = {g}, got {J.shape} and {T.shape}")
+        phases = [(J, T)]
+        for where, t in ((0, equilibrate), (1, relax)):
+            t = np.broadcast_to(np.asarray(t, dtype=np.float64), (g,))
+            if (t < 0).any():
+                raise ValueError("equilibrate and relax must be >= 0")
+            if (t > 0).any():
+                ph = (np.zeros((1, g)), t[None, :])
+                phases = [ph] + phases if where == 0 else phases + [ph]
+        J, T = (np.ascontiguousarray(np.concatenate([ph[k] for ph in phases], axis=0)) for k in (0, 1))
+        if J.shape[0] > 4:
+            raise ValueError(f"a trial has at most 4 phases (equilibrate and relax included), got {J.shape[0]}")
+        tgt = np.ascontiguousarray(np.broadcast_to(np.asarray(target, dtype=np.float64), (g, 3)).T)
+        tables = device_params if isinstance(device_params, (list, tuple)) else [device_params]
+        types = device_type if isinstance(device_type, (list, tuple)) else [device_type] * len(tables)
+        if not 1 <= len(tables) <= 64 or len(types) != len(tables):
+            raise ValueError("device_params is one dict or a list of 1 ... 64 dicts (with as many device types, or one)")
+        cls = None
+        if len(tables) > 1:
+            if class_index is None:
+                raise ValueError("class_index [G] is required with more than one device_params dict")
+            cls = np.asarray(class_index).reshape(g)
+            if cls.min() < 0 or cls.max() >= len(tables):
+                raise ValueError("class_index out of range")
+            cls = torch.from_numpy(cls.astype(np.uint8))
+        stride = int(trial_offset) + r if trial_stride is None else int(trial_stride)
+        if int(trial_offset) < 0 or stride < int(trial_offset) + r:
+            raise ValueError("trial_offset must be >= 0 and trial_stride >= trial_offset + n_trials")
+        cfg = EnvConfig(solver=self._solver_name, include_thermal_fluctuations=True, temperature=float(temperature), gamma=self.gamma,
+                        max_step=self.max_step, rtol=self.rtol, atol=self.atol, seed=self._seed, noise_model=self.noise_model,
+                        correlation_time=self.correlation_time)
+        b = self._backend_factory(g, cfg, self.device_index, 0)
+        try:
+            b.set_params([_flat_for(p, t, self._validate_params) for p, t in zip(tables, types)], cls)
+            out, step = None, int(max_trials_per_launch)
+            for done in range(0, r, step):
+                out = b.switch_stats(torch.from_numpy(np.ascontiguousarray(m0.T)), torch.from_numpy(J), torch.from_numpy(T),
+                                     torch.from_numpy(tgt), min(step, r - done), trial0=int(trial_offset) + done, trial_stride=stride,
+                                     cond_cls=cls, env_step=env_step, threshold=float(threshold), n_bins=int(n_bins), out=out)
+            n_sw, n_failed = (x.cpu().numpy().astype(np.int64) for x in out[:2])
+            hist = out[2].cpu().numpy().astype(np.int64) if n_bins > 0 else np.zeros((g, 0), dtype=np.int64)
+        finally:
+            b.close()
+        self.solve_count += g * r
+        p = n_sw / r
+        return {"p_switch": p, "wer": 1.0 - p, "n_switched": n_sw, "n_failed": n_failed, "stderr": np.sqrt(p * (1.0 - p) / r),
+                "hist": hist, "bin_edges": np.linspace(-1.0, 1.0, int(n_bins) + 1) if n_bins > 0 else np.zeros(0)}
+
     def _solve_one(self, m_initial, t_span, device_params, current_func, field_func, thermal_noise, temperature,
                    traj_cap):
         t0, t1 = float(t_span[0]), float(t_span[1])
