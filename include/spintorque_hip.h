@@ -378,7 +378,7 @@ int stg_solve_wave(stg_ctx* ctx, const double* m0, const double* J, const double
  * the condition's m0 and hands each phase's final m to the next.
  *
  * Stream rule: trial r (trial0 <= r < trial0 + R) of condition g IS problem i = g * trial_stride + r of stg_solve -- phase p is the
- * solve of stg_solve with (m, J[p][g], T[p][g]) at Philox counter word env_step + p on the stream of env id env_id0 + i (env_id0 of
+ * solve of stg_solve with (m, J[p][g], T[p][g]) at Philox counter word env_step + p modulo 2^32 on the stream of env id env_id0 + i (env_id0 of
  * stg_create), with the context's solver, thermal field and class row.  With P = 1 and trial_stride = R the G * R trials are the
  * problems of ONE stg_solve over the arrays replicated R times per condition, and the counts below equal the host's reduction of
  * that call's m_final and success exactly.

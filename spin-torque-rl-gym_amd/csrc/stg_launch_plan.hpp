@@ -48,6 +48,17 @@ inline void refill_auto(int64_t n, bool thermal, int& r, int64_t& nw) {
     r = (int)(rr < 2 ? 2 : (rr > 0x7FFFFFFF ? 0x7FFFFFFF : rr));              // (envs per lane on average; only != 0 matters to the launch)
 }
 
+// stg_switch_stats (kernels: stg_switch_stats.hip; pinned by tests/test_switch_stats_plan_host.py).
+// Launch rule: every lane runs one trial (L = 1) while that needs at most STG_SWITCH_STATS_WAVES wavefronts in all; beyond that the
+// wavefronts per condition are capped at max(1, STG_SWITCH_STATS_WAVES / G) and each lane loops over L trials.
+static inline void switch_stats_plan(int32_t G, int64_t R, int64_t* L, int32_t* waves_per_cond) {
+    const int64_t w1 = (R + 63) / 64;                              // wavefronts per condition at one trial per lane
+    int64_t cap = STG_SWITCH_STATS_WAVES / (int64_t)G;
+    if (cap < 1) cap = 1;
+    *L = w1 <= cap ? 1 : (w1 + cap - 1) / cap;
+    *waves_per_cond = (int32_t)((w1 + *L - 1) / *L);
+}
+
 struct StepPlan {
     bool sort;                // the plan kernel runs and the step launch follows its permutation (else: identity schedule)
     bool by_kind, regroup, skip_done;   // ... the plan kernel's arguments (read only with `sort`)

@@ -17,14 +17,6 @@ struct SwitchStatsArgs {
     unsigned long long *n_switched, *n_failed, *hist;   // [G], [G], [G][n_bins] (nullptr iff n_bins == 0): added to
 };
 
-// Launch rule: every lane runs one trial (L = 1) while that needs at most STG_SWITCH_STATS_WAVES wavefronts in all; beyond that the
-// wavefronts per condition are capped at max(1, STG_SWITCH_STATS_WAVES / G) and each lane loops over L trials.
-static inline void switch_stats_plan(int32_t G, int64_t R, int64_t* L, int32_t* waves_per_cond) {
-    const int64_t w1 = (R + 63) / 64;                              // wavefronts per condition at one trial per lane
-    int64_t cap = STG_SWITCH_STATS_WAVES / (int64_t)G;
-    if (cap < 1) cap = 1;
-    *L = w1 <= cap ? 1 : (w1 + cap - 1) / cap;
-    *waves_per_cond = (int32_t)((w1 + *L - 1) / *L);
-}
+// (the launch rule, switch_stats_plan, is host-only C++: stg_launch_plan.hpp, pinned by tests/test_switch_stats_plan_host.py)
 
 void stg_switch_stats_launch(const SwitchStatsArgs& a, int solver, bool thermal, bool multi, hipStream_t st);

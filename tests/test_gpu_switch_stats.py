@@ -25,11 +25,12 @@ import torch
 
 import brown_ref as br
 from helpers import Guarded
+# the references, shared with tests/test_gpu_switch_stats_config.py and the CPU tests of the oracle comparison
+from switch_stats_ref import (G, SEED, backend as _backend, bins as _bins, conditions as _conditions, host_counts as _host_counts,  # noqa: F401
+                              host_path as _host_path, params as _params, proj as _proj)
 
 pytestmark = pytest.mark.gpu
 
-SEED = 41
-G = 3
 SMALL_R = (1, 63, 64, 65, 130)
 FORMS = (("rk4", "brown"), ("euler", "brown"), ("rk4", "ou"), ("rk4", "white"), ("rk45", "white"))
 
@@ -39,76 +40,6 @@ def stg():
     import spin_torque_gym_amd as s
     assert torch.cuda.is_available(), "these tests need the GPU"
     return s
-
-
-def _params(volume=br.SWITCH["volume"]):
-    return br.physics_params(volume, br.SWITCH["damping"])
-
-
-def _conditions():
-    """m0 [G,3] a little above the equator, J [G], T [G] (20, 60, 100 ps), target -z.  The NumPy restatement (tests/brown_ref.py, NumPy's
-    own generator, 1500 samples) switches 0.36, ~0.6 and ~0.45 of the trials of these conditions under the Brown field"""
-    mz = np.array([0.1, 0.2, 0.3])
-    ph = np.array([0.3, 1.7, 4.0])
-    s = np.sqrt(1.0 - mz * mz)
-    m0 = np.stack([s * np.cos(ph), s * np.sin(ph), mz], axis=1)
-    J = br.SWITCH["J"] * np.array([0.5, 0.6, 0.45])
-    T = np.array([2e-11, 6e-11, 1e-10])
-    return m0, J, T, np.tile([0.0, 0.0, -1.0], (G, 1))
-
-
-def _backend(stg, solver, noise, n, tables=None, cls=None, env_id0=0, **cfg):
-    from spin_torque_gym_amd.backend import EnvConfig, HipBackend
-    b = HipBackend(n, EnvConfig(solver=solver, include_thermal_fluctuations=True, noise_model=noise, seed=SEED, **cfg), 0, env_id0)
-    tables = [_params()] if tables is None else tables
-    b.set_params([stg.flatten_params(stg.DeviceFactory().create_device("stt_mram", p)) for p in tables], cls)
-    return b
-
-
-def _proj(m, tgt):
-    """the header's projection, [n] from m [3,n] and target rows [n,3]: ((mx tx) + (my ty)) + (mz tz), each operation rounded"""
-    return ((m[0] * tgt[:, 0]) + (m[1] * tgt[:, 1])) + (m[2] * tgt[:, 2])
-
-
-def _bins(proj, n_bins):
-    """the header's bin rule: min(n_bins - 1, max(0, (int)floor((proj + 1.0) * (0.5 * n_bins)))); NaN -> bin 0"""
-    b = np.floor((proj + 1.0) * (0.5 * n_bins))
-    b = np.where(np.isnan(b), 0.0, b)
-    return np.minimum(n_bins - 1, np.maximum(0, b)).astype(np.int64)
-
-
-def _host_path(stg, solver, noise, m0, J, T, tgt, R, env_step=0, tables=None, cond_cls=None, **cfg):
-    """The existing path: stg_solve over the G R replicated problems (problem g R + r = trial r of condition g), one call per phase at
-    env_step + p with m_final fed back as m0; a phase with T == 0 is skipped, a row whose solve failed keeps the m that solve handed
-    back and takes no further phase.  J, T [P,G].  Returns (m_final [3, G R], failed [G R]) as NumPy arrays."""
-    g = m0.shape[0]
-    n = g * R
-    cls = None if cond_cls is None else np.repeat(cond_cls, R).astype(np.uint8)
-    b = _backend(stg, solver, noise, n, tables, cls, **cfg)
-    m = torch.from_numpy(np.repeat(m0, R, axis=0).T.copy()).cuda()
-    failed = torch.zeros(n, dtype=torch.bool, device="cuda")
-    for p in range(J.shape[0]):
-        Tp = torch.from_numpy(np.repeat(T[p], R)).cuda()
-        out = b.solve(m, torch.from_numpy(np.repeat(J[p], R)), Tp, env_step=env_step + p)
-        live = ~failed & (Tp != 0.0)
-        m = torch.where(live[None, :], out["m_final"], m)
-        failed = failed | (live & (out["success"] == 0))
-    torch.cuda.synchronize()
-    res = m.cpu().numpy(), failed.cpu().numpy()
-    b.close()
-    return res
-
-
-def _host_counts(m, failed, tgt, R, threshold=0.0, n_bins=0):
-    g = tgt.shape[0]
-    proj = _proj(m, np.repeat(tgt, R, axis=0))
-    n_sw = (proj > threshold).reshape(g, R).sum(axis=1)
-    n_failed = failed.reshape(g, R).sum(axis=1)
-    hist = None
-    if n_bins:
-        b = _bins(proj, n_bins).reshape(g, R)
-        hist = np.stack([np.bincount(row, minlength=n_bins) for row in b])
-    return n_sw, n_failed, hist
 
 
 def _median_threshold(m, tgt, R, g=1):
