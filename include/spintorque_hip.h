@@ -412,6 +412,40 @@ int stg_switch_stats(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t
                      const double* target, double threshold, int32_t n_bins, unsigned long long* n_switched,
                      unsigned long long* n_failed, unsigned long long* hist, void* stream);
 
+/* stg_switch_stats with ONE phase of the trial, `wave_phase`, driven by piecewise-linear tables: a shaped current pulse (rise time,
+ * pre-emphasis, bipolar tails) and / or an applied field, per condition.  Like stg_switch_stats it holds no per-trial memory: a
+ * condition's tables are read once per wavefront, whatever R is.
+ *
+ * Tables: layout, value rule, knot limits and validity are those of stg_solve_wave above with N = G (condition index fastest):
+ * tj, jk double[kj][G]; th double[kh][G]; hk double[kh][3][G].  Times are in seconds, t = 0 at the START OF THE WAVE PHASE; there is no
+ * built-in t <= T gate.  (A bias field across equilibrate, pulse and relax is one phase whose tables cover the whole trial.)
+ *   kj = 0: the wave phase's current is the rectangular J[wave_phase][g] while t <= T[wave_phase][g].  With kj > 0 that J entry is not
+ *           read; with kj > 0 and P == 1 no J entry is, and J may be NULL.
+ *   kh = 0: zero field.
+ *   kj = kh = 0 is STG_E_INVALID: the call for it is stg_switch_stats.
+ *
+ * Stream rule: trial r (trial0 <= r < trial0 + R) of condition g IS problem i = g * trial_stride + r.  Phase wave_phase is its solve of
+ * stg_solve_wave with (m, T[wave_phase][g], condition g's tables) at Philox counter word env_step + wave_phase; every other phase p is
+ * its solve of stg_solve with (m, J[p][g], T[p][g]) at env_step + p -- all modulo 2^32, on the stream of env id env_id0 + i, with the
+ * context's solver, thermal field and class row.  With P = 1 and trial_stride = R the G * R trials are the problems of ONE
+ * stg_solve_wave over the arrays and the tables replicated R times per condition, and the counts equal the host's reduction of that
+ * call's m_final and success exactly.
+ * Table CONTENTS are checked on the device, once per wavefront: a condition whose table is not strictly increasing or not finite has
+ * the wave phase of every trial fail as in stg_solve_wave -- m stays the phase's input m, the trial ends there, adds one to
+ * n_failed[g] and is classified like any other; the other conditions are not affected.
+ *
+ * Everything else is stg_switch_stats word for word: a phase with T[p][g] == 0.0 exactly is skipped (the wave phase too, bad table
+ * or not), a failed phase ends the trial, the classification and the bin arithmetic, cond_cls, the launch rule; the call ADDS to
+ * n_switched[G], n_failed[G] and hist[G][n_bins] and touches no other memory; it enqueues kernels only (no allocation, no
+ * synchronisation); per-env parameters return STG_E_STATE.  STG_E_INVALID with nothing launched: the causes stg_switch_stats lists
+ * (J == NULL only where J is read, above), wave_phase outside [0, P), a knot count of 1, negative or above STG_MAX_KNOTS, a missing
+ * table pointer for a positive knot count, kj = kh = 0.  R == 0 is valid and does nothing. */
+int stg_switch_stats_wave(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t P,
+                          const double* m0, const double* J, const double* T, int32_t wave_phase, int32_t kj, const double* tj,
+                          const double* jk, int32_t kh, const double* th, const double* hk, const uint8_t* cond_cls,
+                          uint32_t env_step, const double* target, double threshold, int32_t n_bins,
+                          unsigned long long* n_switched, unsigned long long* n_failed, unsigned long long* hist, void* stream);
+
 /* SpinTorqueEnv.step for all N envs with the drive of stg_solve_wave: current_func(t) and field_func(t) as piecewise-linear tables
  * in place of the rectangular pulse in zero field of stg_step (spin_torque_env.py:442-447).
  *

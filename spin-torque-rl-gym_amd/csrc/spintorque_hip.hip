@@ -14,6 +14,7 @@
 #include "stg_kernels.hpp"
 #include "stg_wave.hpp"
 #include "stg_switch_stats.hpp"
+#include "stg_switch_stats_wave.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -1030,14 +1031,17 @@ int stg_solve_wave(stg_ctx* ctx, const double* m0, const double* J, const double
     return STG_OK;
 }
 
-// Monte-Carlo switching statistics: its kernels live in stg_switch_stats.hip (stg_switch_stats_launch)
-int stg_switch_stats(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t P, const double* m0, const double* J,
-                     const double* T, const uint8_t* cond_cls, uint32_t env_step, const double* target, double threshold, int32_t n_bins,
-                     unsigned long long* n_switched, unsigned long long* n_failed, unsigned long long* hist, void* stream) {
+// Monte-Carlo switching statistics: its kernels live in stg_switch_stats.hip (stg_switch_stats_launch) and, with one waveform phase,
+// in stg_switch_stats_wave.hip (stg_switch_stats_wave_launch).  The argument checks and the argument block the two entries share;
+// `need_J`: whether a NULL J is refused here.
+static int switch_stats_args(stg_ctx* ctx, const char* what, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t P,
+                             const double* m0, const double* J, const double* T, const uint8_t* cond_cls, uint32_t env_step,
+                             const double* target, double threshold, int32_t n_bins, unsigned long long* n_switched,
+                             unsigned long long* n_failed, unsigned long long* hist, bool need_J, SwitchStatsArgs& a) {
     if (!ctx) return fail(STG_E_INVALID, "ctx is NULL");
-    if (!ctx->have_params) return fail(STG_E_STATE, "stg_set_params must precede stg_switch_stats");
-    if (ctx->per_env) return fail(STG_E_STATE, "stg_switch_stats works on the class table (stg_set_params), not on per-env parameters");
-    if (!m0 || !J || !T || !target || !n_switched || !n_failed) return fail(STG_E_INVALID, "m0/J/T/target/n_switched/n_failed must not be NULL");
+    if (!ctx->have_params) return fail(STG_E_STATE, std::string("stg_set_params must precede ") + what);
+    if (ctx->per_env) return fail(STG_E_STATE, std::string(what) + " works on the class table (stg_set_params), not on per-env parameters");
+    if (!m0 || (need_J && !J) || !T || !target || !n_switched || !n_failed) return fail(STG_E_INVALID, "m0/J/T/target/n_switched/n_failed must not be NULL");
     if (G < 1) return fail(STG_E_INVALID, "G must be >= 1");
     if (R < 0) return fail(STG_E_INVALID, "R must be >= 0");
     if (P < 1 || P > STG_MAX_PHASES) return fail(STG_E_INVALID, "P must be in 1 ... STG_MAX_PHASES");
@@ -1047,18 +1051,50 @@ int stg_switch_stats(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t
     if (R > INT64_MAX - trial0 || trial_stride < trial0 + R)
         return fail(STG_E_INVALID, "trial_stride must be >= trial0 + R (the streams of two conditions would overlap)");
     if (trial_stride > (INT64_MAX - ctx->env_id0) / (int64_t)G) return fail(STG_E_INVALID, "env_id0 + G * trial_stride exceeds int64");
-    if (R == 0) return STG_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    SwitchStatsArgs a{};
     a.c = cfg_view(ctx->cfg); a.env_id0 = ctx->env_id0;
     a.R = R; a.trial0 = trial0; a.trial_stride = trial_stride;
-    switch_stats_plan(G, R, &a.L, &a.waves_per_cond);
+    if (R > 0) switch_stats_plan(G, R, &a.L, &a.waves_per_cond);
     a.G = G; a.P = P; a.n_bins = n_bins; a.ncls = ctx->ncls;
     a.ctab = ctx->ctab; a.cond_cls = cond_cls;
     a.m0 = m0; a.J = J; a.T = T; a.target = target; a.threshold = threshold; a.env_step = env_step;
     a.n_switched = n_switched; a.n_failed = n_failed; a.hist = hist;
+    return STG_OK;
+}
+
+int stg_switch_stats(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t P, const double* m0, const double* J,
+                     const double* T, const uint8_t* cond_cls, uint32_t env_step, const double* target, double threshold, int32_t n_bins,
+                     unsigned long long* n_switched, unsigned long long* n_failed, unsigned long long* hist, void* stream) {
+    SwitchStatsArgs a{};
+    if (int rc = switch_stats_args(ctx, "stg_switch_stats", G, R, trial0, trial_stride, P, m0, J, T, cond_cls, env_step, target, threshold, n_bins,
+                                   n_switched, n_failed, hist, true, a)) return rc;
+    if (R == 0) return STG_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
     const bool thermal = ctx->cfg.solver == STG_SOLVER_RK45 ? ctx->cfg.thermal != 0 : (ctx->cfg.thermal && ctx->cfg.temperature > 0);
     stg_switch_stats_launch(a, ctx->cfg.solver, thermal, ctx->ncls > 1 && cond_cls != nullptr, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return STG_OK;
+}
+
+int stg_switch_stats_wave(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t P, const double* m0, const double* J,
+                          const double* T, int32_t wave_phase, int32_t kj, const double* tj, const double* jk, int32_t kh, const double* th,
+                          const double* hk, const uint8_t* cond_cls, uint32_t env_step, const double* target, double threshold, int32_t n_bins,
+                          unsigned long long* n_switched, unsigned long long* n_failed, unsigned long long* hist, void* stream) {
+    SwitchStatsWaveArgs w{};
+    // (J is read for the rectangular phases, and for the wave phase without a current table: a single tabled phase needs none)
+    if (int rc = switch_stats_args(ctx, "stg_switch_stats_wave", G, R, trial0, trial_stride, P, m0, J, T, cond_cls, env_step, target, threshold,
+                                   n_bins, n_switched, n_failed, hist, !(P == 1 && kj > 0), w.s)) return rc;
+    if (wave_phase < 0 || wave_phase >= P) return fail(STG_E_INVALID, "wave_phase must be in 0 ... P - 1");
+    if (kj != 0 && (kj < 2 || kj > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kj must be 0 or 2 ... STG_MAX_KNOTS");
+    if (kh != 0 && (kh < 2 || kh > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kh must be 0 or 2 ... STG_MAX_KNOTS");
+    if (kj == 0 && kh == 0) return fail(STG_E_INVALID, "kj = kh = 0: no waveform, use stg_switch_stats");
+    if (kj != 0 && (!tj || !jk)) return fail(STG_E_INVALID, "tj/jk must not be NULL with kj > 0");
+    if (kh != 0 && (!th || !hk)) return fail(STG_E_INVALID, "th/hk must not be NULL with kh > 0");
+    if (R == 0) return STG_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    w.wave_phase = wave_phase;
+    w.kj = kj; w.tj = tj; w.jk = jk; w.kh = kh; w.th = th; w.hk = hk;
+    const bool thermal = ctx->cfg.solver == STG_SOLVER_RK45 ? ctx->cfg.thermal != 0 : (ctx->cfg.thermal && ctx->cfg.temperature > 0);
+    stg_switch_stats_wave_launch(w, ctx->cfg.solver, thermal, ctx->ncls > 1 && cond_cls != nullptr, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return STG_OK;
 }

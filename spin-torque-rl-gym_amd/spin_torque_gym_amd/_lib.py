@@ -84,6 +84,8 @@ SYMBOLS = {
                                  _VP, _VP, _VP, _VP]),
     "stg_switch_stats": (C.c_int, [_VP, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _VP, _VP, _VP, _VP, C.c_uint32, _VP, C.c_double,
                                    C.c_int32, _VP, _VP, _VP, _VP]),
+    "stg_switch_stats_wave": (C.c_int, [_VP, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP,
+                                        C.c_int32, _VP, _VP, _VP, C.c_uint32, _VP, C.c_double, C.c_int32, _VP, _VP, _VP, _VP]),
     "stg_step_wave": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                 _VP]),
     "stg_set_pulse_shape": (C.c_int, [_VP, C.c_int32, _VP, _VP, C.c_int32, _VP, _VP]),

@@ -291,10 +291,11 @@ class HipBackend:
         return self._one_step(lambda a, f64, outs: self.lib.stg_step_many(self._ctx, 1, _ptr(a), f64, 1, int(bool(autoreset)), *outs,
                                                                           self._stream()), actions, autoreset, out)
 
-    def _wave_tables(self, wave):
+    def _wave_tables(self, wave, n=None):
         """wave = dict(current=(tj [K,N], jk [K,N]) | None, field=(th [K,N], hk [K,3,N]) | None) -> (kj, tj, jk, kh, th, hk) on the
-        device, as stg_solve_wave / stg_step_wave take them (a missing table: knot count 0, no pointers)."""
-        n = self.n
+        device, as stg_solve_wave / stg_step_wave take them (a missing table: knot count 0, no pointers).  n: the number of columns
+        (None: the context's envs; stg_switch_stats_wave has one column per condition)."""
+        n = self.n if n is None else n
         tj = jk = th = hk = None
         kj = kh = 0
         if wave.get("current") is not None:
@@ -576,6 +577,35 @@ class HipBackend:
                                              _ptr(target), float(threshold), int(n_bins), _ptr(n_sw), _ptr(n_failed), _ptr(hist),
                                              self._stream()))
         self._keep = (m0, J, T, target, cond_cls)
+        return out
+
+    def switch_stats_wave(self, m0, J, T, target, n_trials, wave, wave_phase=0, trial0=0, trial_stride=None, cond_cls=None, env_step=0,
+                          threshold=0.0, n_bins=0, out=None):
+        """switch_stats with phase `wave_phase` driven by piecewise-linear tables (stg_switch_stats_wave): wave = dict(current=(tj [K,G],
+        jk [K,G]) | None, field=(th [K,G], hk [K,3,G]) | None) as solve(wave=) takes it, one column per CONDITION; times in seconds from
+        the start of that phase.  A missing current table means the rectangular J[wave_phase], a missing field table zero field (not
+        both).  The other phases are the rectangular J, T [P,G] of switch_stats; trial r of condition g is problem g * trial_stride + r
+        of `solve(wave=)` at env_step + wave_phase and of `solve` at the other phases' env_step + p.  Returns and `out` as switch_stats."""
+        dev = self.device
+        m0 = self._dev(m0, torch.float64)
+        g = int(m0.shape[-1])
+        m0 = self._dev(m0, torch.float64, (3, g))
+        J, T = self._dev(J, torch.float64), self._dev(T, torch.float64)
+        p = int(T.shape[0])
+        J, T = self._dev(J, torch.float64, (p, g)), self._dev(T, torch.float64, (p, g))
+        target = self._dev(target, torch.float64, (3, g))
+        cond_cls = self._dev(cond_cls, torch.uint8, (g,))
+        kj, tj, jk, kh, th, hk = self._wave_tables(wave, g)
+        r, t0 = int(n_trials), int(trial0)
+        stride = t0 + r if trial_stride is None else int(trial_stride)
+        if out is None:
+            out = (torch.zeros(g, dtype=torch.int64, device=dev), torch.zeros(g, dtype=torch.int64, device=dev),
+                   torch.zeros((g, int(n_bins)), dtype=torch.int64, device=dev) if n_bins > 0 else None)
+        n_sw, n_failed, hist = out
+        _lib.check(self.lib.stg_switch_stats_wave(self._ctx, g, r, t0, stride, p, _ptr(m0), _ptr(J), _ptr(T), int(wave_phase), kj, _ptr(tj),
+                                                  _ptr(jk), kh, _ptr(th), _ptr(hk), _ptr(cond_cls), int(env_step), _ptr(target),
+                                                  float(threshold), int(n_bins), _ptr(n_sw), _ptr(n_failed), _ptr(hist), self._stream()))
+        self._keep = (m0, J, T, target, cond_cls, tj, jk, th, hk)
         return out
 
     def device_terms(self, m, J, volt):

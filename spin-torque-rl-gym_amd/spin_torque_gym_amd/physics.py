@@ -24,6 +24,7 @@ SimpleLLGSSolver here always applies RobustLLGSSolver's gates, because that is t
 the two classes differ only in their constructor signature.  The result cache of the reference (keyed
 without J, stale hits) is deliberately not reproduced.
 """
+import functools
 import warnings
 from typing import Any, Callable, Dict, Optional, Tuple
 
@@ -229,7 +230,7 @@ class _GpuSolverBase:
     def switching_statistics(self, m_initial, current, duration, device_params, n_trials: int, *, equilibrate=0.0, relax=0.0,
                              target=(0.0, 0.0, -1.0), threshold: float = 0.0, n_bins: int = 0, temperature: float = 300.0,
                              device_type="stt_mram", class_index=None, env_step: int = 0, trial_offset: int = 0, trial_stride=None,
-                             max_trials_per_launch: int = 2 ** 22) -> Dict[str, Any]:
+                             max_trials_per_launch: int = 2 ** 22, current_knots=None, field_knots=None) -> Dict[str, Any]:
         """Monte-Carlo switching statistics of G conditions with R = n_trials thermal trials each, with the trial loop and the
         reduction on the GPU (stg_switch_stats): no per-trial array exists, so R is bounded by time, not by memory.
 
@@ -246,6 +247,13 @@ class _GpuSolverBase:
         The trials run in launches of at most max_trials_per_launch per condition, which keeps each kernel short on a shared
         device; the counts do not depend on it.  The thermal field is on (choose its model with the constructor's noise_model).
 
+        current_knots = (tk, jk) and / or field_knots = (tk, hk) shape the pulse (stg_switch_stats_wave): piecewise-linear
+        current_func(t) and field_func(t) as in switching_probability and solve_batch -- tk [K] with jk [K] / hk [K,3] is one table
+        for all conditions, tk [K,G] with jk [K,G] / hk [K,G,3] one per condition; 2 <= K <= 32; t = 0 at the start of the pulse.
+        current and duration then describe that single pulse ([G] or [1,G]; current may be None with current_knots, which replaces
+        it); equilibrate and relax still add their rectangular J = 0 phases around it.  A condition whose table is not finite or not
+        strictly increasing fails its pulse in every trial.  The tables are held once per condition, not per trial.
+
         Returns dict(p_switch [G] = n_switched / R, wer [G] = 1 - p_switch, n_switched [G], n_failed [G],
         stderr [G] = sqrt(p (1 - p) / R), hist [G,n_bins], bin_edges [n_bins + 1] (empty without bins))."""
         m0 = np.asarray(m_initial.cpu() if torch.is_tensor(m_initial) else m_initial, dtype=np.float64).reshape(-1, 3)
@@ -256,11 +264,22 @@ class _GpuSolverBase:
             raise ValueError("max_trials_per_launch must be >= 1")
         if not 0 <= int(n_bins) <= 64:
             raise ValueError("n_bins must be in 0 ... 64")
+        wave = None
+        if current_knots is not None or field_knots is not None:
+            wave = {"current": _knot_tables(current_knots, g, 1, "current_knots"), "field": _knot_tables(field_knots, g, 3, "field_knots")}
+            wave = {k: None if v is None else tuple(torch.from_numpy(a) for a in v) for k, v in wave.items()}
+        if current is None:
+            if current_knots is None:
+                raise ValueError("current is required without current_knots")
+            current = np.zeros(np.shape(duration))
         J, T = (np.asarray(x, dtype=np.float64) for x in (current, duration))
         J, T = (np.broadcast_to(x, (g,))[None, :] if x.ndim <= 1 else x for x in (J, T))
+        if wave is not None and (J.shape[0] != 1 or T.shape[0] != 1):
+            raise ValueError("with current_knots / field_knots, current and duration describe the one shaped pulse: shape [G] or [1,G]")
         if J.shape != T.shape or J.ndim != 2 or J.shape[1] != g:
             raise ValueError(f"current and duration must both have shape [G] or [P,G] with G = {g}, got {J.shape} and {T.shape}")
         phases = [(J, T)]
+        wave_phase = 0                      # (the pulse's place in the chain: behind the equilibration, if there is one)
         for where, t in ((0, equilibrate), (1, relax)):
             t = np.broadcast_to(np.asarray(t, dtype=np.float64), (g,))
             if (t < 0).any():
@@ -268,6 +287,7 @@ class _GpuSolverBase:
             if (t > 0).any():
                 ph = (np.zeros((1, g)), t[None, :])
                 phases = [ph] + phases if where == 0 else phases + [ph]
+                wave_phase += where == 0
         J, T = (np.ascontiguousarray(np.concatenate([ph[k] for ph in phases], axis=0)) for k in (0, 1))
         if J.shape[0] > 4:
             raise ValueError(f"a trial has at most 4 phases (equilibrate and relax included), got {J.shape[0]}")
@@ -294,10 +314,12 @@ class _GpuSolverBase:
         try:
             b.set_params([_flat_for(p, t, self._validate_params) for p, t in zip(tables, types)], cls)
             out, step = None, int(max_trials_per_launch)
+            # (without knots: exactly the rectangular call; a backend without waveforms is never asked for them)
+            launch = b.switch_stats if wave is None else functools.partial(b.switch_stats_wave, wave=wave, wave_phase=int(wave_phase))
             for done in range(0, r, step):
-                out = b.switch_stats(torch.from_numpy(np.ascontiguousarray(m0.T)), torch.from_numpy(J), torch.from_numpy(T),
-                                     torch.from_numpy(tgt), min(step, r - done), trial0=int(trial_offset) + done, trial_stride=stride,
-                                     cond_cls=cls, env_step=env_step, threshold=float(threshold), n_bins=int(n_bins), out=out)
+                out = launch(torch.from_numpy(np.ascontiguousarray(m0.T)), torch.from_numpy(J), torch.from_numpy(T),
+                             torch.from_numpy(tgt), min(step, r - done), trial0=int(trial_offset) + done, trial_stride=stride,
+                             cond_cls=cls, env_step=env_step, threshold=float(threshold), n_bins=int(n_bins), out=out)
             n_sw, n_failed = (x.cpu().numpy().astype(np.int64) for x in out[:2])
             hist = out[2].cpu().numpy().astype(np.int64) if n_bins > 0 else np.zeros((g, 0), dtype=np.int64)
         finally:
