@@ -446,6 +446,46 @@ int stg_switch_stats_wave(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, in
                           uint32_t env_step, const double* target, double threshold, int32_t n_bins,
                           unsigned long long* n_switched, unsigned long long* n_failed, unsigned long long* hist, void* stream);
 
+/* stg_switch_stats / stg_switch_stats_wave with the question WHEN a trial switched answered for ONE phase of the trial, the watched
+ * phase `watch_phase`: the first passage of m . target over `threshold` during that phase, reduced to integer counts.  Like its
+ * siblings it holds no per-trial memory (the route through stg_solve_traj costs (n + 1) * 32 bytes per trial).
+ *
+ * Trials, streams, phases, cond_cls, the class table, the launch rule, n_switched / n_failed / hist with their classification and bin
+ * arithmetic are those of stg_switch_stats_wave word for word, with watch_phase in the place of wave_phase: the tables (layout, knot
+ * limits, validity, t = 0 at the start of the watched phase, a bad table fails that phase of every trial of its condition, J == NULL
+ * only where J is not read) drive the watched phase.  kj = kh = 0 is VALID here: the watched phase is then the rectangular solve of
+ * stg_solve, and the three old outputs are those of stg_switch_stats on the same arguments, bit for bit.
+ *
+ * The watched phase's points are the rows stg_solve_traj records for that solve with an unlimited traj_cap (with tables: the rows of
+ * stg_solve_wave with traj_cap > 0): row k = 0 ... n_points has time t_k and magnetisation m_k, row 0 is t = 0; RK45: the
+ * renormalised output row of every accepted point.  In IEEE fp64 without FMA contraction:
+ *   proj_k = ((m_k.x * target[0][g]) + (m_k.y * target[1][g])) + (m_k.z * target[2][g])
+ *   the trial crosses at the FIRST k with proj_k > threshold                  (a NaN never crosses)
+ *   t_x = 0.0 for k = 0, else 0.5 * (t_{k-1} + t_k)                           (each operation rounded)
+ *   bin = min(n_tbins - 1, max(0, (int)floor(t_x * ((double)n_tbins / T[watch_phase][g]))))     (clamped before the conversion)
+ * i.e. n_tbins equal bins over the watched phase's [0, T].  t_x is the midpoint of the interval in which the crossing happened: a
+ * better estimator than t_k, and one that keeps the point times of a fixed-step solve -- multiples of T / n -- off the bin edges in
+ * the usual case of n_tbins dividing n.
+ * A trial has NOT crossed when no row satisfies the test, when the watched phase is skipped (T == 0.0 exactly), when an earlier phase
+ * failed, or when the watched phase's own solve failed by any cause (rejected input, a mid-run reset, a bad table, RK45 out of
+ * attempts): whatever rows such a solve passed are discarded.
+ *   n_crossed[G]         trials that crossed
+ *   n_returned[G]        trials that crossed AND whose final classification is not "switched": back-hops, and pulses cut short by a
+ *                        later phase
+ *   t_hist[G][n_tbins]   the time histogram of the crossed trials; 0 <= n_tbins <= STG_MAX_TBINS, NULL iff n_tbins == 0
+ * The call ADDS to all six arrays and touches no other memory; it enqueues kernels only; per-env parameters return STG_E_STATE.
+ * STG_E_INVALID with nothing launched and nothing written: the causes stg_switch_stats_wave lists except kj = kh = 0, watch_phase
+ * outside [0, P), n_tbins out of range, n_crossed or n_returned NULL, t_hist NULL with n_tbins > 0 or non-NULL with n_tbins == 0.
+ * R == 0 is valid and does nothing. */
+#define STG_MAX_TBINS 1024
+int stg_switch_times(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t P,
+                     const double* m0, const double* J, const double* T, int32_t watch_phase,
+                     int32_t kj, const double* tj, const double* jk, int32_t kh, const double* th, const double* hk,
+                     const uint8_t* cond_cls, uint32_t env_step, const double* target, double threshold, int32_t n_bins,
+                     unsigned long long* n_switched, unsigned long long* n_failed, unsigned long long* hist,
+                     int32_t n_tbins, unsigned long long* n_crossed, unsigned long long* n_returned,
+                     unsigned long long* t_hist, void* stream);
+
 /* SpinTorqueEnv.step for all N envs with the drive of stg_solve_wave: current_func(t) and field_func(t) as piecewise-linear tables
  * in place of the rectangular pulse in zero field of stg_step (spin_torque_env.py:442-447).
  *

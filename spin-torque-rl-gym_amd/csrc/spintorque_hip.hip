@@ -15,6 +15,7 @@
 #include "stg_wave.hpp"
 #include "stg_switch_stats.hpp"
 #include "stg_switch_stats_wave.hpp"
+#include "stg_switch_times.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -1032,7 +1033,8 @@ int stg_solve_wave(stg_ctx* ctx, const double* m0, const double* J, const double
 }
 
 // Monte-Carlo switching statistics: its kernels live in stg_switch_stats.hip (stg_switch_stats_launch) and, with one waveform phase,
-// in stg_switch_stats_wave.hip (stg_switch_stats_wave_launch).  The argument checks and the argument block the two entries share;
+// in stg_switch_stats_wave.hip (stg_switch_stats_wave_launch); with the first passage of a watched phase, in stg_switch_times.hip
+// (stg_switch_times_launch).  The argument checks and the argument block the three entries share;
 // `need_J`: whether a NULL J is refused here.
 static int switch_stats_args(stg_ctx* ctx, const char* what, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t P,
                              const double* m0, const double* J, const double* T, const uint8_t* cond_cls, uint32_t env_step,
@@ -1095,6 +1097,35 @@ int stg_switch_stats_wave(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, in
     w.kj = kj; w.tj = tj; w.jk = jk; w.kh = kh; w.th = th; w.hk = hk;
     const bool thermal = ctx->cfg.solver == STG_SOLVER_RK45 ? ctx->cfg.thermal != 0 : (ctx->cfg.thermal && ctx->cfg.temperature > 0);
     stg_switch_stats_wave_launch(w, ctx->cfg.solver, thermal, ctx->ncls > 1 && cond_cls != nullptr, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return STG_OK;
+}
+
+int stg_switch_times(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t P, const double* m0, const double* J,
+                     const double* T, int32_t watch_phase, int32_t kj, const double* tj, const double* jk, int32_t kh, const double* th,
+                     const double* hk, const uint8_t* cond_cls, uint32_t env_step, const double* target, double threshold, int32_t n_bins,
+                     unsigned long long* n_switched, unsigned long long* n_failed, unsigned long long* hist, int32_t n_tbins,
+                     unsigned long long* n_crossed, unsigned long long* n_returned, unsigned long long* t_hist, void* stream) {
+    SwitchTimesArgs x{};
+    SwitchStatsWaveArgs& w = x.w;
+    // (J as in stg_switch_stats_wave: not read for a single phase with a current table)
+    if (int rc = switch_stats_args(ctx, "stg_switch_times", G, R, trial0, trial_stride, P, m0, J, T, cond_cls, env_step, target, threshold,
+                                   n_bins, n_switched, n_failed, hist, !(P == 1 && kj > 0), w.s)) return rc;
+    if (watch_phase < 0 || watch_phase >= P) return fail(STG_E_INVALID, "watch_phase must be in 0 ... P - 1");
+    if (kj != 0 && (kj < 2 || kj > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kj must be 0 or 2 ... STG_MAX_KNOTS");
+    if (kh != 0 && (kh < 2 || kh > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kh must be 0 or 2 ... STG_MAX_KNOTS");
+    if (kj != 0 && (!tj || !jk)) return fail(STG_E_INVALID, "tj/jk must not be NULL with kj > 0");
+    if (kh != 0 && (!th || !hk)) return fail(STG_E_INVALID, "th/hk must not be NULL with kh > 0");
+    if (n_tbins < 0 || n_tbins > STG_MAX_TBINS) return fail(STG_E_INVALID, "n_tbins must be in 0 ... STG_MAX_TBINS");
+    if (!n_crossed || !n_returned) return fail(STG_E_INVALID, "n_crossed/n_returned must not be NULL");
+    if ((t_hist == nullptr) != (n_tbins == 0)) return fail(STG_E_INVALID, "t_hist must be NULL if and only if n_tbins == 0");
+    if (R == 0) return STG_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    w.wave_phase = watch_phase;
+    w.kj = kj; w.tj = tj; w.jk = jk; w.kh = kh; w.th = th; w.hk = hk;
+    x.n_tbins = n_tbins; x.n_crossed = n_crossed; x.n_returned = n_returned; x.t_hist = t_hist;
+    const bool thermal = ctx->cfg.solver == STG_SOLVER_RK45 ? ctx->cfg.thermal != 0 : (ctx->cfg.thermal && ctx->cfg.temperature > 0);
+    stg_switch_times_launch(x, ctx->cfg.solver, thermal, ctx->ncls > 1 && cond_cls != nullptr, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return STG_OK;
 }

@@ -214,9 +214,9 @@ __device__ __forceinline__ LlgsEnergyK load_energy(const double* r) {
     return LlgsEnergyK{r[C_KUV], r[C_EDEMAG], V3{r[C_RX], r[C_RY], r[C_RZ]}, V3{r[C_NX], r[C_NY], r[C_NZ]}};
 }
 
-template <int SOLVER, bool THERMAL, bool RECORD, bool AXIS_Z, bool DEVPHYS, class NSRC>
+template <int SOLVER, bool THERMAL, bool RECORD, bool AXIS_Z, bool DEVPHYS, class NSRC, class REC = Recorder>
 __device__ __forceinline__ SolveOut run_solver(const V3& m, double J, double T, const double* row, const CfgView& c,
-                                               const RngKey& rk, const Recorder& rec, NSRC& ns, bool enabled) {
+                                               const RngKey& rk, const REC& rec, NSRC& ns, bool enabled) {
     if (SOLVER == STG_SOLVER_RK45) {
         const LlgsK k = load_llgs(row);
         LlgsEnergyK ek{};

@@ -728,6 +728,9 @@ struct SolveOut {
 };
 
 // Optional trajectory recorder (stg_solve_traj): rows are written with env index fastest.
+// The solvers below take their per-point observer as a template parameter REC, Recorder by default: put(row, t, m, e, tq) const
+// is called for row 0 (t = 0) and every later point when RECORD is set, and the members e / tq say whether the RK45 by-products
+// are wanted at all (stg_switch_times.hpp has an observer that stores nothing: FirstPassage).
 struct Recorder {
     double* t;       // [cap][N]
     double* m;       // [cap][3][N]
@@ -735,6 +738,7 @@ struct Recorder {
     double* tq;      // [cap][N] or nullptr: |tau_stt| + |tau_fl| per accepted point (llgs_solver.py:159-172)
     int64_t N, i;
     int32_t cap;
+    static constexpr bool kByProducts = true;     // energy and torque norms may be asked for (e, tq)
     __device__ __forceinline__ void put(int32_t row, double tt, const V3& mm, double ee, double tqv = 0.0) const {
         if (row < cap) {
             if (t) t[(int64_t)row * N + i] = tt;
@@ -749,10 +753,10 @@ struct Recorder {
 };
 
 // A3 + A4 + A5: RobustLLGSSolver.solve -> SimpleLLGSSolver.solve, METHOD 0 = rk4, 1 = euler.
-template <int METHOD, bool THERMAL, bool RECORD, bool AXIS_Z, bool DEVPHYS, class NSRC>
+template <int METHOD, bool THERMAL, bool RECORD, bool AXIS_Z, bool DEVPHYS, class NSRC, class REC = Recorder>
 __device__ __forceinline__ SolveOut simple_solve(const V3& m0, double J, double T, const SimpleK& k, double pol,
                                                  double msv, bool class_valid, double temperature, double max_step,
-                                                 const RngKey& rk, const Recorder& rec, const DevTorque& dv, NSRC& ns,
+                                                 const RngKey& rk, const REC& rec, const DevTorque& dv, NSRC& ns,
                                                  double inv_tau, bool enabled) {
 #pragma clang fp contract(off)
     SolveOut o{m0, 0, 0, 0, false};
@@ -1016,8 +1020,8 @@ __device__ __forceinline__ void llgs_masks_close(LlgsLane& L, const LlgsMasks& M
 
 // every accepted point is renormalised on output (llgs_solver.py:152-153); without a recorder only the last one is ever
 // read, so it is formed once after the loop (llgs_lane_finish)
-template <bool RECORD>
-__device__ __forceinline__ void llgs_lane_emit(LlgsLane& L, V3& out_m, const Recorder& rec, const LlgsEnergyK& ek) {
+template <bool RECORD, class REC = Recorder>
+__device__ __forceinline__ void llgs_lane_emit(LlgsLane& L, V3& out_m, const REC& rec, const LlgsEnergyK& ek) {
     const double inv = rsqrt_fast(dot(L.y, L.y));
     out_m = V3{L.y.x * inv, L.y.y * inv, L.y.z * inv};
     // (the recorded time points never pass T, so current_func(t) = J at every one of them)
@@ -1045,10 +1049,10 @@ __device__ __forceinline__ V3 llgs_draw(NSRC& ns, const LlgsK& k, bool even) {
 
 // Prologue of a solve: normalise m0 (llgs_solver.py:76), f(t0, y0), select_initial_step (common.py:68-134).
 // `enabled` = false: a lane that only walks its workgroup's chunk loop (SharedNormals).
-template <bool THERMAL, bool RECORD, bool AXIS_Z, class NSRC>
+template <bool THERMAL, bool RECORD, bool AXIS_Z, class NSRC, class REC = Recorder>
 __device__ __forceinline__ void llgs_lane_begin(LlgsLane& L, V3& out_m, const V3& m0, double J, double T, const LlgsK& k, double beta,
                                                 double betap, double rtol, double atol, double max_step, const RngKey& rk,
-                                                const Recorder& rec, const LlgsEnergyK& ek, NSRC& ns, bool enabled) {
+                                                const REC& rec, const LlgsEnergyK& ek, NSRC& ns, bool enabled) {
     const bool useJ = !(fabs(J) < 1e-12);                                   // llgs_solver.py:222
     L.bJ = useJ ? beta * J : 0.0;
     L.bpJ = useJ ? betap * J : 0.0;
@@ -1147,9 +1151,9 @@ __device__ __forceinline__ bool attempt_loop_more(lanemask& active, lanemask not
 // instead of sum-over-steps(max-over-lanes(attempts of that step)).
 // z2, z3: the thermal fields of the first two RHS calls of the attempt (fetched by the caller, see llgs_draw).
 // M: the loop's flags.  UNIFORM_IT: the caller's loop is one env per lane and takes arrived lanes out of M.active itself.
-template <bool THERMAL, bool RECORD, bool AXIS_Z, bool UNIFORM_IT, class NSRC>
+template <bool THERMAL, bool RECORD, bool AXIS_Z, bool UNIFORM_IT, class NSRC, class REC = Recorder>
 __device__ __forceinline__ void llgs_lane_attempt(LlgsLane& L, LlgsMasks& M, V3& out_m, const LlgsK& k, const Dp5Tab& tb, double rtol,
-                                                  double atol, double max_step, const Recorder& rec, const LlgsEnergyK& ek, NSRC& ns, V3& z2, V3& z3) {
+                                                  double atol, double max_step, const REC& rec, const LlgsEnergyK& ek, NSRC& ns, V3& z2, V3& z3) {
     constexpr double A21 = 1.0 / 5;
     constexpr double A31 = 3.0 / 40, A32 = 9.0 / 40;
     constexpr double A41 = 44.0 / 45, A42 = -56.0 / 15, A43 = 32.0 / 9;
@@ -1252,8 +1256,8 @@ __device__ __forceinline__ void llgs_lane_attempt(LlgsLane& L, LlgsMasks& M, V3&
 }
 
 // end of a solve: the final row (the input row when the solve failed), accepted points, attempts
-template <bool RECORD, class NSRC>
-__device__ __forceinline__ SolveOut llgs_lane_finish(LlgsLane& L, V3& out_m, const Recorder& rec, const LlgsEnergyK& ek, const NSRC& ns) {
+template <bool RECORD, class NSRC, class REC = Recorder>
+__device__ __forceinline__ SolveOut llgs_lane_finish(LlgsLane& L, V3& out_m, const REC& rec, const LlgsEnergyK& ek, const NSRC& ns) {
     SolveOut o{L.m0, 0, 0, 0, false};
     if (!RECORD) { llgs_lane_emit<RECORD>(L, out_m, rec, ek); --L.npts; }
     o.m = out_m;
@@ -1266,10 +1270,10 @@ __device__ __forceinline__ SolveOut llgs_lane_finish(LlgsLane& L, V3& out_m, con
 }
 
 // A7 (+A8 when RECORD): scipy solve_ivp(RK45) as LLGSSolver.solve drives it, one env per lane from start to end.
-template <bool THERMAL, bool RECORD, bool AXIS_Z, class NSRC>
+template <bool THERMAL, bool RECORD, bool AXIS_Z, class NSRC, class REC = Recorder>
 __device__ __forceinline__ SolveOut llgs_solve(const V3& m0, double J, double T, const LlgsK& k, double beta,
                                                double betap, double rtol, double atol, double max_step,
-                                               int64_t max_attempts, const RngKey& rk, const Recorder& rec,
+                                               int64_t max_attempts, const RngKey& rk, const REC& rec,
                                                const LlgsEnergyK& ek, NSRC& ns, bool enabled) {
     const Dp5Tab tb = make_dp5_tab();
     const V3 zero{0.0, 0.0, 0.0};

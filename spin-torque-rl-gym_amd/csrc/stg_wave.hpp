@@ -263,10 +263,10 @@ __device__ __forceinline__ V3 simple_rhs_wave(const V3& m, const SimpleK& k, dou
 // simple_solve with the drive evaluated per RHS call at that call's own time (simple_solver.py:290-293,324-326,364-367): stage times
 // t_i = i dt (np.linspace), t_i + dt/2, t_i + dt, in exactly those roundings.  One env per lane, normals inline, reference torque model.
 // ngeff = -gamma/(1+alpha^2).
-template <int METHOD, bool THERMAL, bool RECORD, class WS>
+template <int METHOD, bool THERMAL, bool RECORD, class WS, class REC = Recorder>
 __device__ __forceinline__ SolveOut simple_solve_wave(const V3& m0, double T, const SimpleK& k, double ngeff, double pol, double msv,
                                                       bool class_valid, double temperature, double max_step, const RngKey& rk,
-                                                      const Recorder& rec, InlineNormals& ns, double inv_tau, WS& src) {
+                                                      const REC& rec, InlineNormals& ns, double inv_tau, WS& src) {
 #pragma clang fp contract(off)
     SolveOut o{m0, 0, 0, 0, false};
     // robust_solver.py:152-190 (_validate_inputs); any failure ends in the fallback result (:140-150)
@@ -413,23 +413,28 @@ __device__ __forceinline__ V3 llgs_fun_wave(bool has_h, const LlgsDrive& d, cons
 // llgs_lane_emit with the by-products taken at the point's own time: energy includes the Zeeman term -mu0 Ms V m.h_applied
 // (llgs_solver.py:250), torques use current(t) (llgs_solver.py:161,169-172).  `src` is the solve's own cursor pair, which stands at or
 // before L.t.
-template <bool RECORD, class WS>
-__device__ __forceinline__ void llgs_lane_emit_wave(LlgsLane& L, V3& out_m, const Recorder& rec, const LlgsEnergyK& ek, WS& src,
+template <bool RECORD, class WS, class REC = Recorder>
+__device__ __forceinline__ void llgs_lane_emit_wave(LlgsLane& L, V3& out_m, const REC& rec, const LlgsEnergyK& ek, WS& src,
                                                     const LlgsWaveK& wk) {
     const double inv = rsqrt_fast(dot(L.y, L.y));
     out_m = V3{L.y.x * inv, L.y.y * inv, L.y.z * inv};
     if (RECORD) {
-        const LlgsDrive d = llgs_drive(src, wk, L.t);
-        const double e = rec.e ? -wk.mu0msv * dot(out_m, d.h) + llgs_energy(out_m, ek) : 0.0;
-        rec.put(L.npts, L.t, out_m, e, rec.tq ? llgs_torque_norms(out_m, d.bJ, d.bpJ) : 0.0);
+        if constexpr (REC::kByProducts) {
+            const LlgsDrive d = llgs_drive(src, wk, L.t);
+            const double e = rec.e ? -wk.mu0msv * dot(out_m, d.h) + llgs_energy(out_m, ek) : 0.0;
+            rec.put(L.npts, L.t, out_m, e, rec.tq ? llgs_torque_norms(out_m, d.bJ, d.bpJ) : 0.0);
+        } else {
+            // (an observer that wants neither by-product: no drive lookup; the next attempt seeks the cursors to its start time itself)
+            rec.put(L.npts, L.t, out_m, 0.0, 0.0);
+        }
     }
     ++L.npts;
 }
 
 // llgs_lane_begin: f(t0, y0) sees the drive at t0 = 0, select_initial_step's second call the drive at t0 + h0 (common.py:117-118)
-template <bool THERMAL, bool RECORD, class WS>
+template <bool THERMAL, bool RECORD, class WS, class REC = Recorder>
 __device__ __forceinline__ void llgs_lane_begin_wave(LlgsLane& L, V3& out_m, const V3& m0, double T, const LlgsK& k, double rtol, double atol,
-                                                     double max_step, const RngKey& rk, const Recorder& rec, const LlgsEnergyK& ek,
+                                                     double max_step, const RngKey& rk, const REC& rec, const LlgsEnergyK& ek,
                                                      InlineNormals& ns, WS& src, const LlgsWaveK& wk) {
     L.bJ = 0.0; L.bpJ = 0.0;               // (unused here: the drive is per call)
     L.m0 = m0;
@@ -472,9 +477,9 @@ __device__ __forceinline__ void llgs_lane_begin_wave(LlgsLane& L, V3& out_m, con
 // 4/5, 8/9, 1 and -- f_new -- t + h (rk.py:64-68).  A rejected attempt retries from the same t with a smaller h, so the solve's cursors
 // (`src`) only ever move to the attempt's START time; the stage times are looked up with a copy that scans forward from there and is
 // dropped afterwards.
-template <bool THERMAL, bool RECORD, class WS>
+template <bool THERMAL, bool RECORD, class WS, class REC = Recorder>
 __device__ __forceinline__ void llgs_lane_attempt_wave(LlgsLane& L, LlgsMasks& M, V3& out_m, const LlgsK& k, const Dp5Tab& tb, double rtol,
-                                                       double atol, double max_step, const Recorder& rec, const LlgsEnergyK& ek,
+                                                       double atol, double max_step, const REC& rec, const LlgsEnergyK& ek,
                                                        InlineNormals& ns, WS& src, const LlgsWaveK& wk) {
     constexpr double A21 = 1.0 / 5;
     constexpr double A31 = 3.0 / 40, A32 = 9.0 / 40;
@@ -536,9 +541,9 @@ __device__ __forceinline__ void llgs_lane_attempt_wave(LlgsLane& L, LlgsMasks& M
 }
 
 // llgs_solve with waveforms: begin / gate / attempt / finish as there, one env per lane from start to end
-template <bool THERMAL, bool RECORD, class WS>
+template <bool THERMAL, bool RECORD, class WS, class REC = Recorder>
 __device__ __forceinline__ SolveOut llgs_solve_wave(const V3& m0, double T, const LlgsK& k, double rtol, double atol, double max_step,
-                                                    int64_t max_attempts, const RngKey& rk, const Recorder& rec, const LlgsEnergyK& ek,
+                                                    int64_t max_attempts, const RngKey& rk, const REC& rec, const LlgsEnergyK& ek,
                                                     InlineNormals& ns, WS& src, const LlgsWaveK& wk) {
     const Dp5Tab tb = make_dp5_tab();
     LlgsLane L;

@@ -608,6 +608,39 @@ class HipBackend:
         self._keep = (m0, J, T, target, cond_cls, tj, jk, th, hk)
         return out
 
+    def switch_times(self, m0, J, T, target, n_trials, watch_phase=0, wave=None, n_tbins=0, trial0=0, trial_stride=None, cond_cls=None,
+                     env_step=0, threshold=0.0, n_bins=0, out=None):
+        """switch_stats / switch_stats_wave plus the first passage of m . target over `threshold` during phase `watch_phase`
+        (stg_switch_times).  wave = None: that phase is the rectangular J[watch_phase]; wave = dict(current=..., field=...) as
+        switch_stats_wave takes it drives it.  A trial crosses at the first recorded point of the watched phase (the rows of
+        `solve(traj_cap=)`) beyond the threshold; its crossing time is the midpoint of that point and the one before, binned into
+        n_tbins equal bins over the phase's [0, T].  Returns (n_switched [G], n_failed [G], hist [G,n_bins] or None, n_crossed [G],
+        n_returned [G], t_hist [G,n_tbins] or None), int64 on the device -- n_returned: crossed, yet not switched at the trial's end.
+        The call ADDS to them: `out` = the tuple of an earlier call accumulates, None starts from zero.  Enqueues only."""
+        dev = self.device
+        m0 = self._dev(m0, torch.float64)
+        g = int(m0.shape[-1])
+        m0 = self._dev(m0, torch.float64, (3, g))
+        J, T = self._dev(J, torch.float64), self._dev(T, torch.float64)
+        p = int(T.shape[0])
+        J, T = self._dev(J, torch.float64, (p, g)), self._dev(T, torch.float64, (p, g))
+        target = self._dev(target, torch.float64, (3, g))
+        cond_cls = self._dev(cond_cls, torch.uint8, (g,))
+        kj, tj, jk, kh, th, hk = self._wave_tables(wave, g) if wave is not None else (0, None, None, 0, None, None)
+        r, t0 = int(n_trials), int(trial0)
+        stride = t0 + r if trial_stride is None else int(trial_stride)
+        if out is None:
+            zeros = lambda *shape: torch.zeros(shape, dtype=torch.int64, device=dev)
+            out = (zeros(g), zeros(g), zeros(g, int(n_bins)) if n_bins > 0 else None,
+                   zeros(g), zeros(g), zeros(g, int(n_tbins)) if n_tbins > 0 else None)
+        n_sw, n_failed, hist, n_cr, n_ret, t_hist = out
+        _lib.check(self.lib.stg_switch_times(self._ctx, g, r, t0, stride, p, _ptr(m0), _ptr(J), _ptr(T), int(watch_phase), kj, _ptr(tj),
+                                             _ptr(jk), kh, _ptr(th), _ptr(hk), _ptr(cond_cls), int(env_step), _ptr(target),
+                                             float(threshold), int(n_bins), _ptr(n_sw), _ptr(n_failed), _ptr(hist), int(n_tbins),
+                                             _ptr(n_cr), _ptr(n_ret), _ptr(t_hist), self._stream()))
+        self._keep = (m0, J, T, target, cond_cls, tj, jk, th, hk)
+        return out
+
     def device_terms(self, m, J, volt):
         """Device-class formulas per env: (tau_dl [3,N], tau_fl [3,N], k_eff [N]) for m [3,N], J [N], volt [N]."""
         n, dev = self.n, self.device

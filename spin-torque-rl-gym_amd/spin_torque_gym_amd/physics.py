@@ -230,7 +230,8 @@ class _GpuSolverBase:
     def switching_statistics(self, m_initial, current, duration, device_params, n_trials: int, *, equilibrate=0.0, relax=0.0,
                              target=(0.0, 0.0, -1.0), threshold: float = 0.0, n_bins: int = 0, temperature: float = 300.0,
                              device_type="stt_mram", class_index=None, env_step: int = 0, trial_offset: int = 0, trial_stride=None,
-                             max_trials_per_launch: int = 2 ** 22, current_knots=None, field_knots=None) -> Dict[str, Any]:
+                             max_trials_per_launch: int = 2 ** 22, current_knots=None, field_knots=None, time_bins: int = 0,
+                             watch_phase: int = 0) -> Dict[str, Any]:
         """Monte-Carlo switching statistics of G conditions with R = n_trials thermal trials each, with the trial loop and the
         reduction on the GPU (stg_switch_stats): no per-trial array exists, so R is bounded by time, not by memory.
 
@@ -255,7 +256,18 @@ class _GpuSolverBase:
         strictly increasing fails its pulse in every trial.  The tables are held once per condition, not per trial.
 
         Returns dict(p_switch [G] = n_switched / R, wer [G] = 1 - p_switch, n_switched [G], n_failed [G],
-        stderr [G] = sqrt(p (1 - p) / R), hist [G,n_bins], bin_edges [n_bins + 1] (empty without bins))."""
+        stderr [G] = sqrt(p (1 - p) / R), hist [G,n_bins], bin_edges [n_bins + 1] (empty without bins)).
+
+        time_bins > 0 (at most 1024) also answers WHEN the trials switched (stg_switch_times): during the pulse -- with current /
+        duration given as [P,G], phase watch_phase of them -- a trial crosses at the first integrator point with m . target >
+        threshold; its crossing time is the midpoint of that point and the one before it, binned into time_bins equal bins over the
+        pulse's [0, duration].  The result gains n_crossed [G], n_returned [G] (crossed, yet not switched at the trial's end:
+        back-hops, pulses cut short by a later phase), p_cross [G] = n_crossed / R, t_hist [G,time_bins], t_edges [G,time_bins + 1]
+        (per condition: the durations differ), p_cross_by [G,time_bins] = cumsum(t_hist) / R -- the first-passage curve, i.e.
+        p_cross for every pulse width up to the duration from one run -- and t_mean, t_std [G] over the crossed trials, formed
+        from the bin centres (NaN where nobody crossed).  The moments are exact to one bin width; time_bins = n, the pulse's
+        sub-step count, resolves every sub-step of a fixed-step solver.  With time_bins == 0 the call is exactly the one above: watch_phase is
+        still checked against the number of phases, but has no meaning then."""
         m0 = np.asarray(m_initial.cpu() if torch.is_tensor(m_initial) else m_initial, dtype=np.float64).reshape(-1, 3)
         g, r = int(m0.shape[0]), int(n_trials)
         if r < 1:
@@ -264,6 +276,8 @@ class _GpuSolverBase:
             raise ValueError("max_trials_per_launch must be >= 1")
         if not 0 <= int(n_bins) <= 64:
             raise ValueError("n_bins must be in 0 ... 64")
+        if not 0 <= int(time_bins) <= 1024:
+            raise ValueError("time_bins must be in 0 ... 1024")
         wave = None
         if current_knots is not None or field_knots is not None:
             wave = {"current": _knot_tables(current_knots, g, 1, "current_knots"), "field": _knot_tables(field_knots, g, 3, "field_knots")}
@@ -278,6 +292,8 @@ class _GpuSolverBase:
             raise ValueError("with current_knots / field_knots, current and duration describe the one shaped pulse: shape [G] or [1,G]")
         if J.shape != T.shape or J.ndim != 2 or J.shape[1] != g:
             raise ValueError(f"current and duration must both have shape [G] or [P,G] with G = {g}, got {J.shape} and {T.shape}")
+        if not 0 <= int(watch_phase) < J.shape[0]:
+            raise ValueError(f"watch_phase must be in 0 ... {J.shape[0] - 1}")
         phases = [(J, T)]
         wave_phase = 0                      # (the pulse's place in the chain: behind the equilibration, if there is one)
         for where, t in ((0, equilibrate), (1, relax)):
@@ -316,6 +332,8 @@ class _GpuSolverBase:
             out, step = None, int(max_trials_per_launch)
             # (without knots: exactly the rectangular call; a backend without waveforms is never asked for them)
             launch = b.switch_stats if wave is None else functools.partial(b.switch_stats_wave, wave=wave, wave_phase=int(wave_phase))
+            if time_bins > 0:
+                launch = functools.partial(b.switch_times, watch_phase=int(wave_phase) + int(watch_phase), wave=wave, n_tbins=int(time_bins))
             for done in range(0, r, step):
                 out = launch(torch.from_numpy(np.ascontiguousarray(m0.T)), torch.from_numpy(J), torch.from_numpy(T),
                              torch.from_numpy(tgt), min(step, r - done), trial0=int(trial_offset) + done, trial_stride=stride,
@@ -326,8 +344,19 @@ class _GpuSolverBase:
             b.close()
         self.solve_count += g * r
         p = n_sw / r
-        return {"p_switch": p, "wer": 1.0 - p, "n_switched": n_sw, "n_failed": n_failed, "stderr": np.sqrt(p * (1.0 - p) / r),
-                "hist": hist, "bin_edges": np.linspace(-1.0, 1.0, int(n_bins) + 1) if n_bins > 0 else np.zeros(0)}
+        res = {"p_switch": p, "wer": 1.0 - p, "n_switched": n_sw, "n_failed": n_failed, "stderr": np.sqrt(p * (1.0 - p) / r),
+               "hist": hist, "bin_edges": np.linspace(-1.0, 1.0, int(n_bins) + 1) if n_bins > 0 else np.zeros(0)}
+        if time_bins > 0:
+            n_cr, n_ret, t_hist = (x.cpu().numpy().astype(np.int64) for x in out[3:6])
+            t_edges = np.linspace(0.0, 1.0, int(time_bins) + 1)[None, :] * T[int(wave_phase) + int(watch_phase)][:, None]
+            centres = 0.5 * (t_edges[:, :-1] + t_edges[:, 1:])
+            binned = t_hist.sum(axis=1).astype(np.float64)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                t_mean = (t_hist * centres).sum(axis=1) / binned
+                t_var = (t_hist * (centres - t_mean[:, None]) ** 2).sum(axis=1) / binned
+            res.update({"n_crossed": n_cr, "n_returned": n_ret, "p_cross": n_cr / r, "t_hist": t_hist, "t_edges": t_edges,
+                        "p_cross_by": np.cumsum(t_hist, axis=1) / r, "t_mean": t_mean, "t_std": np.sqrt(t_var)})
+        return res
 
     def _solve_one(self, m_initial, t_span, device_params, current_func, field_func, thermal_noise, temperature,
                    traj_cap):
