@@ -13,9 +13,7 @@
 // with per-env parameters each lane derives its constants from its env's record into registers (step kernel, MULTI == 2).
 #include "stg_kernels.hpp"
 #include "stg_wave.hpp"
-#include "stg_switch_stats.hpp"
-#include "stg_switch_stats_wave.hpp"
-#include "stg_switch_times.hpp"
+#include "stg_switch.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -408,6 +406,11 @@ static CfgView cfg_view(const stg_config& c) {
     return v;
 }
 
+// the kernels' THERMAL flag: the fixed-step solvers draw a field only at a positive temperature, RK45 whenever thermal is on
+static bool thermal_flag(const stg_config& c) {
+    return c.solver == STG_SOLVER_RK45 ? c.thermal != 0 : (c.thermal && c.temperature > 0);
+}
+
 static int check_cfg(const stg_config* c) {
     if (!c) return fail(STG_E_INVALID, "cfg is NULL");
     if (c->solver < 0 || c->solver > 2) return fail(STG_E_INVALID, "cfg.solver must be STG_SOLVER_RK4/EULER/RK45");
@@ -774,8 +777,7 @@ int stg_step_wave(stg_ctx* ctx, const void* actions, int32_t act_f64, int32_t au
     w.kj = kj; w.tj = tj; w.jk = jk; w.kh = kh; w.th = th; w.hk = hk;
     const bool rk45 = ctx->cfg.solver == STG_SOLVER_RK45;
     w.axis_z = (rk45 ? ctx->axis_z_llgs : ctx->axis_z) ? 1 : 0;
-    const bool thermal = rk45 ? ctx->cfg.thermal != 0 : (ctx->cfg.thermal && ctx->cfg.temperature > 0);
-    stg_step_wave_launch(w, ctx->cfg.solver, thermal, ctx->ncls > 1, act_f64, (hipStream_t)stream);
+    stg_step_wave_launch(w, ctx->cfg.solver, thermal_flag(ctx->cfg), ctx->ncls > 1, act_f64, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return STG_OK;
 }
@@ -832,9 +834,7 @@ static int enqueue_shaped(stg_ctx* ctx, ShapedStepArgs& w, int32_t act_f64, hipS
     a.ctab = ctx->ctab; a.cls = ctx->cls; a.ncls = ctx->ncls;
     a.counters = ctx->counters;
     w.kj = ctx->shape_kj; w.kh = ctx->shape_kh; w.shape = ctx->shape;
-    const bool rk45 = ctx->cfg.solver == STG_SOLVER_RK45;
-    const bool thermal = rk45 ? ctx->cfg.thermal != 0 : (ctx->cfg.thermal && ctx->cfg.temperature > 0);
-    stg_step_shaped_launch(w, ctx->cfg.solver, thermal, ctx->ncls > 1, act_f64, st);
+    stg_step_shaped_launch(w, ctx->cfg.solver, thermal_flag(ctx->cfg), ctx->ncls > 1, act_f64, st);
     HIP_TRY(hipGetLastError());
     return STG_OK;
 }
@@ -921,9 +921,7 @@ static int enqueue_knots(stg_ctx* ctx, KnotsStepArgs& w, int32_t act_f64, hipStr
     a.ctab = ctx->ctab; a.cls = ctx->cls; a.ncls = ctx->ncls;
     a.counters = ctx->counters;
     w.P = ctx->knots_P; w.kh = ctx->knots_kh; w.s_limit = ctx->knots_limit; w.knots = ctx->knots;
-    const bool rk45 = ctx->cfg.solver == STG_SOLVER_RK45;
-    const bool thermal = rk45 ? ctx->cfg.thermal != 0 : (ctx->cfg.thermal && ctx->cfg.temperature > 0);
-    stg_step_knots_launch(w, ctx->cfg.solver, thermal, ctx->ncls > 1, act_f64, st);
+    stg_step_knots_launch(w, ctx->cfg.solver, thermal_flag(ctx->cfg), ctx->ncls > 1, act_f64, st);
     HIP_TRY(hipGetLastError());
     return STG_OK;
 }
@@ -981,11 +979,11 @@ static int solve_common(stg_ctx* ctx, const double* m0, const double* J, const d
     a.traj_cap = traj_cap; a.traj_t = tt; a.traj_m = tm; a.traj_e = te; a.traj_tq = ttq;
     const bool multi = ctx->ncls > 1;
     hipStream_t st = (hipStream_t)stream;
-    const bool th_simple = ctx->cfg.thermal && ctx->cfg.temperature > 0, th_llgs = ctx->cfg.thermal != 0;
+    const bool thermal = thermal_flag(ctx->cfg);
     switch (ctx->cfg.solver) {
-        case STG_SOLVER_RK4: dispatch_solve<STG_SOLVER_RK4>(a, th_simple, multi, record, st); break;
-        case STG_SOLVER_EULER: dispatch_solve<STG_SOLVER_EULER>(a, th_simple, multi, record, st); break;
-        default: dispatch_solve<STG_SOLVER_RK45>(a, th_llgs, multi, record, st); break;
+        case STG_SOLVER_RK4: dispatch_solve<STG_SOLVER_RK4>(a, thermal, multi, record, st); break;
+        case STG_SOLVER_EULER: dispatch_solve<STG_SOLVER_EULER>(a, thermal, multi, record, st); break;
+        default: dispatch_solve<STG_SOLVER_RK45>(a, thermal, multi, record, st); break;
     }
     HIP_TRY(hipGetLastError());
     return STG_OK;
@@ -1026,16 +1024,14 @@ int stg_solve_wave(stg_ctx* ctx, const double* m0, const double* J, const double
     a.traj_cap = traj_cap;
     if (record) { a.traj_t = t; a.traj_m = m; a.traj_e = energy; a.traj_tq = torques; }
     w.kj = kj; w.tj = tj; w.jk = jk; w.kh = kh; w.th = th; w.hk = hk;
-    const bool thermal = ctx->cfg.solver == STG_SOLVER_RK45 ? ctx->cfg.thermal != 0 : (ctx->cfg.thermal && ctx->cfg.temperature > 0);
-    stg_wave_launch(w, ctx->cfg.solver, thermal, ctx->ncls > 1, record, (hipStream_t)stream);
+    stg_wave_launch(w, ctx->cfg.solver, thermal_flag(ctx->cfg), ctx->ncls > 1, record, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return STG_OK;
 }
 
-// Monte-Carlo switching statistics: its kernels live in stg_switch_stats.hip (stg_switch_stats_launch) and, with one waveform phase,
-// in stg_switch_stats_wave.hip (stg_switch_stats_wave_launch); with the first passage of a watched phase, in stg_switch_times.hip
-// (stg_switch_times_launch).  The argument checks and the argument block the three entries share;
-// `need_J`: whether a NULL J is refused here.
+// Monte-Carlo switching statistics: the three entries launch the one trial kernel of stg_switch.hpp (stg_switch_launch) on the largest
+// argument block, SwitchTimesArgs, of which stg_switch_stats fills in the innermost part and stg_switch_stats_wave the middle one.
+// The argument checks and the argument block the three entries share; `need_J`: whether a NULL J is refused here.
 static int switch_stats_args(stg_ctx* ctx, const char* what, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t P,
                              const double* m0, const double* J, const double* T, const uint8_t* cond_cls, uint32_t env_step,
                              const double* target, double threshold, int32_t n_bins, unsigned long long* n_switched,
@@ -1063,42 +1059,49 @@ static int switch_stats_args(stg_ctx* ctx, const char* what, int32_t G, int64_t 
     return STG_OK;
 }
 
+// the tabled (stg_switch_stats_wave) or watched (stg_switch_times) phase and the tables: checks, then the wiring.  `need_table`: whether
+// a call without any table is refused
+static int switch_wave_args(const char* phase_name, bool need_table, int32_t phase, int32_t P, int32_t kj, const double* tj, const double* jk,
+                            int32_t kh, const double* th, const double* hk, SwitchStatsWaveArgs& w) {
+    if (phase < 0 || phase >= P) return fail(STG_E_INVALID, std::string(phase_name) + " must be in 0 ... P - 1");
+    if (kj != 0 && (kj < 2 || kj > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kj must be 0 or 2 ... STG_MAX_KNOTS");
+    if (kh != 0 && (kh < 2 || kh > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kh must be 0 or 2 ... STG_MAX_KNOTS");
+    if (need_table && kj == 0 && kh == 0) return fail(STG_E_INVALID, "kj = kh = 0: no waveform, use stg_switch_stats");
+    if (kj != 0 && (!tj || !jk)) return fail(STG_E_INVALID, "tj/jk must not be NULL with kj > 0");
+    if (kh != 0 && (!th || !hk)) return fail(STG_E_INVALID, "th/hk must not be NULL with kh > 0");
+    w.wave_phase = phase;
+    w.kj = kj; w.tj = tj; w.jk = jk; w.kh = kh; w.th = th; w.hk = hk;
+    return STG_OK;
+}
+
+// the launch tail of the three entries (`times`: stg_switch_times); no trials, no launch
+static int switch_launch(stg_ctx* ctx, const SwitchTimesArgs& x, bool times, void* stream) {
+    if (x.w.s.R == 0) return STG_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    stg_switch_launch(x, times, ctx->cfg.solver, thermal_flag(ctx->cfg), ctx->ncls > 1 && x.w.s.cond_cls != nullptr, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return STG_OK;
+}
+
 int stg_switch_stats(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t P, const double* m0, const double* J,
                      const double* T, const uint8_t* cond_cls, uint32_t env_step, const double* target, double threshold, int32_t n_bins,
                      unsigned long long* n_switched, unsigned long long* n_failed, unsigned long long* hist, void* stream) {
-    SwitchStatsArgs a{};
+    SwitchTimesArgs x{};
     if (int rc = switch_stats_args(ctx, "stg_switch_stats", G, R, trial0, trial_stride, P, m0, J, T, cond_cls, env_step, target, threshold, n_bins,
-                                   n_switched, n_failed, hist, true, a)) return rc;
-    if (R == 0) return STG_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const bool thermal = ctx->cfg.solver == STG_SOLVER_RK45 ? ctx->cfg.thermal != 0 : (ctx->cfg.thermal && ctx->cfg.temperature > 0);
-    stg_switch_stats_launch(a, ctx->cfg.solver, thermal, ctx->ncls > 1 && cond_cls != nullptr, (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    return STG_OK;
+                                   n_switched, n_failed, hist, true, x.w.s)) return rc;
+    return switch_launch(ctx, x, false, stream);
 }
 
 int stg_switch_stats_wave(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t P, const double* m0, const double* J,
                           const double* T, int32_t wave_phase, int32_t kj, const double* tj, const double* jk, int32_t kh, const double* th,
                           const double* hk, const uint8_t* cond_cls, uint32_t env_step, const double* target, double threshold, int32_t n_bins,
                           unsigned long long* n_switched, unsigned long long* n_failed, unsigned long long* hist, void* stream) {
-    SwitchStatsWaveArgs w{};
+    SwitchTimesArgs x{};
     // (J is read for the rectangular phases, and for the wave phase without a current table: a single tabled phase needs none)
     if (int rc = switch_stats_args(ctx, "stg_switch_stats_wave", G, R, trial0, trial_stride, P, m0, J, T, cond_cls, env_step, target, threshold,
-                                   n_bins, n_switched, n_failed, hist, !(P == 1 && kj > 0), w.s)) return rc;
-    if (wave_phase < 0 || wave_phase >= P) return fail(STG_E_INVALID, "wave_phase must be in 0 ... P - 1");
-    if (kj != 0 && (kj < 2 || kj > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kj must be 0 or 2 ... STG_MAX_KNOTS");
-    if (kh != 0 && (kh < 2 || kh > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kh must be 0 or 2 ... STG_MAX_KNOTS");
-    if (kj == 0 && kh == 0) return fail(STG_E_INVALID, "kj = kh = 0: no waveform, use stg_switch_stats");
-    if (kj != 0 && (!tj || !jk)) return fail(STG_E_INVALID, "tj/jk must not be NULL with kj > 0");
-    if (kh != 0 && (!th || !hk)) return fail(STG_E_INVALID, "th/hk must not be NULL with kh > 0");
-    if (R == 0) return STG_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    w.wave_phase = wave_phase;
-    w.kj = kj; w.tj = tj; w.jk = jk; w.kh = kh; w.th = th; w.hk = hk;
-    const bool thermal = ctx->cfg.solver == STG_SOLVER_RK45 ? ctx->cfg.thermal != 0 : (ctx->cfg.thermal && ctx->cfg.temperature > 0);
-    stg_switch_stats_wave_launch(w, ctx->cfg.solver, thermal, ctx->ncls > 1 && cond_cls != nullptr, (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    return STG_OK;
+                                   n_bins, n_switched, n_failed, hist, !(P == 1 && kj > 0), x.w.s)) return rc;
+    if (int rc = switch_wave_args("wave_phase", true, wave_phase, P, kj, tj, jk, kh, th, hk, x.w)) return rc;
+    return switch_launch(ctx, x, false, stream);
 }
 
 int stg_switch_times(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t P, const double* m0, const double* J,
@@ -1107,27 +1110,15 @@ int stg_switch_times(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t
                      unsigned long long* n_switched, unsigned long long* n_failed, unsigned long long* hist, int32_t n_tbins,
                      unsigned long long* n_crossed, unsigned long long* n_returned, unsigned long long* t_hist, void* stream) {
     SwitchTimesArgs x{};
-    SwitchStatsWaveArgs& w = x.w;
     // (J as in stg_switch_stats_wave: not read for a single phase with a current table)
     if (int rc = switch_stats_args(ctx, "stg_switch_times", G, R, trial0, trial_stride, P, m0, J, T, cond_cls, env_step, target, threshold,
-                                   n_bins, n_switched, n_failed, hist, !(P == 1 && kj > 0), w.s)) return rc;
-    if (watch_phase < 0 || watch_phase >= P) return fail(STG_E_INVALID, "watch_phase must be in 0 ... P - 1");
-    if (kj != 0 && (kj < 2 || kj > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kj must be 0 or 2 ... STG_MAX_KNOTS");
-    if (kh != 0 && (kh < 2 || kh > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kh must be 0 or 2 ... STG_MAX_KNOTS");
-    if (kj != 0 && (!tj || !jk)) return fail(STG_E_INVALID, "tj/jk must not be NULL with kj > 0");
-    if (kh != 0 && (!th || !hk)) return fail(STG_E_INVALID, "th/hk must not be NULL with kh > 0");
+                                   n_bins, n_switched, n_failed, hist, !(P == 1 && kj > 0), x.w.s)) return rc;
+    if (int rc = switch_wave_args("watch_phase", false, watch_phase, P, kj, tj, jk, kh, th, hk, x.w)) return rc;
     if (n_tbins < 0 || n_tbins > STG_MAX_TBINS) return fail(STG_E_INVALID, "n_tbins must be in 0 ... STG_MAX_TBINS");
     if (!n_crossed || !n_returned) return fail(STG_E_INVALID, "n_crossed/n_returned must not be NULL");
     if ((t_hist == nullptr) != (n_tbins == 0)) return fail(STG_E_INVALID, "t_hist must be NULL if and only if n_tbins == 0");
-    if (R == 0) return STG_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    w.wave_phase = watch_phase;
-    w.kj = kj; w.tj = tj; w.jk = jk; w.kh = kh; w.th = th; w.hk = hk;
     x.n_tbins = n_tbins; x.n_crossed = n_crossed; x.n_returned = n_returned; x.t_hist = t_hist;
-    const bool thermal = ctx->cfg.solver == STG_SOLVER_RK45 ? ctx->cfg.thermal != 0 : (ctx->cfg.thermal && ctx->cfg.temperature > 0);
-    stg_switch_times_launch(x, ctx->cfg.solver, thermal, ctx->ncls > 1 && cond_cls != nullptr, (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    return STG_OK;
+    return switch_launch(ctx, x, true, stream);
 }
 
 int stg_get_state(stg_ctx* ctx, double* m, double* target, double* total_energy, int32_t* step_count, uint32_t* rng_step,

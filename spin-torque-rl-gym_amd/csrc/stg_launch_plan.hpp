@@ -48,7 +48,7 @@ inline void refill_auto(int64_t n, bool thermal, int& r, int64_t& nw) {
     r = (int)(rr < 2 ? 2 : (rr > 0x7FFFFFFF ? 0x7FFFFFFF : rr));              // (envs per lane on average; only != 0 matters to the launch)
 }
 
-// stg_switch_stats (kernels: stg_switch_stats.hip; pinned by tests/test_switch_stats_plan_host.py).
+// stg_switch_stats (kernel: stg_switch.hpp; pinned by tests/test_switch_stats_plan_host.py).
 // Launch rule: every lane runs one trial (L = 1) while that needs at most STG_SWITCH_STATS_WAVES wavefronts in all; beyond that the
 // wavefronts per condition are capped at max(1, STG_SWITCH_STATS_WAVES / G) and each lane loops over L trials.
 static inline void switch_stats_plan(int32_t G, int64_t R, int64_t* L, int32_t* waves_per_cond) {

@@ -730,7 +730,7 @@ struct SolveOut {
 // Optional trajectory recorder (stg_solve_traj): rows are written with env index fastest.
 // The solvers below take their per-point observer as a template parameter REC, Recorder by default: put(row, t, m, e, tq) const
 // is called for row 0 (t = 0) and every later point when RECORD is set, and the members e / tq say whether the RK45 by-products
-// are wanted at all (stg_switch_times.hpp has an observer that stores nothing: FirstPassage).
+// are wanted at all (stg_switch.hpp has an observer that stores nothing: FirstPassage).
 struct Recorder {
     double* t;       // [cap][N]
     double* m;       // [cap][3][N]

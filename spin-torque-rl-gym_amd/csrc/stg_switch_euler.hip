@@ -1,0 +1,6 @@
+// stg_switch_euler.hip -- instantiations of the switching trial kernel for STG_SOLVER_EULER (see stg_switch.hpp)
+#include "stg_switch.hpp"
+
+void stg_dispatch_switch_euler(const SwitchTimesArgs& x, bool times, bool thermal, bool multi, hipStream_t st) {
+    dispatch_switch<STG_SOLVER_EULER>(x, times, thermal, multi, st);
+}

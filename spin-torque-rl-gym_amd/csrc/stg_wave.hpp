@@ -5,10 +5,11 @@
 // This header holds the waveform variants of the functions of stg_physics.hpp that take J as a per-solve constant (simple_solve, the
 // llgs_lane_* family); the functions in which the drive enters as an argument -- llgs_rhs, validation, the RK45 controller pieces, the
 // recorder, the normal stream -- are reused as they are.  Only stg_solve_wave.hip, stg_step_wave.hip, stg_step_shaped.hip,
-// stg_step_knots.hip and stg_switch_stats_wave.hip instantiate anything in here: the step kernels, stg_solve_kernel and the array kernels
-// do not see this file's device code (profiles/waveform_existing_kernels_unchanged.txt, profiles/step_wave_existing_kernels_unchanged.txt,
+// stg_step_knots.hip and the switching trial kernel (stg_switch.hpp: stg_switch_rk4.hip / _euler.hip / _rk45.hip) instantiate anything in
+// here: the step kernels, stg_solve_kernel and the array kernels do not see this file's device code
+// (profiles/waveform_existing_kernels_unchanged.txt, profiles/step_wave_existing_kernels_unchanged.txt,
 // profiles/step_shaped_existing_kernels_unchanged.txt, profiles/step_knots_existing_kernels_unchanged.txt,
-// profiles/switch_stats_wave_existing_kernels_unchanged.txt).
+// profiles/switch_stats_wave_existing_kernels_unchanged.txt, profiles/switch_family_existing_kernels_unchanged.txt).
 //
 // Waveform semantics (the C header states them for callers; physics.PiecewiseLinear and tests/waveform_ref.py use the same arithmetic):
 //   K knots, 2 <= K <= STG_MAX_KNOTS, times tk[0] < ... < tk[K-1] finite, values vk (a scalar, or three field components).

@@ -551,6 +551,26 @@ class HipBackend:
         self._keep = (m0, J, T)
         return out
 
+    def _switch_args(self, m0, J, T, target, n_trials, trial0, trial_stride, cond_cls, bins, out):
+        """What the three switching entries share: (G, R, trial0, stride, P) as ints, the condition arrays on the device in their
+        shapes, and `out` -- the caller's, or zeros: two [G] counts and a [G,b] histogram (None for b = 0) for every b of `bins`.
+        J may be None (a single tabled phase)."""
+        m0 = self._dev(m0, torch.float64)
+        g = int(m0.shape[-1])
+        m0 = self._dev(m0, torch.float64, (3, g))
+        T = self._dev(T, torch.float64)
+        p = int(T.shape[0])
+        J, T = self._dev(J, torch.float64, (p, g)), self._dev(T, torch.float64, (p, g))
+        target = self._dev(target, torch.float64, (3, g))
+        cond_cls = self._dev(cond_cls, torch.uint8, (g,))
+        r, t0 = int(n_trials), int(trial0)
+        stride = t0 + r if trial_stride is None else int(trial_stride)
+        if out is None:
+            zeros = lambda *shape: torch.zeros(shape, dtype=torch.int64, device=self.device)      # noqa: E731
+            out = tuple(x for b in bins for x in (zeros(g), zeros(g), zeros(g, int(b)) if b > 0 else None))
+        self._keep = (m0, J, T, target, cond_cls)
+        return (g, r, t0, stride, p), (m0, J, T, target, cond_cls), out
+
     def switch_stats(self, m0, J, T, target, n_trials, trial0=0, trial_stride=None, cond_cls=None, env_step=0, threshold=0.0,
                      n_bins=0, out=None):
         """Monte-Carlo switching counts reduced on the device (stg_switch_stats): trials trial0 ... trial0 + n_trials - 1 of the G
@@ -558,25 +578,12 @@ class HipBackend:
         Trial r of condition g is problem g * trial_stride + r of `solve` at env_step + p (trial_stride None: trial0 + n_trials).
         Returns (n_switched [G], n_failed [G], hist [G,n_bins] or None), int64 on the device; the call ADDS to them: `out` = the
         triple of an earlier call accumulates a chunked trial range, None starts from zero.  Enqueues only."""
-        dev = self.device
-        m0 = self._dev(m0, torch.float64)
-        g = int(m0.shape[-1])
-        m0 = self._dev(m0, torch.float64, (3, g))
-        J, T = self._dev(J, torch.float64), self._dev(T, torch.float64)
-        p = int(J.shape[0])
-        J, T = self._dev(J, torch.float64, (p, g)), self._dev(T, torch.float64, (p, g))
-        target = self._dev(target, torch.float64, (3, g))
-        cond_cls = self._dev(cond_cls, torch.uint8, (g,))
-        r, t0 = int(n_trials), int(trial0)
-        stride = t0 + r if trial_stride is None else int(trial_stride)
-        if out is None:
-            out = (torch.zeros(g, dtype=torch.int64, device=dev), torch.zeros(g, dtype=torch.int64, device=dev),
-                   torch.zeros((g, int(n_bins)), dtype=torch.int64, device=dev) if n_bins > 0 else None)
+        (g, r, t0, stride, p), (m0, J, T, target, cond_cls), out = self._switch_args(m0, J, T, target, n_trials, trial0, trial_stride,
+                                                                                     cond_cls, (n_bins,), out)
         n_sw, n_failed, hist = out
         _lib.check(self.lib.stg_switch_stats(self._ctx, g, r, t0, stride, p, _ptr(m0), _ptr(J), _ptr(T), _ptr(cond_cls), int(env_step),
                                              _ptr(target), float(threshold), int(n_bins), _ptr(n_sw), _ptr(n_failed), _ptr(hist),
                                              self._stream()))
-        self._keep = (m0, J, T, target, cond_cls)
         return out
 
     def switch_stats_wave(self, m0, J, T, target, n_trials, wave, wave_phase=0, trial0=0, trial_stride=None, cond_cls=None, env_step=0,
@@ -586,26 +593,14 @@ class HipBackend:
         the start of that phase.  A missing current table means the rectangular J[wave_phase], a missing field table zero field (not
         both).  The other phases are the rectangular J, T [P,G] of switch_stats; trial r of condition g is problem g * trial_stride + r
         of `solve(wave=)` at env_step + wave_phase and of `solve` at the other phases' env_step + p.  Returns and `out` as switch_stats."""
-        dev = self.device
-        m0 = self._dev(m0, torch.float64)
-        g = int(m0.shape[-1])
-        m0 = self._dev(m0, torch.float64, (3, g))
-        J, T = self._dev(J, torch.float64), self._dev(T, torch.float64)
-        p = int(T.shape[0])
-        J, T = self._dev(J, torch.float64, (p, g)), self._dev(T, torch.float64, (p, g))
-        target = self._dev(target, torch.float64, (3, g))
-        cond_cls = self._dev(cond_cls, torch.uint8, (g,))
+        (g, r, t0, stride, p), (m0, J, T, target, cond_cls), out = self._switch_args(m0, J, T, target, n_trials, trial0, trial_stride,
+                                                                                     cond_cls, (n_bins,), out)
         kj, tj, jk, kh, th, hk = self._wave_tables(wave, g)
-        r, t0 = int(n_trials), int(trial0)
-        stride = t0 + r if trial_stride is None else int(trial_stride)
-        if out is None:
-            out = (torch.zeros(g, dtype=torch.int64, device=dev), torch.zeros(g, dtype=torch.int64, device=dev),
-                   torch.zeros((g, int(n_bins)), dtype=torch.int64, device=dev) if n_bins > 0 else None)
         n_sw, n_failed, hist = out
         _lib.check(self.lib.stg_switch_stats_wave(self._ctx, g, r, t0, stride, p, _ptr(m0), _ptr(J), _ptr(T), int(wave_phase), kj, _ptr(tj),
                                                   _ptr(jk), kh, _ptr(th), _ptr(hk), _ptr(cond_cls), int(env_step), _ptr(target),
                                                   float(threshold), int(n_bins), _ptr(n_sw), _ptr(n_failed), _ptr(hist), self._stream()))
-        self._keep = (m0, J, T, target, cond_cls, tj, jk, th, hk)
+        self._keep += (tj, jk, th, hk)
         return out
 
     def switch_times(self, m0, J, T, target, n_trials, watch_phase=0, wave=None, n_tbins=0, trial0=0, trial_stride=None, cond_cls=None,
@@ -617,28 +612,15 @@ class HipBackend:
         n_tbins equal bins over the phase's [0, T].  Returns (n_switched [G], n_failed [G], hist [G,n_bins] or None, n_crossed [G],
         n_returned [G], t_hist [G,n_tbins] or None), int64 on the device -- n_returned: crossed, yet not switched at the trial's end.
         The call ADDS to them: `out` = the tuple of an earlier call accumulates, None starts from zero.  Enqueues only."""
-        dev = self.device
-        m0 = self._dev(m0, torch.float64)
-        g = int(m0.shape[-1])
-        m0 = self._dev(m0, torch.float64, (3, g))
-        J, T = self._dev(J, torch.float64), self._dev(T, torch.float64)
-        p = int(T.shape[0])
-        J, T = self._dev(J, torch.float64, (p, g)), self._dev(T, torch.float64, (p, g))
-        target = self._dev(target, torch.float64, (3, g))
-        cond_cls = self._dev(cond_cls, torch.uint8, (g,))
+        (g, r, t0, stride, p), (m0, J, T, target, cond_cls), out = self._switch_args(m0, J, T, target, n_trials, trial0, trial_stride,
+                                                                                     cond_cls, (n_bins, n_tbins), out)
         kj, tj, jk, kh, th, hk = self._wave_tables(wave, g) if wave is not None else (0, None, None, 0, None, None)
-        r, t0 = int(n_trials), int(trial0)
-        stride = t0 + r if trial_stride is None else int(trial_stride)
-        if out is None:
-            zeros = lambda *shape: torch.zeros(shape, dtype=torch.int64, device=dev)
-            out = (zeros(g), zeros(g), zeros(g, int(n_bins)) if n_bins > 0 else None,
-                   zeros(g), zeros(g), zeros(g, int(n_tbins)) if n_tbins > 0 else None)
         n_sw, n_failed, hist, n_cr, n_ret, t_hist = out
         _lib.check(self.lib.stg_switch_times(self._ctx, g, r, t0, stride, p, _ptr(m0), _ptr(J), _ptr(T), int(watch_phase), kj, _ptr(tj),
                                              _ptr(jk), kh, _ptr(th), _ptr(hk), _ptr(cond_cls), int(env_step), _ptr(target),
                                              float(threshold), int(n_bins), _ptr(n_sw), _ptr(n_failed), _ptr(hist), int(n_tbins),
                                              _ptr(n_cr), _ptr(n_ret), _ptr(t_hist), self._stream()))
-        self._keep = (m0, J, T, target, cond_cls, tj, jk, th, hk)
+        self._keep += (tj, jk, th, hk)
         return out
 
     def device_terms(self, m, J, volt):

@@ -15,6 +15,7 @@ same arguments (_check does both).
   4. m0 beyond the threshold, a threshold nobody reaches, a point exactly on the threshold, RK45 out of attempts;
   5. class table; 6. stream ids; 7. lanes that loop; 8. additivity; 9. write footprint and refusals; 10. the Python method;
   11. the NumPy statement under the oracle's normals (no library solve involved).
+  12. the three entries against each other: stg_switch_times' first three outputs are stg_switch_stats' / stg_switch_stats_wave's.
 
 Every test fails without the feature: the library has no symbol stg_switch_times."""
 import ctypes as C
@@ -537,3 +538,48 @@ def test_all_six_equal_the_numpy_statement(stg, oracle_mod, solver, noise):
     b.close()
     print(f"{solver} {noise}: crossed {got[3].tolist()} (NumPy {case['counts'][3].tolist()}), returned {got[4].tolist()} ({case['counts'][4].tolist()})")
     _same(got, case["counts"], solver)
+
+
+# ------------------------------------------------------------------------------------------------
+# 12. one kernel, three entries: they agree where their definitions coincide
+# ------------------------------------------------------------------------------------------------
+AGREE_T = 5e-11                                       # every phase: short pulses keep the twelve cases to a few seconds in all
+AGREE_FIELD = 1e6                                     # A/m, half the anisotropy field: the tabled phase must not look like the rectangular one
+
+
+@pytest.mark.parametrize("big,R", ((G, 100), (12289, 130)), ids=("G3-R100", "G12289-R130"))
+@pytest.mark.parametrize("thermal", (True, False), ids=("thermal", "no-field"))
+@pytest.mark.parametrize("solver,noise", (("rk4", "brown"), ("euler", "brown"), ("rk45", "white")))
+def test_the_three_entries_agree_where_their_definitions_coincide(stg, solver, noise, thermal, big, R):
+    """stg_switch_times is stg_switch_stats (no tables) or stg_switch_stats_wave (tables) in its first three outputs, whatever n_tbins:
+    EXACT equality, three phases with the special one in the middle, three classes with a class byte beyond the table, a partial
+    wavefront (R = 100) and lanes that loop (G = 12289, R = 130: one wavefront per condition, L = 3).  The two old entries differ from
+    each other here (the in-plane field ramp reaches half the anisotropy field), so an entry that launched the other's form of the
+    phase fails; condition 0 starts beyond the threshold, so its trials cross at the watched phase's first row, and the time histogram
+    must hold every crossing: an entry without the observer or without the histogram's LDS fails."""
+    assert ssr.plan_cap(big) >= -(-R // 64) if big == G else (ssr.plan_cap(big) == 1 and R > 128)
+    m3, J3, T3, t3 = _pulse(solver)
+    m3 = m3.copy()
+    m3[0] = (0.6, 0.0, -0.8)                                                       # m0 . target = 0.8 > 0
+    idx = np.arange(big) % G
+    m0, tgt = m3[idx], t3[idx]
+    Jp = J3[idx] * (0.8 + 0.4 * np.arange(big) / big)
+    J, T = np.stack([np.zeros(big), Jp, np.zeros(big)]), np.full((3, big), AGREE_T)
+    cur, fld = swr.trapezoid(Jp, T[1]), (np.stack([np.zeros(big), T[1]]), np.stack([np.zeros((big, 3)), np.tile([AGREE_FIELD, 0.0, 0.0], (big, 1))]))
+    v = br.SWITCH["volume"]
+    three = [ssr.params(), ssr.params(0.7 * v), ssr.params(1.3 * v)]
+    cond_cls = torch.from_numpy(np.array([2, 200, 1], dtype=np.uint8)[idx])
+    b = _context(stg, solver, noise, big, three, include_thermal_fluctuations=thermal)
+    kw = dict(threshold=0.0, n_bins=64, env_step=3, cond_cls=cond_cls)
+    stats = ssr.fused(b, m0, J, T, tgt, R, **kw)
+    stats_wave = swr.fused(b, m0, J, T, tgt, R, cur, fld, wave_phase=1, **kw)
+    assert not np.array_equal(stats[2], stats_wave[2])                             # (the tables matter)
+    for old, tables in ((stats, (None, None)), (stats_wave, (cur, fld))):
+        for n_tbins in (0, 7):
+            got = stref.fused(b, m0, J, T, tgt, R, 1, *tables, n_tbins=n_tbins, **kw)
+            what = (solver, noise, thermal, big, tables[0] is not None, n_tbins)
+            _same(got[:3], old, what)
+            assert (got[3][idx == 0] > 0).all(), what
+            assert (got[5] is None) if n_tbins == 0 else np.array_equal(got[5].sum(axis=1), got[3]), what
+    b.close()
+    assert (stats[2].sum(axis=1) == R).all() and not stats[1].any()
