@@ -486,6 +486,71 @@ int stg_switch_times(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t
                      int32_t n_tbins, unsigned long long* n_crossed, unsigned long long* n_returned,
                      unsigned long long* t_hist, void* stream);
 
+/* stg_switch_times over a POPULATION of devices: the switching statistics of a chip whose bits scatter in damping, Ms, K_u, volume and
+ * polarization, not of one device.  A condition's class row (cond_cls) is the NOMINAL device; every trial belongs to a device drawn
+ * around it, and integrates with that device's own derived constants -- its thermal strength follows its own volume, Ms and damping.
+ * No per-device memory is held: the number of devices is bounded by time, not by STG_MAX_CLASSES.
+ *
+ * The draw.  Five fields vary, the first STG_NVARY doubles of stg_device_params in declaration order: damping, ms, ku, volume,
+ * polarization (k = 0 ... 4).  Every other field, dev_type and params_valid are the nominal record's (the record stg_set_params was
+ * given for the condition's class).
+ *   Device identity: trial r of condition g (the ABSOLUTE trial index, trial0 <= r < trial0 + R) belongs to device d = r / Q (integer
+ *   division), Q = trials_per_device >= 1.  The device's draws come from the stream of env id env_id0 + g * trial_stride + d * Q -- the
+ *   id of the device's first trial -- at Philox counter word var_step, tag 0, calls 0 and 1: exactly the six normals z_0 ... z_5 that
+ *   stg_thermal_normals(env_step = var_step, call0 = 0, n_calls = 2) dumps for that env id.  z_0 ... z_4 are used, z_5 is discarded.
+ *   A device therefore depends on (cfg.seed, that env id, var_step) and on nothing else: not on chunks (trial0), ranks, the number of
+ *   trials per lane or the grid.
+ *   Arithmetic, IEEE fp64, each operation rounded, no FMA contraction:
+ *       zc_k    = min(max(z_k, -z_clip), z_clip)
+ *       f_k     = 1.0 + sigma[k][g] * zc_k
+ *       value_k = nominal_k * f_k
+ *   sigma[k][g] == 0 gives the nominal value bit for bit.  The device's row of derived constants is formed from the varied record by
+ *   the arithmetic that forms a class table row (gamma and temperature of the configuration), so a trial of device d equals, bit for
+ *   bit, the same trial run on a class table that holds device d's record.
+ *   Validity: a condition's sigma column is checked on the device, once per wavefront, like a bad knot table.  It is bad if an entry
+ *   is negative or not finite, or if sigma[k][g] * z_clip >= 1.0 (a parameter could come out non-positive).  A bad column makes every
+ *   trial of that condition fail at its first phase that is not skipped: m stays m0, n_failed[g] gains one, the trial is classified
+ *   like any other and has not crossed.  The other conditions are not affected.
+ *
+ * Arguments: those of stg_switch_times, with this difference: n_crossed and n_returned may BOTH be NULL when n_tbins == 0 (t_hist is
+ * NULL then anyway); the first passage is then not observed at all and the watched phase runs as in stg_switch_stats(_wave).
+ * watch_phase still names the phase the tables drive.  Then:
+ *   sigma [dev] double[STG_NVARY][G], condition index fastest; z_clip finite and > 0; var_step; trials_per_device = Q;
+ *   dev_switched [dev] or NULL, with dev_stride: dev_switched[g * dev_stride + d] gains one per switched trial of device d.  It is
+ *   indexed by the ABSOLUTE device id, so every chunk and every rank adds into the same array; only the elements
+ *   trial0 / Q ... (trial0 + R - 1) / Q of each condition are touched.
+ * Everything else is stg_switch_times word for word: the stream rule of the trials, the phases, skipped and failed phases, the
+ * classification and both bin rules, the first passage, cond_cls, the launch rule; the call ADDS to its output arrays and touches no
+ * other memory; it enqueues kernels only (no allocation, no synchronisation); per-env parameters return STG_E_STATE.  With every sigma
+ * 0 the six outputs of stg_switch_times are reproduced integer for integer.
+ * STG_E_INVALID with nothing launched and nothing written: every cause stg_switch_times lists (n_crossed / n_returned: one of them
+ * NULL, or both NULL with n_tbins > 0); sigma NULL; z_clip not finite or <= 0; trials_per_device < 1; var_step equal to env_step + p
+ * modulo 2^32 for some p < P (the device's draw would reuse a thermal stream of its own first trial); dev_switched non-NULL with
+ * dev_stride < (trial0 + R + Q - 1) / Q; G * dev_stride beyond int64.  R == 0 is valid and does nothing. */
+#define STG_NVARY 5
+int stg_switch_population(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t P,
+                          const double* m0, const double* J, const double* T, int32_t watch_phase,
+                          int32_t kj, const double* tj, const double* jk, int32_t kh, const double* th, const double* hk,
+                          const uint8_t* cond_cls, uint32_t env_step, const double* target, double threshold, int32_t n_bins,
+                          unsigned long long* n_switched, unsigned long long* n_failed, unsigned long long* hist,
+                          int32_t n_tbins, unsigned long long* n_crossed, unsigned long long* n_returned,
+                          unsigned long long* t_hist, const double* sigma, double z_clip, uint32_t var_step,
+                          int64_t trials_per_device, unsigned long long* dev_switched, int64_t dev_stride, void* stream);
+
+/* The devices of stg_switch_population made observable (the diagnostic twin of stg_thermal_normals): the parameters, and optionally
+ * the raw normals, of devices dev0 ... dev0 + D - 1 of each of the G conditions, formed by the device function the trial kernel calls.
+ *   params [dev] double[STG_NVARY][G][D]   (device index fastest): damping, ms, ku, volume, polarization of device dev0 + j
+ *   z      [dev] double[6][G][D] or NULL:  the device's six normals, z_5 included
+ * A condition with a bad sigma column (above) gets NaN parameters; its normals are still written.  G, trials_per_device,
+ * trial_stride, var_step, z_clip, sigma and cond_cls mean what they mean in stg_switch_population; the env id of device d of condition
+ * g is env_id0 + g * trial_stride + d * trials_per_device.  Enqueues one kernel; writes those arrays and nothing else.
+ * Per-env parameters return STG_E_STATE.  STG_E_INVALID with nothing launched: a NULL ctx / sigma / params, G < 1, D < 0, dev0 < 0,
+ * trials_per_device < 1, a bad z_clip, (dev0 + D - 1) * trials_per_device >= trial_stride (the device's first trial would lie in the
+ * next condition's streams), G * trial_stride (+ env_id0) beyond int64, G * D above 2^40.  D == 0 is valid and does nothing. */
+int stg_switch_population_devices(stg_ctx* ctx, int32_t G, int64_t D, int64_t dev0, int64_t trials_per_device, int64_t trial_stride,
+                                  uint32_t var_step, double z_clip, const double* sigma, const uint8_t* cond_cls, double* params,
+                                  double* z, void* stream);
+
 /* SpinTorqueEnv.step for all N envs with the drive of stg_solve_wave: current_func(t) and field_func(t) as piecewise-linear tables
  * in place of the rectangular pulse in zero field of stg_step (spin_torque_env.py:442-447).
  *

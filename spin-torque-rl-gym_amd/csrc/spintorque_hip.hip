@@ -117,6 +117,26 @@ __global__ void stg_normals_kernel(uint64_t seed, int64_t env_id0, int64_t N, ui
     }
 }
 
+// stg_switch_population_devices: thread (g, j) dumps device dev0 + j of condition g through vary_draw, the trial kernel's own function
+__global__ void stg_population_devices_kernel(uint64_t seed, int64_t env_id0, int32_t G, int64_t D, int64_t dev0, int64_t Q, int64_t trial_stride,
+                                              uint32_t var_step, double z_clip, const double* sigma, const stg_device_params* ptab,
+                                              const uint8_t* cond_cls, int32_t ncls, double* params, double* z) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)G * D) return;
+    const int64_t g = i / D, j = i % D;
+    const int c = (cond_cls && ncls > 1) ? (int)cond_cls[g] : 0;
+    double zz[6];
+    stg_device_params p;
+    vary_draw(seed, (uint64_t)vary_device_env(env_id0, g, trial_stride, dev0 + j, Q), var_step, ptab[c < ncls ? c : 0], sigma, G, g, z_clip, zz, p);
+    const bool ok = vary_column_ok(sigma, G, g, z_clip);
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    const double v[STG_NVARY] = {p.damping, p.ms, p.ku, p.volume, p.polarization};
+    const int64_t n = (int64_t)G * D;
+    for (int k = 0; k < STG_NVARY; ++k) params[k * n + i] = ok ? v[k] : nan;
+    if (z)
+        for (int k = 0; k < 6; ++k) z[k * n + i] = zz[k];
+}
+
 // stg_get_state / stg_set_state: between the library's state records and the caller's component-major arrays
 // (m, target: double[3][N]; the others [N]; any may be NULL = field not copied)
 template <bool SET>
@@ -359,6 +379,7 @@ struct stg_ctx {
     void* slab = nullptr;
     double* ctab = nullptr;           // device, [ncls][C_COUNT]
     double h_ctab[STG_MAX_CLASSES][C_COUNT];
+    stg_device_params* ptab = nullptr;   // device, [ncls]: the table as stg_set_params was given it (the nominal records of stg_switch_population)
     int32_t ncls = 0;
     const uint8_t* cls = nullptr;     // caller-owned device pointer
     unsigned long long* counters = nullptr;
@@ -463,7 +484,7 @@ int stg_create(stg_ctx** out, int device_id, int64_t n_envs, int64_t env_id0, co
     const size_t rc = al(2 * REFILL_STRIPES * REFILL_CURSOR_STRIDE * sizeof(unsigned long long));
     const size_t total = rs + r4 + ra + rp + rc + al(sizeof(double) * STG_MAX_CLASSES * C_COUNT) +
                          COUNTER_STRIPES * COUNTER_STRIDE * sizeof(unsigned long long) + al(sizeof(double) * STG_SHAPE_DOUBLES) +
-                         al(sizeof(double) * STG_KNOTS_DOUBLES);
+                         al(sizeof(double) * STG_KNOTS_DOUBLES) + al(sizeof(stg_device_params) * STG_MAX_CLASSES);
     hipError_t e = hipMalloc(&c->slab, total);
     if (e != hipSuccess) { delete c; return fail(STG_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
     e = hipMemset(c->slab, 0, total);
@@ -478,6 +499,7 @@ int stg_create(stg_ctx** out, int device_id, int64_t n_envs, int64_t env_id0, co
     c->refill_cursor = (unsigned long long*)p; p += rc;
     c->shape = (double*)p; p += al(sizeof(double) * STG_SHAPE_DOUBLES);
     c->knots = (double*)p; p += al(sizeof(double) * STG_KNOTS_DOUBLES);
+    c->ptab = (stg_device_params*)p; p += al(sizeof(stg_device_params) * STG_MAX_CLASSES);
     *out = c;
     return STG_OK;
 }
@@ -509,6 +531,7 @@ int stg_set_params(stg_ctx* ctx, const stg_device_params* table, int32_t n_class
     }
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipMemcpy(ctx->ctab, ctx->h_ctab, sizeof(double) * n_classes * C_COUNT, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ctx->ptab, table, sizeof(stg_device_params) * n_classes, hipMemcpyHostToDevice));
     ctx->ncls = n_classes;
     ctx->axis_z = true;
     for (int k = 0; k < n_classes; ++k)
@@ -1074,6 +1097,18 @@ static int switch_wave_args(const char* phase_name, bool need_table, int32_t pha
     return STG_OK;
 }
 
+// the first-passage outputs (stg_switch_times, stg_switch_population): checks, then the wiring.  `counts_optional`: n_crossed and
+// n_returned may both be NULL with n_tbins == 0
+static int switch_passage_args(int32_t n_tbins, unsigned long long* n_crossed, unsigned long long* n_returned, unsigned long long* t_hist,
+                               bool counts_optional, SwitchTimesArgs& x) {
+    if (n_tbins < 0 || n_tbins > STG_MAX_TBINS) return fail(STG_E_INVALID, "n_tbins must be in 0 ... STG_MAX_TBINS");
+    const bool none = counts_optional && n_tbins == 0 && !n_crossed && !n_returned;
+    if (!none && (!n_crossed || !n_returned)) return fail(STG_E_INVALID, "n_crossed/n_returned must not be NULL");
+    if ((t_hist == nullptr) != (n_tbins == 0)) return fail(STG_E_INVALID, "t_hist must be NULL if and only if n_tbins == 0");
+    x.n_tbins = n_tbins; x.n_crossed = n_crossed; x.n_returned = n_returned; x.t_hist = t_hist;
+    return STG_OK;
+}
+
 // the launch tail of the three entries (`times`: stg_switch_times); no trials, no launch
 static int switch_launch(stg_ctx* ctx, const SwitchTimesArgs& x, bool times, void* stream) {
     if (x.w.s.R == 0) return STG_OK;
@@ -1114,11 +1149,71 @@ int stg_switch_times(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t
     if (int rc = switch_stats_args(ctx, "stg_switch_times", G, R, trial0, trial_stride, P, m0, J, T, cond_cls, env_step, target, threshold,
                                    n_bins, n_switched, n_failed, hist, !(P == 1 && kj > 0), x.w.s)) return rc;
     if (int rc = switch_wave_args("watch_phase", false, watch_phase, P, kj, tj, jk, kh, th, hk, x.w)) return rc;
-    if (n_tbins < 0 || n_tbins > STG_MAX_TBINS) return fail(STG_E_INVALID, "n_tbins must be in 0 ... STG_MAX_TBINS");
-    if (!n_crossed || !n_returned) return fail(STG_E_INVALID, "n_crossed/n_returned must not be NULL");
-    if ((t_hist == nullptr) != (n_tbins == 0)) return fail(STG_E_INVALID, "t_hist must be NULL if and only if n_tbins == 0");
-    x.n_tbins = n_tbins; x.n_crossed = n_crossed; x.n_returned = n_returned; x.t_hist = t_hist;
+    if (int rc = switch_passage_args(n_tbins, n_crossed, n_returned, t_hist, false, x)) return rc;
     return switch_launch(ctx, x, true, stream);
+}
+
+// what stg_switch_population and its diagnostic twin share: the checks of the draw's scalars
+static int switch_vary_scalars(const double* sigma, double z_clip, int64_t trials_per_device) {
+    if (!sigma) return fail(STG_E_INVALID, "sigma must not be NULL");
+    if (!(z_clip > 0) || !std::isfinite(z_clip)) return fail(STG_E_INVALID, "z_clip must be finite and > 0");
+    if (trials_per_device < 1) return fail(STG_E_INVALID, "trials_per_device must be >= 1");
+    return STG_OK;
+}
+
+int stg_switch_population(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t P, const double* m0, const double* J,
+                          const double* T, int32_t watch_phase, int32_t kj, const double* tj, const double* jk, int32_t kh, const double* th,
+                          const double* hk, const uint8_t* cond_cls, uint32_t env_step, const double* target, double threshold, int32_t n_bins,
+                          unsigned long long* n_switched, unsigned long long* n_failed, unsigned long long* hist, int32_t n_tbins,
+                          unsigned long long* n_crossed, unsigned long long* n_returned, unsigned long long* t_hist, const double* sigma,
+                          double z_clip, uint32_t var_step, int64_t trials_per_device, unsigned long long* dev_switched, int64_t dev_stride,
+                          void* stream) {
+    SwitchPopArgs x{};
+    if (int rc = switch_stats_args(ctx, "stg_switch_population", G, R, trial0, trial_stride, P, m0, J, T, cond_cls, env_step, target, threshold,
+                                   n_bins, n_switched, n_failed, hist, !(P == 1 && kj > 0), x.t.w.s)) return rc;
+    if (int rc = switch_wave_args("watch_phase", false, watch_phase, P, kj, tj, jk, kh, th, hk, x.t.w)) return rc;
+    if (int rc = switch_passage_args(n_tbins, n_crossed, n_returned, t_hist, true, x.t)) return rc;
+    if (int rc = switch_vary_scalars(sigma, z_clip, trials_per_device)) return rc;
+    for (int32_t p = 0; p < P; ++p)
+        if (var_step == env_step + (uint32_t)p)
+            return fail(STG_E_INVALID, "var_step must differ from env_step + p for every phase p (the device's draw would reuse a thermal stream)");
+    const int64_t Q = trials_per_device;
+    if (dev_switched) {
+        // devices 0 ... (trial0 + R - 1) / Q of a condition must fit its row: ceil((trial0 + R) / Q), formed without overflow
+        const int64_t end = trial0 + R, need = end / Q + (end % Q != 0 ? 1 : 0);
+        if (dev_stride < need) return fail(STG_E_INVALID, "dev_stride must be >= (trial0 + R + Q - 1) / Q");
+        if (dev_stride > INT64_MAX / (int64_t)G) return fail(STG_E_INVALID, "G * dev_stride exceeds int64");
+    }
+    x.v.sigma = sigma; x.v.ptab = ctx->ptab; x.v.z_clip = z_clip; x.v.gamma = ctx->cfg.gamma; x.v.Q = Q; x.v.var_step = var_step;
+    x.v.dev_switched = dev_switched; x.v.dev_stride = dev_stride;
+    if (R == 0) return STG_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    stg_switch_vary_launch(x, n_crossed != nullptr, ctx->cfg.solver, thermal_flag(ctx->cfg), (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return STG_OK;
+}
+
+int stg_switch_population_devices(stg_ctx* ctx, int32_t G, int64_t D, int64_t dev0, int64_t trials_per_device, int64_t trial_stride,
+                                  uint32_t var_step, double z_clip, const double* sigma, const uint8_t* cond_cls, double* params, double* z,
+                                  void* stream) {
+    if (!ctx) return fail(STG_E_INVALID, "ctx is NULL");
+    if (!ctx->have_params) return fail(STG_E_STATE, "stg_set_params must precede stg_switch_population_devices");
+    if (ctx->per_env) return fail(STG_E_STATE, "stg_switch_population_devices works on the class table (stg_set_params), not on per-env parameters");
+    if (!params) return fail(STG_E_INVALID, "params must not be NULL");
+    if (G < 1) return fail(STG_E_INVALID, "G must be >= 1");
+    if (D < 0 || dev0 < 0) return fail(STG_E_INVALID, "D and dev0 must be >= 0");
+    if (int rc = switch_vary_scalars(sigma, z_clip, trials_per_device)) return rc;
+    if (trial_stride < 1 || trial_stride > (INT64_MAX - ctx->env_id0) / (int64_t)G) return fail(STG_E_INVALID, "env_id0 + G * trial_stride exceeds int64");
+    if (D > 0 && (D - 1 > INT64_MAX - dev0 || dev0 + D - 1 > (trial_stride - 1) / trials_per_device))
+        return fail(STG_E_INVALID, "(dev0 + D - 1) * trials_per_device must be < trial_stride");
+    if (D > INT64_MAX / (int64_t)G / 6 || (int64_t)G * D > (int64_t)UINT32_MAX * 256) return fail(STG_E_INVALID, "G * D too large");
+    if (D == 0) return STG_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int64_t n = (int64_t)G * D;
+    hipLaunchKernelGGL(stg_population_devices_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ctx->cfg.seed,
+                       ctx->env_id0, G, D, dev0, trials_per_device, trial_stride, var_step, z_clip, sigma, ctx->ptab, cond_cls, ctx->ncls, params, z);
+    HIP_TRY(hipGetLastError());
+    return STG_OK;
 }
 
 int stg_get_state(stg_ctx* ctx, double* m, double* target, double* total_energy, int32_t* step_count, uint32_t* rng_step,

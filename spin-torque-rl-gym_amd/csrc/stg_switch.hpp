@@ -1,6 +1,7 @@
 // stg_switch.hpp -- the Monte-Carlo switching family: the argument blocks, the first-passage observer and the ONE trial kernel of
-// stg_switch_stats, stg_switch_stats_wave and stg_switch_times (C-ABI: spintorque_hip.hip), (rk4 | euler | rk45) x thermal x class
-// table x WAVE x TIMES, fp64.  The kernel is instantiated per solver in stg_switch_rk4.hip / _euler.hip / _rk45.hip and nowhere else.
+// stg_switch_stats, stg_switch_stats_wave, stg_switch_times and stg_switch_population (C-ABI: spintorque_hip.hip), (rk4 | euler | rk45)
+// x thermal x class table x WAVE x TIMES, and VARY x thermal x WAVE x TIMES, fp64.  The kernel is instantiated per solver in
+// stg_switch_rk4.hip / _euler.hip / _rk45.hip and nowhere else.
 //
 // One 64-lane wavefront per workgroup works on ONE condition g: its m0, phase table, target, class row and waveform tables are
 // wave-uniform (scalar loads, the tables staged in LDS), and the sub-step count of a fixed-step phase is the same in every lane.  A lane
@@ -14,11 +15,16 @@
 //          there (SharedKnots, unscaled: the same doubles GlobalKnots hands Pwl for a replicated table, so Pwl gives the same bits).
 //   TIMES  phase `wave_phase` -- rectangular or tabled -- runs with RECORD set and FirstPassage as its observer: the rows it sees are
 //          the rows stg_solve_traj / stg_solve_wave record.  The time histogram's LDS is sized by the launch: 8 n_tbins bytes.
-// An instantiation without a flag holds nothing of what the flag brings: no staged tables, no observer, no extra counts.
+//   VARY   (stg_switch_population) every lane draws the device its trial belongs to (stg_vary.hpp: device r / Q, five clipped normals
+//          of the device's own stream scale the nominal record's damping, Ms, K_u, volume and polarization), derives that device's row
+//          with derive_row -- the arithmetic of a class table row -- into a private array, and runs every phase, plain, tabled and
+//          watched alike, on it instead of the wave-uniform row.  The draw is kept while a lane's next trial is the same device's.
+// An instantiation without a flag holds nothing of what the flag brings: no staged tables, no observer, no extra counts, no row of its own.
 // (Constants fold the flagged statements away; their order is kept as it is on purpose: the TIMES instantiations compile to the same
 // machine code as before the three entries were merged -- profiles/NOTEBOOK.md, round 23.)
 #pragma once
 #include "stg_wave.hpp"
+#include "stg_vary.hpp"
 
 struct SwitchStatsArgs {
     CfgView c;
@@ -51,6 +57,33 @@ struct SwitchTimesArgs {
     unsigned long long *n_crossed, *n_returned, *t_hist;   // [G], [G], [G][n_tbins] (nullptr iff n_tbins == 0): added to
 };
 
+// stg_switch_population: every lane draws the device of its trial and integrates with that device's own row (stg_vary.hpp: the rule)
+struct SwitchVaryArgs {
+    const double* sigma;              // [STG_NVARY][G]
+    const stg_device_params* ptab;    // the context's class table as the caller gave it (the nominal records), [ncls]
+    double z_clip, gamma;
+    int64_t Q;                        // trials per device
+    uint32_t var_step;
+    unsigned long long* dev_switched; // [G][dev_stride], indexed by the absolute device id: added to; or nullptr
+    int64_t dev_stride;
+};
+struct SwitchPopArgs {
+    SwitchTimesArgs t;                // as stg_switch_times
+    SwitchVaryArgs v;
+};
+
+// One device of the population: its six normals -- calls 0 and 1 of the thermal stream of `dev_env` at counter word var_step, the
+// values stg_thermal_normals dumps -- and its record (vary_params on the first five).  The trial kernel and the diagnostic dump both
+// call this and nothing else.
+__device__ __forceinline__ void vary_draw(uint64_t seed, uint64_t dev_env, uint32_t var_step, const stg_device_params& nominal,
+                                          const double* sigma, int64_t G, int64_t g, double z_clip, double (&z)[6], stg_device_params& out) {
+    NormalStream s;
+    s.init(seed, dev_env, var_step, 0u);
+    const V3 a = s.draw3_even(), b = s.draw3_odd();
+    z[0] = a.x; z[1] = a.y; z[2] = a.z; z[3] = b.x; z[4] = b.y; z[5] = b.z;
+    vary_params(nominal, sigma, G, g, z, z_clip, out);
+}
+
 // The per-point observer of the watched phase (the REC parameter of the solvers, stg_physics.hpp: Recorder): the first passage of
 // m . target over `threshold`, kept in three values per lane (crossed, t_x, t_prev: two fp64 register pairs and one bit of a wave mask).
 // It stores nothing and wants no energy and no torque norm.
@@ -81,9 +114,16 @@ static_assert(STG_MAX_KNOTS <= 64, "lane j stages knot j");
 
 using SwitchSource = WaveSourceT<Pwl<1, SharedKnots<1, false>>, Pwl<3, SharedKnots<3, false>>>;
 
-template <int SOLVER, bool THERMAL, bool MULTI, bool WAVE, bool TIMES>
-__global__ void __launch_bounds__(64) stg_switch_kernel(const SwitchTimesArgs x) {
+// The kernel's argument block: SwitchTimesArgs, or -- VARY -- SwitchPopArgs.  (The body reaches the block through `x`, set by a plain
+// member access: handing the kernel argument to a function by reference, a forced-inline one included, changes the register allocation
+// of every instantiation -- profiles/NOTEBOOK.md, round 24.)  Under VARY the class table only selects the nominal record, so MULTI is a
+// run-time matter there -- cond_cls may be NULL -- and VARY is instantiated with MULTI = true alone.
+template <int SOLVER, bool THERMAL, bool MULTI, bool WAVE, bool TIMES, bool VARY>
+__global__ void __launch_bounds__(64) stg_switch_kernel(const std::conditional_t<VARY, SwitchPopArgs, SwitchTimesArgs> xa) {
     static_assert(STG_MAX_BINS == 64, "lane b owns bin b");
+    const SwitchTimesArgs* xp;
+    if constexpr (VARY) xp = &xa.t; else xp = &xa;
+    const SwitchTimesArgs& x = *xp;
     __shared__ unsigned long long s_hist[STG_MAX_BINS];
     __shared__ double s_knots[WAVE ? STG_SHAPE_DOUBLES : 1];
     extern __shared__ unsigned long long s_thist[];                                // [n_tbins]
@@ -111,9 +151,20 @@ __global__ void __launch_bounds__(64) stg_switch_kernel(const SwitchTimesArgs x)
     }
     __syncthreads();
     const double* row = a.ctab;
+    int nominal_cls = 0;                                                           // (VARY: the condition's nominal record)
     if (MULTI) {
         const int c = a.cond_cls ? (int)a.cond_cls[g] : 0;
         row = a.ctab + (c < a.ncls ? c : 0) * C_COUNT;
+        nominal_cls = c < a.ncls ? c : 0;
+    }
+    // VARY: the lane's own row of derived constants (constant indices only: the array dissolves into registers), the device it was
+    // derived for, and whether the condition's sigma column is valid (wave-uniform)
+    double own_row[VARY ? C_COUNT : 1];
+    int64_t own_dev = -1;
+    bool sigma_ok = true;
+    if constexpr (VARY) {
+        sigma_ok = vary_column_ok(xa.v.sigma, G, g, xa.v.z_clip);
+        row = own_row;
     }
     const V3 m0{a.m0[g], a.m0[G + g], a.m0[2 * G + g]};
     const V3 tg{a.target[g], a.target[G + g], a.target[2 * G + g]};
@@ -139,12 +190,29 @@ __global__ void __launch_bounds__(64) stg_switch_kernel(const SwitchTimesArgs x)
         V3 m = m0;
         bool failed = false;
         FirstPassage fp{tg, a.threshold, 0.0, 0.0, false};                         // (TIMES: with RECORD off no solver touches it)
+        int64_t dev = 0;                                                           // (VARY: this trial's device)
+        if constexpr (VARY) {
+            dev = vary_device_of(a.trial0 + r, xa.v.Q);
+            if (active && sigma_ok && dev != own_dev) {
+                // a new device: its record from its own stream, its row by the arithmetic that builds a class table row
+                const int64_t dev_env = vary_device_env(a.env_id0, g, a.trial_stride, dev, xa.v.Q);
+                double z[6];
+                stg_device_params dp;
+                vary_draw(a.c.seed, (uint64_t)dev_env, xa.v.var_step, xa.v.ptab[nominal_cls], xa.v.sigma, G, g, xa.v.z_clip, z, dp);
+                derive_row(dp, xa.v.gamma, a.c.temperature, own_row);
+                own_dev = dev;
+            }
+        }
         if (active) {
             InlineNormals ns;
 #pragma clang loop unroll(disable)
             for (int32_t p = 0; p < a.P && !failed; ++p) {
                 const double Tp = a.T[(int64_t)p * G + g];
                 if (Tp == 0.0) continue;
+                if (VARY && !sigma_ok) {                                           // a bad sigma column: the first phase that would run fails
+                    failed = true;
+                    break;
+                }
                 // the tabled and / or watched phase (a compile-time `false` without a flag: the plain kernel keeps ONE call site of run_solver)
                 const bool watched = (WAVE || TIMES) && p == w.wave_phase;
                 const double Jp = (watched && has_j) ? 0.0 : a.J[(int64_t)p * G + g];
@@ -191,6 +259,22 @@ __global__ void __launch_bounds__(64) stg_switch_kernel(const SwitchTimesArgs x)
         n_fail += (unsigned long long)__popcll(__ballot(active && failed));
         n_cr += (unsigned long long)__popcll(__ballot(crossed));
         n_ret += (unsigned long long)__popcll(__ballot(crossed && !switched));
+        if constexpr (VARY) {
+            // per-device counts: one atomic for the wavefront where the round's live lanes share a device (wave-uniform test on the
+            // round's first and last live trial), one per switched lane where they straddle devices
+            const int64_t r_first = (wv * a.L + l) * 64;
+            if (xa.v.dev_switched && r_first < a.R) {
+                const int64_t r_last = r_first + 63 < a.R ? r_first + 63 : a.R - 1;
+                const int64_t d_first = vary_device_of(a.trial0 + r_first, xa.v.Q), d_last = vary_device_of(a.trial0 + r_last, xa.v.Q);
+                unsigned long long* cnt = xa.v.dev_switched + (int64_t)g * xa.v.dev_stride;
+                const unsigned long long sw = __ballot(switched);
+                if (d_first == d_last) {
+                    if (lane == 0 && sw) atomicAdd(cnt + d_first, (unsigned long long)__popcll(sw));
+                } else if (switched) {
+                    atomicAdd(cnt + dev, 1ull);
+                }
+            }
+        }
         if (active && a.n_bins > 0) {
             // min(n_bins - 1, max(0, (int)floor(x))), clamped before the conversion: NaN -> bin 0, +-inf and huge values -> the outer bins
             const double b = floor(mul_x(add_x(proj, 1.0), bin_scale));
@@ -220,6 +304,16 @@ __global__ void __launch_bounds__(64) stg_switch_kernel(const SwitchTimesArgs x)
     }
 }
 
+// one solver's 8 population kernels (VARY, with MULTI = true); `times`: the caller wants the first-passage counts
+template <int SOLVER>
+static void dispatch_switch_vary(const SwitchPopArgs& x, bool times, bool thermal, hipStream_t st) {
+    const dim3 grid((unsigned)((int64_t)x.t.w.s.G * x.t.w.s.waves_per_cond));
+    const size_t lds = times ? sizeof(unsigned long long) * (size_t)x.t.n_tbins : 0;
+    with_flag(thermal, [&](auto THERMAL) { with_flag(x.t.w.kj > 0 || x.t.w.kh > 0, [&](auto WAVE) { with_flag(times, [&](auto TIMES) {
+        hipLaunchKernelGGL((stg_switch_kernel<SOLVER, THERMAL.value, true, WAVE.value, TIMES.value, true>), grid, dim3(64), lds, st, x);
+    }); }); });
+}
+
 // one solver's 16 kernels; WAVE: a table is there.  `times` is the entry, not the arguments: stg_switch_times with n_tbins = 0 still counts
 template <int SOLVER>
 static void dispatch_switch(const SwitchTimesArgs& x, bool times, bool thermal, bool multi, hipStream_t st) {
@@ -227,7 +321,7 @@ static void dispatch_switch(const SwitchTimesArgs& x, bool times, bool thermal, 
     const size_t lds = times ? sizeof(unsigned long long) * (size_t)x.n_tbins : 0;
     with_flag(thermal, [&](auto THERMAL) { with_flag(multi, [&](auto MULTI) { with_flag(x.w.kj > 0 || x.w.kh > 0, [&](auto WAVE) {
         with_flag(times, [&](auto TIMES) {
-            hipLaunchKernelGGL((stg_switch_kernel<SOLVER, THERMAL.value, MULTI.value, WAVE.value, TIMES.value>), grid, dim3(64), lds, st, x);
+            hipLaunchKernelGGL((stg_switch_kernel<SOLVER, THERMAL.value, MULTI.value, WAVE.value, TIMES.value, false>), grid, dim3(64), lds, st, x);
         });
     }); }); });
 }
@@ -243,5 +337,17 @@ inline void stg_switch_launch(const SwitchTimesArgs& x, bool times, int solver, 
         case STG_SOLVER_RK4: stg_dispatch_switch_rk4(x, times, thermal, multi, st); break;
         case STG_SOLVER_EULER: stg_dispatch_switch_euler(x, times, thermal, multi, st); break;
         default: stg_dispatch_switch_rk45(x, times, thermal, multi, st); break;
+    }
+}
+
+// the same for stg_switch_population
+void stg_dispatch_switch_vary_rk4(const SwitchPopArgs& x, bool times, bool thermal, hipStream_t st);
+void stg_dispatch_switch_vary_euler(const SwitchPopArgs& x, bool times, bool thermal, hipStream_t st);
+void stg_dispatch_switch_vary_rk45(const SwitchPopArgs& x, bool times, bool thermal, hipStream_t st);
+inline void stg_switch_vary_launch(const SwitchPopArgs& x, bool times, int solver, bool thermal, hipStream_t st) {
+    switch (solver) {
+        case STG_SOLVER_RK4: stg_dispatch_switch_vary_rk4(x, times, thermal, st); break;
+        case STG_SOLVER_EULER: stg_dispatch_switch_vary_euler(x, times, thermal, st); break;
+        default: stg_dispatch_switch_vary_rk45(x, times, thermal, st); break;
     }
 }

@@ -20,6 +20,7 @@ STG_MAX_TBINS = 1024     # time bins of stg_switch_times
 SWITCH_STATS_WAVES = 12288  # STG_SWITCH_STATS_WAVES: above this many wavefronts in a launch, the lanes of stg_switch_stats loop over trials
 ABI_VERSION = 5         # STG_ABI_VERSION of include/spintorque_hip.h this binding was written against
 STG_NPARAM = 30          # double-valued fields of stg_device_params, in declaration order
+STG_NVARY = 5            # the first of them vary from device to device in stg_switch_population: damping, ms, ku, volume, polarization
 SOLVERS = {"rk4": 0, "euler": 1, "rk45": 2}
 DEV_TYPES = {"stt_mram": 0, "sot_mram": 1, "vcma_mram": 2}
 OUT_LAYOUTS = {"soa": 0, "records": 1}
@@ -90,6 +91,11 @@ SYMBOLS = {
     "stg_switch_times": (C.c_int, [_VP, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP,
                                    C.c_int32, _VP, _VP, _VP, C.c_uint32, _VP, C.c_double, C.c_int32, _VP, _VP, _VP, C.c_int32, _VP, _VP, _VP,
                                    _VP]),
+    "stg_switch_population": (C.c_int, [_VP, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP,
+                                        C.c_int32, _VP, _VP, _VP, C.c_uint32, _VP, C.c_double, C.c_int32, _VP, _VP, _VP, C.c_int32, _VP, _VP, _VP,
+                                        _VP, C.c_double, C.c_uint32, C.c_int64, _VP, C.c_int64, _VP]),
+    "stg_switch_population_devices": (C.c_int, [_VP, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, C.c_double, _VP, _VP, _VP,
+                                                _VP, _VP]),
     "stg_step_wave": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                 _VP]),
     "stg_set_pulse_shape": (C.c_int, [_VP, C.c_int32, _VP, _VP, C.c_int32, _VP, _VP]),

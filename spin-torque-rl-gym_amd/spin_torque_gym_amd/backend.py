@@ -623,6 +623,53 @@ class HipBackend:
         self._keep += (tj, jk, th, hk)
         return out
 
+    def switch_population(self, m0, J, T, target, n_trials, sigma, watch_phase=0, wave=None, n_tbins=0, passage=None, z_clip=4.0,
+                          var_step=2 ** 31, trials_per_device=1, dev_switched=None, trial0=0, trial_stride=None, cond_cls=None, env_step=0,
+                          threshold=0.0, n_bins=0, out=None):
+        """switch_times over a population of devices (stg_switch_population): trial r (absolute) of condition g belongs to device
+        r // trials_per_device, whose damping, Ms, K_u, volume and polarization are the condition's nominal ones (its class of
+        set_params) times 1 + sigma[k, g] * clip(z_k, +- z_clip), z from the stream of the device's first trial at counter word
+        var_step; the trial integrates with that device's own constants.  sigma float64 [5, G].  passage (None: n_tbins > 0) asks for
+        the first-passage counts; without them the tuple is (n_switched, n_failed, hist) as switch_stats returns it, with them the six
+        of switch_times.  dev_switched int64 [G, dev_stride] on the device, indexed by the absolute device id, is added to as well
+        when given.  Everything else, `out` included, as switch_times.  Enqueues only."""
+        passage = n_tbins > 0 if passage is None else bool(passage)
+        (g, r, t0, stride, p), (m0, J, T, target, cond_cls), out = self._switch_args(
+            m0, J, T, target, n_trials, trial0, trial_stride, cond_cls, (n_bins, n_tbins) if passage else (n_bins,), out)
+        kj, tj, jk, kh, th, hk = self._wave_tables(wave, g) if wave is not None else (0, None, None, 0, None, None)
+        sigma = self._dev(sigma, torch.float64, (_lib.STG_NVARY, g))
+        n_sw, n_failed, hist, n_cr, n_ret, t_hist = tuple(out) + (() if passage else (None, None, None))
+        dev_stride = 0
+        if dev_switched is not None:
+            if (not torch.is_tensor(dev_switched) or dev_switched.dtype != torch.int64 or dev_switched.dim() != 2 or dev_switched.shape[0] != g
+                    or not dev_switched.is_contiguous() or not dev_switched.is_cuda):
+                raise ValueError(f"dev_switched must be a contiguous int64 tensor [G = {g}, dev_stride] on {self.device}")
+            dev_stride = int(dev_switched.shape[1])
+        _lib.check(self.lib.stg_switch_population(self._ctx, g, r, t0, stride, p, _ptr(m0), _ptr(J), _ptr(T), int(watch_phase), kj, _ptr(tj),
+                                                  _ptr(jk), kh, _ptr(th), _ptr(hk), _ptr(cond_cls), int(env_step), _ptr(target),
+                                                  float(threshold), int(n_bins), _ptr(n_sw), _ptr(n_failed), _ptr(hist), int(n_tbins),
+                                                  _ptr(n_cr), _ptr(n_ret), _ptr(t_hist), _ptr(sigma), float(z_clip), int(var_step),
+                                                  int(trials_per_device), _ptr(dev_switched), dev_stride, self._stream()))
+        self._keep += (tj, jk, th, hk, sigma)
+        return out
+
+    def switch_population_devices(self, n_cond, n_devices, sigma, dev0=0, trials_per_device=1, trial_stride=None, var_step=2 ** 31,
+                                  z_clip=4.0, cond_cls=None, want_z=False):
+        """The devices switch_population draws, made observable (stg_switch_population_devices): params float64 [5, G, D] -- damping,
+        Ms, K_u, volume, polarization of devices dev0 ... dev0 + D - 1 of each of the G = n_cond conditions (NaN for a condition with
+        a bad sigma column) -- and, with want_z, their six normals [6, G, D].  trial_stride None: (dev0 + D) * trials_per_device.
+        Returns params, or (params, z).  Enqueues only."""
+        g, d, q = int(n_cond), int(n_devices), int(trials_per_device)
+        sigma = self._dev(sigma, torch.float64, (_lib.STG_NVARY, g))
+        cond_cls = self._dev(cond_cls, torch.uint8, (g,))
+        stride = (int(dev0) + d) * q if trial_stride is None else int(trial_stride)
+        params = torch.empty((_lib.STG_NVARY, g, d), dtype=torch.float64, device=self.device)
+        z = torch.empty((6, g, d), dtype=torch.float64, device=self.device) if want_z else None
+        _lib.check(self.lib.stg_switch_population_devices(self._ctx, g, d, int(dev0), q, stride, int(var_step), float(z_clip), _ptr(sigma),
+                                                          _ptr(cond_cls), _ptr(params), _ptr(z), self._stream()))
+        self._keep = (sigma, cond_cls)
+        return (params, z) if want_z else params
+
     def device_terms(self, m, J, volt):
         """Device-class formulas per env: (tau_dl [3,N], tau_fl [3,N], k_eff [N]) for m [3,N], J [N], volt [N]."""
         n, dev = self.n, self.device

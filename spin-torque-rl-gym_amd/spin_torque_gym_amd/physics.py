@@ -163,6 +163,36 @@ def _check_zero_field(field_func: Optional[Callable], t0: float, t1: float) -> N
                                       "CPU solver")
 
 
+# the device parameters that vary from device to device in a population (stg_switch_population), in the order of the library's sigma rows
+VARIATION_KEYS = ("damping", "saturation_magnetization", "uniaxial_anisotropy", "volume", "polarization")
+
+
+def _variation_sigma(variation, g: int, clip: float) -> np.ndarray:
+    """variation {key: relative sigma, scalar or [G]} -> sigma float64 [5, G]; missing keys are 0.  Raises on unknown keys, on a sigma
+    that is negative or not finite, on a clip that is not finite and positive, and on sigma * clip >= 1 (a parameter could come out
+    non-positive)."""
+    if not isinstance(variation, dict):
+        raise TypeError("variation must be a dict {parameter name: relative sigma} or None")
+    unknown = sorted(set(variation) - set(VARIATION_KEYS))
+    if unknown:
+        raise ValueError(f"variation: unknown keys {unknown}; the parameters that vary are {list(VARIATION_KEYS)}")
+    clip = float(clip)
+    if not (np.isfinite(clip) and clip > 0):
+        raise ValueError("variation_clip must be finite and > 0")
+    sigma = np.zeros((len(VARIATION_KEYS), g), dtype=np.float64)
+    for k, name in enumerate(VARIATION_KEYS):
+        if name in variation:
+            s = np.asarray(variation[name], dtype=np.float64)
+            if s.ndim > 1 or (s.ndim == 1 and s.shape[0] != g):
+                raise ValueError(f"variation[{name!r}] must be a scalar or have shape [G] with G = {g}, got {s.shape}")
+            sigma[k] = s
+    if not np.isfinite(sigma).all() or (sigma < 0).any():
+        raise ValueError("variation: every sigma must be finite and >= 0")
+    if (sigma * clip >= 1.0).any():
+        raise ValueError("variation: sigma * variation_clip must stay below 1 (a clipped draw could make a parameter non-positive)")
+    return sigma
+
+
 class _GpuSolverBase:
     _solver_name = "rk4"
     _validate_params = False        # (RobustLLGSSolver turns the parameter gate on)
@@ -231,7 +261,8 @@ class _GpuSolverBase:
                              target=(0.0, 0.0, -1.0), threshold: float = 0.0, n_bins: int = 0, temperature: float = 300.0,
                              device_type="stt_mram", class_index=None, env_step: int = 0, trial_offset: int = 0, trial_stride=None,
                              max_trials_per_launch: int = 2 ** 22, current_knots=None, field_knots=None, time_bins: int = 0,
-                             watch_phase: int = 0) -> Dict[str, Any]:
+                             watch_phase: int = 0, variation=None, variation_clip: float = 4.0, variation_step: int = 2 ** 31,
+                             trials_per_device: int = 1, per_device: bool = False) -> Dict[str, Any]:
         """Monte-Carlo switching statistics of G conditions with R = n_trials thermal trials each, with the trial loop and the
         reduction on the GPU (stg_switch_stats): no per-trial array exists, so R is bounded by time, not by memory.
 
@@ -267,7 +298,19 @@ class _GpuSolverBase:
         p_cross for every pulse width up to the duration from one run -- and t_mean, t_std [G] over the crossed trials, formed
         from the bin centres (NaN where nobody crossed).  The moments are exact to one bin width; time_bins = n, the pulse's
         sub-step count, resolves every sub-step of a fixed-step solver.  With time_bins == 0 the call is exactly the one above: watch_phase is
-        still checked against the number of phases, but has no meaning then."""
+        still checked against the number of phases, but has no meaning then.
+
+        variation = {"damping": s, "saturation_magnetization": s, "uniaxial_anisotropy": s, "volume": s, "polarization": s} (each s a
+        relative sigma, scalar or [G]; missing keys are 0) turns the R trials of a condition into trials of a POPULATION of devices
+        around device_params (stg_switch_population): the statistics of a chip whose bits scatter, not of one device.  Trial r
+        (counted from 0, trial_offset included) belongs to device r // trials_per_device; that device's five parameters are the
+        nominal ones times 1 + s * clip(z, +- variation_clip), z standard normal from the stream of the device's first trial at
+        counter word variation_step (which must differ from env_step + p of every phase), and the trial integrates with that device's
+        own constants, thermal strength included.  A device depends on the seed, on its own index and on trial_stride alone, so
+        launches, chunks and ranks see the same chip.  The result gains n_devices [G], the devices the trial range touches;
+        per_device = True also returns dev_switched [G, n_dev], dev_trials [G, n_dev] (the first and the last device may be partial)
+        and dev_p_switch = their ratio, for devices trial_offset // trials_per_device onwards (the count array held on the GPU is
+        indexed from device 0).  `draw_devices` returns the devices themselves.  variation = None is exactly the call above."""
         m0 = np.asarray(m_initial.cpu() if torch.is_tensor(m_initial) else m_initial, dtype=np.float64).reshape(-1, 3)
         g, r = int(m0.shape[0]), int(n_trials)
         if r < 1:
@@ -323,23 +366,43 @@ class _GpuSolverBase:
         stride = int(trial_offset) + r if trial_stride is None else int(trial_stride)
         if int(trial_offset) < 0 or stride < int(trial_offset) + r:
             raise ValueError("trial_offset must be >= 0 and trial_stride >= trial_offset + n_trials")
+        sigma, q, dev_first, n_dev = None, int(trials_per_device), 0, 0
+        if variation is not None:
+            sigma = _variation_sigma(variation, g, variation_clip)
+            if q < 1:
+                raise ValueError("trials_per_device must be >= 1")
+            if not 0 <= int(variation_step) < 2 ** 32 or (int(variation_step) - int(env_step)) % 2 ** 32 < J.shape[0]:
+                raise ValueError("variation_step must be a 32-bit counter word other than env_step + p of the trial's phases")
+            dev_first = int(trial_offset) // q
+            n_dev = (int(trial_offset) + r - 1) // q - dev_first + 1
         cfg = EnvConfig(solver=self._solver_name, include_thermal_fluctuations=True, temperature=float(temperature), gamma=self.gamma,
                         max_step=self.max_step, rtol=self.rtol, atol=self.atol, seed=self._seed, noise_model=self.noise_model,
                         correlation_time=self.correlation_time)
         b = self._backend_factory(g, cfg, self.device_index, 0)
+        dev_sw = None
         try:
             b.set_params([_flat_for(p, t, self._validate_params) for p, t in zip(tables, types)], cls)
             out, step = None, int(max_trials_per_launch)
             # (without knots: exactly the rectangular call; a backend without waveforms is never asked for them)
-            launch = b.switch_stats if wave is None else functools.partial(b.switch_stats_wave, wave=wave, wave_phase=int(wave_phase))
-            if time_bins > 0:
-                launch = functools.partial(b.switch_times, watch_phase=int(wave_phase) + int(watch_phase), wave=wave, n_tbins=int(time_bins))
+            if sigma is None:
+                launch = b.switch_stats if wave is None else functools.partial(b.switch_stats_wave, wave=wave, wave_phase=int(wave_phase))
+                if time_bins > 0:
+                    launch = functools.partial(b.switch_times, watch_phase=int(wave_phase) + int(watch_phase), wave=wave, n_tbins=int(time_bins))
+            else:
+                # the chunks below keep absolute trial indices, so every launch sees the same devices and adds into the same counts
+                if per_device:
+                    dev_sw = torch.zeros((g, dev_first + n_dev), dtype=torch.int64, device=b.device)
+                launch = functools.partial(b.switch_population, sigma=torch.from_numpy(sigma), watch_phase=int(wave_phase) + int(watch_phase),
+                                           wave=wave, n_tbins=int(time_bins), passage=time_bins > 0, z_clip=float(variation_clip),
+                                           var_step=int(variation_step), trials_per_device=q, dev_switched=dev_sw)
             for done in range(0, r, step):
                 out = launch(torch.from_numpy(np.ascontiguousarray(m0.T)), torch.from_numpy(J), torch.from_numpy(T),
                              torch.from_numpy(tgt), min(step, r - done), trial0=int(trial_offset) + done, trial_stride=stride,
                              cond_cls=cls, env_step=env_step, threshold=float(threshold), n_bins=int(n_bins), out=out)
             n_sw, n_failed = (x.cpu().numpy().astype(np.int64) for x in out[:2])
             hist = out[2].cpu().numpy().astype(np.int64) if n_bins > 0 else np.zeros((g, 0), dtype=np.int64)
+            if dev_sw is not None:
+                dev_sw = dev_sw[:, dev_first:].cpu().numpy().astype(np.int64)
         finally:
             b.close()
         self.solve_count += g * r
@@ -356,6 +419,58 @@ class _GpuSolverBase:
                 t_var = (t_hist * (centres - t_mean[:, None]) ** 2).sum(axis=1) / binned
             res.update({"n_crossed": n_cr, "n_returned": n_ret, "p_cross": n_cr / r, "t_hist": t_hist, "t_edges": t_edges,
                         "p_cross_by": np.cumsum(t_hist, axis=1) / r, "t_mean": t_mean, "t_std": np.sqrt(t_var)})
+        if sigma is not None:
+            res["n_devices"] = np.full(g, n_dev, dtype=np.int64)
+            if per_device:
+                # trials of each touched device inside [trial_offset, trial_offset + R): the first and the last may be partial
+                lo = np.maximum((dev_first + np.arange(n_dev, dtype=np.int64)) * q, int(trial_offset))
+                hi = np.minimum((dev_first + np.arange(n_dev, dtype=np.int64) + 1) * q, int(trial_offset) + r)
+                dev_trials = np.broadcast_to(hi - lo, (g, n_dev)).copy()
+                res.update({"dev_switched": dev_sw, "dev_trials": dev_trials, "dev_p_switch": dev_sw / dev_trials})
+        return res
+
+    def draw_devices(self, device_params, n_devices: int, variation, *, n_conditions: int = 1, variation_clip: float = 4.0,
+                     variation_step: int = 2 ** 31, trials_per_device: int = 1, trial_stride=None, first_device: int = 0,
+                     device_type="stt_mram", class_index=None, temperature: float = 300.0) -> Dict[str, Any]:
+        """The devices `switching_statistics(variation=...)` draws for the same seed, variation, variation_clip, variation_step,
+        trials_per_device and trial_stride (None: (first_device + n_devices) * trials_per_device, which is that method's default for
+        a trial range ending with device first_device + n_devices - 1): devices first_device ... first_device + n_devices - 1 of each
+        of n_conditions conditions, through the library's own draw (stg_switch_population_devices).  device_params, device_type and
+        class_index as there.  Returns dict(device_params: per condition, a list of n_devices dicts -- the condition's nominal dict
+        with the five varied entries replaced, fit to be handed back as device_params --, one float64 array [G, D] per varied key,
+        and z [6, G, D], each device's six standard normals, the last of which is unused)."""
+        g, d = int(n_conditions), int(n_devices)
+        if g < 1 or d < 1:
+            raise ValueError("n_conditions and n_devices must be >= 1")
+        sigma = _variation_sigma(variation, g, variation_clip)
+        tables = device_params if isinstance(device_params, (list, tuple)) else [device_params]
+        types = device_type if isinstance(device_type, (list, tuple)) else [device_type] * len(tables)
+        if not 1 <= len(tables) <= 64 or len(types) != len(tables):
+            raise ValueError("device_params is one dict or a list of 1 ... 64 dicts (with as many device types, or one)")
+        cls_np, cls = np.zeros(g, dtype=np.int64), None
+        if len(tables) > 1:
+            if class_index is None:
+                raise ValueError("class_index [G] is required with more than one device_params dict")
+            cls_np = np.asarray(class_index).reshape(g)
+            if cls_np.min() < 0 or cls_np.max() >= len(tables):
+                raise ValueError("class_index out of range")
+            cls = torch.from_numpy(cls_np.astype(np.uint8))
+        cfg = EnvConfig(solver=self._solver_name, include_thermal_fluctuations=True, temperature=float(temperature), gamma=self.gamma,
+                        max_step=self.max_step, rtol=self.rtol, atol=self.atol, seed=self._seed, noise_model=self.noise_model,
+                        correlation_time=self.correlation_time)
+        b = self._backend_factory(g, cfg, self.device_index, 0)
+        try:
+            b.set_params([_flat_for(p, t, self._validate_params) for p, t in zip(tables, types)], cls)
+            params, z = b.switch_population_devices(g, d, torch.from_numpy(sigma), dev0=int(first_device), trials_per_device=int(trials_per_device),
+                                                    trial_stride=trial_stride, var_step=int(variation_step), z_clip=float(variation_clip),
+                                                    cond_cls=cls, want_z=True)
+            params, z = params.cpu().numpy(), z.cpu().numpy()
+        finally:
+            b.close()
+        res = {name: params[k] for k, name in enumerate(VARIATION_KEYS)}
+        res["z"] = z
+        res["device_params"] = [[dict(tables[int(cls_np[i])], **{name: float(params[k, i, j]) for k, name in enumerate(VARIATION_KEYS)})
+                                 for j in range(d)] for i in range(g)]
         return res
 
     def _solve_one(self, m_initial, t_span, device_params, current_func, field_func, thermal_noise, temperature,
