@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "_build", "libstg_oracle.so")
 
 __all__ = ["Params", "Config", "EnvState", "StepOut", "lib", "build", "make_params", "make_config",
-           "simple_solve", "llgs_solve", "resistance", "thermal_strength", "env_step", "env_step_batch",
+           "simple_solve", "llgs_solve", "llgs_solve_wave", "pwl_eval", "resistance", "thermal_strength", "env_step", "env_step_batch",
            "thermal_normals", "parse_action", "parse_action_f64", "env_step_f64", "env_step_batch_f64", "simple_dmdt", "llgs_rhs", "DEV_TYPES", "sot_torque", "vcma_keff",
            "ArrayConfig", "make_array_config", "array_coupling", "ArrayEnvState", "array_step", "array_observation", "array_reset_draw",
            "device_field", "ou_update"]
@@ -91,6 +91,12 @@ def lib():
         L.stgo_llgs_solve.argtypes = [dp, C.c_double, C.POINTER(Params), C.POINTER(Config), C.c_double,
                                       C.c_uint64, C.c_uint32, dp, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                                       dp, dp, dp, dp, C.c_int64]
+        L.stgo_pwl_eval.restype = None
+        L.stgo_pwl_eval.argtypes = [C.c_int32, dp, dp, C.c_int32, C.c_double, dp]
+        L.stgo_llgs_solve_wave.restype = C.c_int64
+        L.stgo_llgs_solve_wave.argtypes = [dp, C.c_double, C.POINTER(Params), C.POINTER(Config), C.c_double, C.c_int32, dp, dp,
+                                           C.c_int32, dp, dp, C.c_uint64, C.c_uint32, dp, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                           dp, dp, dp, dp, dp, C.c_int64]
         L.stgo_resistance.restype = C.c_double
         L.stgo_resistance.argtypes = [dp, C.POINTER(Params)]
         L.stgo_thermal_strength.restype = C.c_double
@@ -301,6 +307,44 @@ def llgs_solve(m0, T, p, c, J, env_id=0, env_step=0, cap=20000):
                               C.byref(succ), C.byref(att), _dp(t), _dp(m), _dp(e), _dp(tq), cap)
     k = min(n, cap)
     return dict(success=bool(succ.value), m_final=mf, n_points=int(n), n_attempts=att.value,
+                t=t[:k].copy(), m=m[:k].copy(), energy=e[:k].copy(), torques=tq[:k].copy())
+
+
+def pwl_eval(times, values, t):
+    """PiecewiseLinear.__call__ as the C oracle restates it (stgo_pwl_eval): values [K] -> float, [K,3] -> ndarray [3]."""
+    tk = np.ascontiguousarray(times, dtype=np.float64)
+    vk = np.ascontiguousarray(values, dtype=np.float64)
+    width = 1 if vk.ndim == 1 else 3
+    assert tk.ndim == 1 and len(tk) >= 2 and vk.shape == ((len(tk),) if width == 1 else (len(tk), 3))
+    out = np.zeros(width)
+    lib().stgo_pwl_eval(len(tk), _dp(tk), _dp(vk), width, float(t), _dp(out))
+    return float(out[0]) if width == 1 else out
+
+
+def llgs_solve_wave(m0, T, p, c, J=0.0, current=None, field=None, env_id=0, env_step=0, cap=20000):
+    """stgo_llgs_solve_wave for one problem.  current = (times [K], values [K]) or None (the rectangular J while t <= T);
+    field = (times [K], values [K,3]) or None (no field).  Returns llgs_solve's dict plus `tie`, the smallest |err_norm - 1| over all
+    attempts.  A bad table (not finite, not strictly increasing): success False, n_points 0, m_final = m0."""
+    m0 = np.ascontiguousarray(m0, dtype=np.float64)
+    kj = kh = 0
+    tj = jk = th = hk = None
+    if current is not None:
+        tj, jk = (np.ascontiguousarray(a, dtype=np.float64) for a in current)
+        kj = len(tj)
+        assert tj.shape == jk.shape == (kj,)
+    if field is not None:
+        th, hk = (np.ascontiguousarray(a, dtype=np.float64) for a in field)
+        kh = len(th)
+        assert th.shape == (kh,) and hk.shape == (kh, 3)
+    mf = np.zeros(3)
+    succ, att, tie = C.c_int32(0), C.c_int64(0), C.c_double(0.0)
+    t, m, e, tq = np.zeros(cap), np.zeros((cap, 3)), np.zeros(cap), np.zeros(cap)
+    opt = lambda a: _dp(a) if a is not None else None          # noqa: E731
+    n = lib().stgo_llgs_solve_wave(_dp(m0), float(T), C.byref(p), C.byref(c), float(J), kj, opt(tj), opt(jk), kh, opt(th), opt(hk),
+                                   env_id, env_step, _dp(mf), C.byref(succ), C.byref(att), C.byref(tie), _dp(t), _dp(m), _dp(e), _dp(tq),
+                                   cap)
+    k = min(n, cap)
+    return dict(success=bool(succ.value), m_final=mf, n_points=int(n), n_attempts=att.value, tie=tie.value,
                 t=t[:k].copy(), m=m[:k].copy(), energy=e[:k].copy(), torques=tq[:k].copy())
 
 

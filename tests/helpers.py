@@ -238,9 +238,19 @@ class OracleBackend:
             if st.get("done") is not None:
                 self.done[i] = int(st["done"][i])
 
-    def solve(self, m0, J, T, env_step=0, traj_cap=0, want_energy=False):
+    def solve(self, m0, J, T, env_step=0, traj_cap=0, want_energy=False, wave=None):
+        """wave: the dict HipBackend.solve takes -- current=(tj [K,N], jk [K,N]) | None, field=(th [K,N], hk [K,3,N]) | None --, for
+        solver='rk45' only (oracle.llgs_solve_wave; J may be None with a current table).  Fixed-step waveforms stay with
+        tests/waveform_ref.py: the C oracle does not integrate them."""
         m0 = torch.as_tensor(m0).cpu().numpy().astype(np.float64)
-        J = torch.as_tensor(J).cpu().numpy().astype(np.float64)
+        J = np.zeros(self.n) if J is None else torch.as_tensor(J).cpu().numpy().astype(np.float64)
+        cur = fld = None
+        if wave is not None:
+            if self.cfg.solver != "rk45":
+                raise ValueError("OracleBackend.solve(wave=) is RK45 only; fixed-step waveforms: tests/waveform_ref.py")
+            host = lambda a: torch.as_tensor(a).cpu().numpy().astype(np.float64)          # noqa: E731
+            cur = None if wave.get("current") is None else tuple(host(a) for a in wave["current"])
+            fld = None if wave.get("field") is None else tuple(host(a) for a in wave["field"])
         T = torch.as_tensor(T).cpu().numpy().astype(np.float64)
         n = self.n
         mf = np.zeros((3, n))
@@ -253,9 +263,14 @@ class OracleBackend:
         for i in range(n):
             p = self._p(i)
             if self.cfg.solver == "rk45":
-                r = oracle.llgs_solve(m0[:, i], T[i], p, self.ocfg, J[i], self.env_id0 + i, env_step, cap=max(traj_cap, 1))
+                if wave is not None:
+                    r = oracle.llgs_solve_wave(m0[:, i], T[i], p, self.ocfg, J[i], None if cur is None else (cur[0][:, i], cur[1][:, i]),
+                                               None if fld is None else (fld[0][:, i], fld[1][:, :, i]), self.env_id0 + i, env_step,
+                                               cap=max(traj_cap, 1))
+                else:
+                    r = oracle.llgs_solve(m0[:, i], T[i], p, self.ocfg, J[i], self.env_id0 + i, env_step, cap=max(traj_cap, 1))
                 mf[:, i] = r["m_final"] if r["success"] else m0[:, i]
-                npts[i] = r["n_points"] - 1
+                npts[i] = max(r["n_points"] - 1, 0)           # (a bad table: no point at all)
                 k = min(len(r["t"]), traj_cap)
                 tt[:k, i], tm[:k, :, i], te[:k, i], tq[:k, i] = r["t"][:k], r["m"][:k], r["energy"][:k], r["torques"][:k]
             else:

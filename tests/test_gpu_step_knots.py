@@ -392,7 +392,8 @@ def test_rk4_against_the_numpy_restatement(stg):
 def test_rk45_against_the_cpu_oracle(stg):
     """The NumPy restatement has no RK45.  The independent integrator for it is the CPU oracle's, which knows the rectangular pulse only:
     amplitudes at and beyond the limit of 1 -- all clamped to exactly 1 -- make the table the constant J over (0, T), the same drive.
-    m against the oracle's step; the energy against the closed form of the table in NumPy, and against the oracle's J^2 T form."""
+    m against the oracle's step; the energy against the closed form of the table in NumPy, and against the oracle's J^2 T form.
+    (Amplitudes that are NOT flat, against the oracle's waveform solve: tests/test_gpu_wave_rk45_oracle.py.)"""
     from spin_torque_gym_amd.backend import EnvConfig
     n, P = 65, 5
     p = stt_default_params(volume=VOL["rk45"][0])

@@ -6,7 +6,8 @@
      SpinTorqueVecEnv / SpinTorqueEnv(pulse_shape=, applied_field=): m within the tolerance tests/test_gpu_waveforms.py applies to the same
      device function, fp32 observations within one float32 ulp, flags exact, the energy against the closed form;
   3. a random sweep against the NumPy restatement (tests/wave_step_ref.py): two full wavefronts and a 2-lane tail, per-env tables;
-  4. RK45 against the GPU's own stg_solve_wave of the same tables (pinned by G22) plus the NumPy tail;
+  4. RK45 against the GPU's own stg_solve_wave of the same tables (pinned by G22) plus the NumPy tail -- against the C oracle's waveform
+     solve plus the same tail, two chained steps at N = 130: tests/test_gpu_wave_rk45_oracle.py;
   5. thermal: the same seed twice, and a partition of the envs over two contexts;
   6. autoreset with final_obs, skip_done, records against SoA, a bad table in one lane, the write footprint, the checked errors.
 Sizes are N = 1, 64, 65 and 130 (two full wavefronts plus two lanes)."""

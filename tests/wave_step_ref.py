@@ -1,4 +1,5 @@
-"""NumPy restatement of ONE env step with piecewise-linear current and field waveforms (stg_step_wave; RK4 and Euler, the thermal field of
+"""NumPy restatement of ONE env step with piecewise-linear current and field waveforms (stg_step_wave; RK4 and Euler -- RK45 with the
+C oracle's waveform solve handed in, see step --, the thermal field of
 tests/waveform_ref.py, STT / SOT / VCMA device classes under the reference torque model), vectorised over envs: the action parse, the solve (tests/waveform_ref.py), the energy of the pulse, the state
 update, observation, reward and flags.  Written from the definitions in include/spintorque_hip.h and the env-step arithmetic of the
 reference env (spin_torque_env.py:310-407, 474-520); tests/test_wave_step_host.py pins it against the C oracle's rectangular step (no
@@ -89,7 +90,7 @@ def observation(m, target, r, p, cfg, step_count, total_energy, J, T):
         return np.nan_to_num(np.stack(cols, axis=1).astype(np.float32), nan=0.0, posinf=1e6, neginf=-1e6)
 
 
-def step(state, actions, params, method="rk4", current=None, field=None, cfg=None, cls=None, done=None, dev_types=None, thermal=None):
+def step(state, actions, params, method="rk4", current=None, field=None, cfg=None, cls=None, done=None, dev_types=None, thermal=None, solve=None):
     """One env step of N envs (autoreset off).
     state: dict(m [N,3], target [N,3], total_energy [N], step_count [N]); actions [N,2] float32 / float64;
     params: one device-parameter dict, or a list of them with cls [N] (class index per env);
@@ -100,6 +101,10 @@ def step(state, actions, params, method="rk4", current=None, field=None, cfg=Non
     dev_types: the device type of each class ('stt_mram' | 'sot_mram' | 'vcma_mram'; None: all STT); it selects the resistance form.
     thermal = None or dict(oracle, seed, env_id0, rng_step [N], noise 'white' | 'ou', corr_time): the thermal field at cfg's temperature
     on the stream (seed, env_id0 + i, rng_step[i]), strength per class from oracle.thermal_strength (waveform_ref.thermal_field).
+    method 'rk45' takes its integrator from the caller: solve(m0 [n,3], T [n], p, J [n] or None, current, field, env [n]) for the envs
+    `env` of one class -> dict(success [n], n_steps [n] (accepted points excluding t0), m_final [n,3]); tests/wave_rk45_cases.py:
+    rk45_solver builds it on oracle.llgs_solve_wave, thermal stream included (`thermal` stays None).  The tail -- energy from
+    pulse_sq_integral, reward, flags, observation -- is the one below for every method.
     Returns dict(m, total_energy, step_count, obs [N,12] float32, reward [N] float64, terminated, truncated, energy, status, J, T, n_sub)."""
     cfg = dict(DEFAULT_CFG, **(cfg or {}))
     m0 = np.array(state["m"], dtype=float)
@@ -132,12 +137,16 @@ def step(state, actions, params, method="rk4", current=None, field=None, cfg=Non
             continue
         cur = None if current is None else (np.asarray(current[0])[run], np.asarray(current[1])[run])
         fld = None if field is None else (np.asarray(field[0])[run], np.asarray(field[1])[run])
-        res = waveform_ref.solve(m0[run], T[run], p, method, current=cur, J=J[run] if current is None else None, field=fld,
-                                 max_step=cfg["max_step"], temperature=cfg["temperature"], gamma=cfg["gamma"],
-                                 thermal=None if thermal is None else waveform_ref.thermal_field(
-                                     thermal["oracle"], p, dev_types[c], cfg["gamma"], cfg["temperature"], thermal["seed"],
-                                     thermal.get("env_id0", 0) + run, np.asarray(thermal["rng_step"])[run], thermal.get("noise", "white"),
-                                     thermal.get("corr_time", 1e-12)))
+        if method == "rk45":
+            assert solve is not None and thermal is None, "method 'rk45' integrates with the caller's solve (tests/wave_rk45_cases.py: rk45_solver)"
+            res = solve(m0[run], T[run], p, J[run] if current is None else None, cur, fld, run)
+        else:
+            res = waveform_ref.solve(m0[run], T[run], p, method, current=cur, J=J[run] if current is None else None, field=fld,
+                                     max_step=cfg["max_step"], temperature=cfg["temperature"], gamma=cfg["gamma"],
+                                     thermal=None if thermal is None else waveform_ref.thermal_field(
+                                         thermal["oracle"], p, dev_types[c], cfg["gamma"], cfg["temperature"], thermal["seed"],
+                                         thermal.get("env_id0", 0) + run, np.asarray(thermal["rng_step"])[run], thermal.get("noise", "white"),
+                                         thermal.get("corr_time", 1e-12)))
         success[run], n_sub[run] = res["success"], res["n_steps"]
         mf = res["m_final"]
         mf = mf / np.sqrt((mf[:, 0] * mf[:, 0] + mf[:, 1] * mf[:, 1]) + mf[:, 2] * mf[:, 2])[:, None]      # spin_torque_env.py:461-464
