@@ -680,13 +680,19 @@ static int step_outputs(const stg_ctx* ctx, StepArgs& a, float* obs, float* fina
     return STG_OK;
 }
 
+// the context-owned fields of a step launch's arguments: state, config, env ids, class table, counters
+static void step_context(const stg_ctx* ctx, StepArgs& a) {
+    a.s = ctx->s; a.c = cfg_view(ctx->cfg); a.env_id0 = ctx->env_id0;
+    a.ctab = ctx->ctab; a.cls = ctx->cls; a.ncls = ctx->ncls;
+    a.counters = ctx->counters;
+}
+
 // Enqueues one step launch.  `a` arrives with what the entry point decides (N = the launch's slots, K, out_every, autoreset, actions,
 // outputs, ids / n_state); the rest comes from the context and from the launch plan (stg_launch_plan.hpp).  ws: the workspace of an
 // id launch, nullptr for the full step, which uses the context's own buffers.
 static int enqueue_step(stg_ctx* ctx, StepArgs& a, int32_t act_f64, const IdsWorkspace* ws, hipStream_t st) {
-    a.s = ctx->s; a.c = cfg_view(ctx->cfg); a.env_id0 = ctx->env_id0;
-    a.ctab = ctx->ctab; a.cls = ctx->cls; a.ncls = ctx->ncls; a.ep = env_params_of(ctx);
-    a.counters = ctx->counters;
+    step_context(ctx, a);
+    a.ep = env_params_of(ctx);
     a.placement = ctx->placement + (size_t)(ctx->launch_seq % PLACEMENT_RING) * PLACEMENT_WORDS;
     ctx->launch_seq += 1;
     StepPlan p;
@@ -793,10 +799,8 @@ int stg_step_wave(stg_ctx* ctx, const void* actions, int32_t act_f64, int32_t au
     StepArgs& a = w.s;
     if (int rc = step_outputs(ctx, a, obs, final_obs, reward, reward_f64, energy, terminated, truncated, status)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    a.s = ctx->s; a.c = cfg_view(ctx->cfg); a.N = ctx->N; a.env_id0 = ctx->env_id0;
-    a.ctab = ctx->ctab; a.cls = ctx->cls; a.ncls = ctx->ncls;
-    a.actions = actions; a.K = 1; a.out_every = 1; a.autoreset = autoreset ? 1 : 0;
-    a.counters = ctx->counters;
+    step_context(ctx, a);
+    a.N = ctx->N; a.actions = actions; a.K = 1; a.out_every = 1; a.autoreset = autoreset ? 1 : 0;
     w.kj = kj; w.tj = tj; w.jk = jk; w.kh = kh; w.th = th; w.hk = hk;
     const bool rk45 = ctx->cfg.solver == STG_SOLVER_RK45;
     w.axis_z = (rk45 ? ctx->axis_z_llgs : ctx->axis_z) ? 1 : 0;
@@ -805,23 +809,33 @@ int stg_step_wave(stg_ctx* ctx, const void* actions, int32_t act_f64, int32_t au
     return STG_OK;
 }
 
-// The env-level drive of stg_step_shaped: everything is checked here, on the host, before the context is looked at -- a refused call
-// leaves the shape that was set in force.
-int stg_set_pulse_shape(stg_ctx* ctx, int32_t kj, const double* tau, const double* scale, int32_t kh, const double* th, const double* hk) {
-    if (kj != 0 && (kj < 2 || kj > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kj must be 0 or 2 ... STG_MAX_KNOTS");
-    if (kh != 0 && (kh < 2 || kh > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kh must be 0 or 2 ... STG_MAX_KNOTS");
-    if (kj != 0 && (!tau || !scale)) return fail(STG_E_INVALID, "tau/scale must not be NULL with kj > 0");
-    if (kh != 0 && (!th || !hk)) return fail(STG_E_INVALID, "th/hk must not be NULL with kh > 0");
-    for (int32_t j = 0; j < kj; ++j) {
-        if (!std::isfinite(tau[j]) || !std::isfinite(scale[j])) return fail(STG_E_INVALID, "tau/scale must be finite");
+// What stg_set_pulse_shape and stg_set_pulse_knots check alike.  Everything is checked on the host, before the context is looked at: a
+// refused call leaves what was set in force.  scale: the shape's amplitudes, nullptr for the knots, which have none of their own.
+static int check_tau(int32_t n, const double* tau, const double* scale) {
+    for (int32_t j = 0; j < n; ++j) {
+        if (!std::isfinite(tau[j]) || (scale && !std::isfinite(scale[j]))) return fail(STG_E_INVALID, scale ? "tau/scale must be finite" : "tau must be finite");
         if (tau[j] < 0.0 || tau[j] > 1.0) return fail(STG_E_INVALID, "tau is normalised time: every knot must lie in [0, 1]");
         if (j > 0 && !(tau[j] > tau[j - 1])) return fail(STG_E_INVALID, "tau must be strictly increasing");
     }
+    return STG_OK;
+}
+static int check_field_table(int32_t kh, const double* th, const double* hk) {
     for (int32_t j = 0; j < kh; ++j) {
         if (!std::isfinite(th[j]) || !std::isfinite(hk[3 * j]) || !std::isfinite(hk[3 * j + 1]) || !std::isfinite(hk[3 * j + 2]))
             return fail(STG_E_INVALID, "th/hk must be finite");
         if (j > 0 && !(th[j] > th[j - 1])) return fail(STG_E_INVALID, "th must be strictly increasing");
     }
+    return STG_OK;
+}
+
+// The env-level drive of stg_step_shaped.
+int stg_set_pulse_shape(stg_ctx* ctx, int32_t kj, const double* tau, const double* scale, int32_t kh, const double* th, const double* hk) {
+    if (kj != 0 && (kj < 2 || kj > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kj must be 0 or 2 ... STG_MAX_KNOTS");
+    if (kh != 0 && (kh < 2 || kh > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kh must be 0 or 2 ... STG_MAX_KNOTS");
+    if (kj != 0 && (!tau || !scale)) return fail(STG_E_INVALID, "tau/scale must not be NULL with kj > 0");
+    if (kh != 0 && (!th || !hk)) return fail(STG_E_INVALID, "th/hk must not be NULL with kh > 0");
+    if (int rc = check_tau(kj, tau, scale)) return rc;
+    if (int rc = check_field_table(kh, th, hk)) return rc;
     if (!ctx) return fail(STG_E_INVALID, "ctx is NULL");
     HIP_TRY(hipSetDevice(ctx->device));
     if (kj != 0 || kh != 0) {
@@ -839,75 +853,15 @@ int stg_set_pulse_shape(stg_ctx* ctx, int32_t kj, const double* tau, const doubl
     return STG_OK;
 }
 
-// what stg_step_shaped and stg_step_shaped_ids share: the checks that need no list, then the one kernel (stg_step_shaped.hip).  `a`
-// arrives with N (slots), K, out_every, autoreset, actions, ids / n_state and the outputs.  Identity order, so none of the context's
-// launch scratch is used and the placement ring is left alone.
-static int shaped_checks(const stg_ctx* ctx, const char* who) {
-    if (!ctx) return fail(STG_E_INVALID, "ctx is NULL");
-    if (!ctx->have_params || !ctx->have_state) return fail(STG_E_STATE, std::string("stg_set_params and stg_reset must precede ") + who);
-    if (ctx->per_env) return fail(STG_E_STATE, std::string(who) + " works on the class table (stg_set_params), not on per-env parameters");
-    if (ctx->cfg.torque_model == 1) return fail(STG_E_INVALID, std::string(who) + " implements the reference torque model (cfg.torque_model = 0)");
-    if (ctx->shape_kj == 0 && ctx->shape_kh == 0) return fail(STG_E_STATE, std::string("stg_set_pulse_shape must precede ") + who);
-    return STG_OK;
-}
-static int enqueue_shaped(stg_ctx* ctx, ShapedStepArgs& w, int32_t act_f64, hipStream_t st) {
-    StepArgs& a = w.s;
-    HIP_TRY(hipSetDevice(ctx->device));
-    a.s = ctx->s; a.c = cfg_view(ctx->cfg); a.env_id0 = ctx->env_id0;
-    a.ctab = ctx->ctab; a.cls = ctx->cls; a.ncls = ctx->ncls;
-    a.counters = ctx->counters;
-    w.kj = ctx->shape_kj; w.kh = ctx->shape_kh; w.shape = ctx->shape;
-    stg_step_shaped_launch(w, ctx->cfg.solver, thermal_flag(ctx->cfg), ctx->ncls > 1, act_f64, st);
-    HIP_TRY(hipGetLastError());
-    return STG_OK;
-}
-
-int stg_step_shaped(stg_ctx* ctx, int32_t K, const void* actions, int32_t act_f64, int32_t out_every, int32_t autoreset, float* obs,
-                    float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated, uint8_t* truncated,
-                    uint8_t* status, void* stream) {
-    if (int rc = shaped_checks(ctx, "stg_step_shaped")) return rc;
-    if (K < 1) return fail(STG_E_INVALID, "K must be >= 1");
-    if (!actions || !obs) return fail(STG_E_INVALID, "actions/obs must not be NULL");
-    ShapedStepArgs w{};
-    StepArgs& a = w.s;
-    if (int rc = step_outputs(ctx, a, obs, final_obs, reward, reward_f64, energy, terminated, truncated, status)) return rc;
-    a.N = ctx->N; a.actions = actions; a.K = K; a.out_every = out_every ? 1 : 0; a.autoreset = autoreset ? 1 : 0;
-    return enqueue_shaped(ctx, w, act_f64, (hipStream_t)stream);
-}
-
-int stg_step_shaped_ids(stg_ctx* ctx, int64_t M, const uint32_t* env_ids, const void* actions, int32_t act_f64, int32_t autoreset, float* obs,
-                        float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated, uint8_t* truncated,
-                        uint8_t* status, void* stream) {
-    if (int rc = shaped_checks(ctx, "stg_step_shaped_ids")) return rc;
-    if (M < 0 || M > 0xFFFFFFFFll) return fail(STG_E_INVALID, "M must be in [0, 2^32)");
-    if (!env_ids || !actions || !obs) return fail(STG_E_INVALID, "env_ids/actions/obs must not be NULL");
-    ShapedStepArgs w{};
-    StepArgs& a = w.s;
-    if (int rc = step_outputs(ctx, a, obs, final_obs, reward, reward_f64, energy, terminated, truncated, status)) return rc;
-    if (M == 0) return STG_OK;                         // an empty list: nothing to launch
-    a.N = M; a.ids = env_ids; a.n_state = ctx->N;
-    a.actions = actions; a.K = 1; a.out_every = 1; a.autoreset = autoreset ? 1 : 0;
-    return enqueue_shaped(ctx, w, act_f64, (hipStream_t)stream);
-}
-
-// The knot times and the field table of stg_step_knots: everything is checked here, on the host, before the context is looked at -- a
-// refused call leaves what was set in force.
+// The knot times and the field table of stg_step_knots.
 int stg_set_pulse_knots(stg_ctx* ctx, int32_t P, const double* tau, double s_limit, int32_t kh, const double* th, const double* hk) {
     if (P != 0 && (P < 2 || P > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "P must be 0 or 2 ... STG_MAX_KNOTS");
     if (kh != 0 && (kh < 2 || kh > STG_MAX_KNOTS)) return fail(STG_E_INVALID, "kh must be 0 or 2 ... STG_MAX_KNOTS");
     if (P != 0 && !tau) return fail(STG_E_INVALID, "tau must not be NULL with P > 0");
     if (P != 0 && kh != 0 && (!th || !hk)) return fail(STG_E_INVALID, "th/hk must not be NULL with kh > 0");
     if (P != 0 && !(std::isfinite(s_limit) && s_limit > 0.0)) return fail(STG_E_INVALID, "s_limit must be finite and positive");
-    for (int32_t j = 0; j < P; ++j) {
-        if (!std::isfinite(tau[j])) return fail(STG_E_INVALID, "tau must be finite");
-        if (tau[j] < 0.0 || tau[j] > 1.0) return fail(STG_E_INVALID, "tau is normalised time: every knot must lie in [0, 1]");
-        if (j > 0 && !(tau[j] > tau[j - 1])) return fail(STG_E_INVALID, "tau must be strictly increasing");
-    }
-    for (int32_t j = 0; P != 0 && j < kh; ++j) {
-        if (!std::isfinite(th[j]) || !std::isfinite(hk[3 * j]) || !std::isfinite(hk[3 * j + 1]) || !std::isfinite(hk[3 * j + 2]))
-            return fail(STG_E_INVALID, "th/hk must be finite");
-        if (j > 0 && !(th[j] > th[j - 1])) return fail(STG_E_INVALID, "th must be strictly increasing");
-    }
+    if (int rc = check_tau(P, tau, nullptr)) return rc;
+    if (int rc = check_field_table(P != 0 ? kh : 0, th, hk)) return rc;
     if (!ctx) return fail(STG_E_INVALID, "ctx is NULL");
     HIP_TRY(hipSetDevice(ctx->device));
     if (P == 0) {                                          // cleared: the step entries return STG_E_STATE until knots are set again
@@ -927,54 +881,95 @@ int stg_set_pulse_knots(stg_ctx* ctx, int32_t P, const double* tau, double s_lim
     return STG_OK;
 }
 
-// what stg_step_knots and stg_step_knots_ids share, as shaped_checks / enqueue_shaped above: the checks that need no list, then the one
-// kernel (stg_step_knots.hip)
-static int knots_checks(const stg_ctx* ctx, const char* who) {
+// The pulse-step entries -- stg_step_shaped / _ids and stg_step_knots / _ids -- are one host path over the argument block of their
+// policy (stg_wave.hpp; the one kernel: stg_step_pulse.hpp).  Identity order, so none of the context's launch scratch is used and the
+// placement ring is left alone.
+// what the context has staged for each of them, into a launch's arguments (false: nothing is set)
+static bool pulse_table(const stg_ctx* ctx, ShapedStepArgs& w) {
+    w.kj = ctx->shape_kj; w.kh = ctx->shape_kh; w.tab = ctx->shape;
+    return w.kj != 0 || w.kh != 0;
+}
+static bool pulse_table(const stg_ctx* ctx, KnotsStepArgs& w) {
+    w.kj = ctx->knots_P; w.kh = ctx->knots_kh; w.s_limit = ctx->knots_limit; w.tab = ctx->knots;
+    return w.kj != 0;
+}
+// the checks that need no list
+static int pulse_checks(const stg_ctx* ctx, const char* who, const char* setter, bool is_set) {
     if (!ctx) return fail(STG_E_INVALID, "ctx is NULL");
     if (!ctx->have_params || !ctx->have_state) return fail(STG_E_STATE, std::string("stg_set_params and stg_reset must precede ") + who);
     if (ctx->per_env) return fail(STG_E_STATE, std::string(who) + " works on the class table (stg_set_params), not on per-env parameters");
     if (ctx->cfg.torque_model == 1) return fail(STG_E_INVALID, std::string(who) + " implements the reference torque model (cfg.torque_model = 0)");
-    if (ctx->knots_P == 0) return fail(STG_E_STATE, std::string("stg_set_pulse_knots must precede ") + who);
+    if (!is_set) return fail(STG_E_STATE, std::string(setter) + " must precede " + who);
     return STG_OK;
 }
-static int enqueue_knots(stg_ctx* ctx, KnotsStepArgs& w, int32_t act_f64, hipStream_t st) {
-    StepArgs& a = w.s;
+extern "C++" {
+// `w` arrives with the staged table and, in w.s, N (slots), K, out_every, autoreset, actions, ids / n_state and the outputs
+template <class ARGS>
+static int enqueue_pulse(stg_ctx* ctx, ARGS& w, int32_t act_f64, hipStream_t st) {
     HIP_TRY(hipSetDevice(ctx->device));
-    a.s = ctx->s; a.c = cfg_view(ctx->cfg); a.env_id0 = ctx->env_id0;
-    a.ctab = ctx->ctab; a.cls = ctx->cls; a.ncls = ctx->ncls;
-    a.counters = ctx->counters;
-    w.P = ctx->knots_P; w.kh = ctx->knots_kh; w.s_limit = ctx->knots_limit; w.knots = ctx->knots;
-    stg_step_knots_launch(w, ctx->cfg.solver, thermal_flag(ctx->cfg), ctx->ncls > 1, act_f64, st);
+    step_context(ctx, w.s);
+    stg_step_pulse_launch(w, ctx->cfg.solver, thermal_flag(ctx->cfg), ctx->ncls > 1, act_f64, st);
     HIP_TRY(hipGetLastError());
     return STG_OK;
+}
+// the K form: all N envs, K steps
+template <class ARGS>
+static int pulse_step_many(stg_ctx* ctx, const char* who, const char* setter, int32_t K, const void* actions, int32_t act_f64, int32_t out_every,
+                           int32_t autoreset, float* obs, float* final_obs, float* reward, double* reward_f64, double* energy,
+                           uint8_t* terminated, uint8_t* truncated, uint8_t* status, void* stream) {
+    ARGS w{};
+    StepArgs& a = w.s;
+    if (int rc = pulse_checks(ctx, who, setter, ctx && pulse_table(ctx, w))) return rc;
+    if (K < 1) return fail(STG_E_INVALID, "K must be >= 1");
+    if (!actions || !obs) return fail(STG_E_INVALID, "actions/obs must not be NULL");
+    if (int rc = step_outputs(ctx, a, obs, final_obs, reward, reward_f64, energy, terminated, truncated, status)) return rc;
+    a.N = ctx->N; a.actions = actions; a.K = K; a.out_every = out_every ? 1 : 0; a.autoreset = autoreset ? 1 : 0;
+    return enqueue_pulse(ctx, w, act_f64, (hipStream_t)stream);
+}
+// the id form: one step of the M envs env_ids
+template <class ARGS>
+static int pulse_step_ids(stg_ctx* ctx, const char* who, const char* setter, int64_t M, const uint32_t* env_ids, const void* actions,
+                          int32_t act_f64, int32_t autoreset, float* obs, float* final_obs, float* reward, double* reward_f64, double* energy,
+                          uint8_t* terminated, uint8_t* truncated, uint8_t* status, void* stream) {
+    ARGS w{};
+    StepArgs& a = w.s;
+    if (int rc = pulse_checks(ctx, who, setter, ctx && pulse_table(ctx, w))) return rc;
+    if (M < 0 || M > 0xFFFFFFFFll) return fail(STG_E_INVALID, "M must be in [0, 2^32)");
+    if (!env_ids || !actions || !obs) return fail(STG_E_INVALID, "env_ids/actions/obs must not be NULL");
+    if (int rc = step_outputs(ctx, a, obs, final_obs, reward, reward_f64, energy, terminated, truncated, status)) return rc;
+    if (M == 0) return STG_OK;                         // an empty list: nothing to launch
+    a.N = M; a.ids = env_ids; a.n_state = ctx->N;
+    a.actions = actions; a.K = 1; a.out_every = 1; a.autoreset = autoreset ? 1 : 0;
+    return enqueue_pulse(ctx, w, act_f64, (hipStream_t)stream);
+}
+}
+
+int stg_step_shaped(stg_ctx* ctx, int32_t K, const void* actions, int32_t act_f64, int32_t out_every, int32_t autoreset, float* obs,
+                    float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated, uint8_t* truncated,
+                    uint8_t* status, void* stream) {
+    return pulse_step_many<ShapedStepArgs>(ctx, "stg_step_shaped", "stg_set_pulse_shape", K, actions, act_f64, out_every, autoreset, obs,
+                                           final_obs, reward, reward_f64, energy, terminated, truncated, status, stream);
+}
+
+int stg_step_shaped_ids(stg_ctx* ctx, int64_t M, const uint32_t* env_ids, const void* actions, int32_t act_f64, int32_t autoreset, float* obs,
+                        float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated, uint8_t* truncated,
+                        uint8_t* status, void* stream) {
+    return pulse_step_ids<ShapedStepArgs>(ctx, "stg_step_shaped_ids", "stg_set_pulse_shape", M, env_ids, actions, act_f64, autoreset, obs,
+                                          final_obs, reward, reward_f64, energy, terminated, truncated, status, stream);
 }
 
 int stg_step_knots(stg_ctx* ctx, int32_t K, const void* actions, int32_t act_f64, int32_t out_every, int32_t autoreset, float* obs,
                    float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated, uint8_t* truncated,
                    uint8_t* status, void* stream) {
-    if (int rc = knots_checks(ctx, "stg_step_knots")) return rc;
-    if (K < 1) return fail(STG_E_INVALID, "K must be >= 1");
-    if (!actions || !obs) return fail(STG_E_INVALID, "actions/obs must not be NULL");
-    KnotsStepArgs w{};
-    StepArgs& a = w.s;
-    if (int rc = step_outputs(ctx, a, obs, final_obs, reward, reward_f64, energy, terminated, truncated, status)) return rc;
-    a.N = ctx->N; a.actions = actions; a.K = K; a.out_every = out_every ? 1 : 0; a.autoreset = autoreset ? 1 : 0;
-    return enqueue_knots(ctx, w, act_f64, (hipStream_t)stream);
+    return pulse_step_many<KnotsStepArgs>(ctx, "stg_step_knots", "stg_set_pulse_knots", K, actions, act_f64, out_every, autoreset, obs,
+                                          final_obs, reward, reward_f64, energy, terminated, truncated, status, stream);
 }
 
 int stg_step_knots_ids(stg_ctx* ctx, int64_t M, const uint32_t* env_ids, const void* actions, int32_t act_f64, int32_t autoreset, float* obs,
                        float* final_obs, float* reward, double* reward_f64, double* energy, uint8_t* terminated, uint8_t* truncated,
                        uint8_t* status, void* stream) {
-    if (int rc = knots_checks(ctx, "stg_step_knots_ids")) return rc;
-    if (M < 0 || M > 0xFFFFFFFFll) return fail(STG_E_INVALID, "M must be in [0, 2^32)");
-    if (!env_ids || !actions || !obs) return fail(STG_E_INVALID, "env_ids/actions/obs must not be NULL");
-    KnotsStepArgs w{};
-    StepArgs& a = w.s;
-    if (int rc = step_outputs(ctx, a, obs, final_obs, reward, reward_f64, energy, terminated, truncated, status)) return rc;
-    if (M == 0) return STG_OK;                         // an empty list: nothing to launch
-    a.N = M; a.ids = env_ids; a.n_state = ctx->N;
-    a.actions = actions; a.K = 1; a.out_every = 1; a.autoreset = autoreset ? 1 : 0;
-    return enqueue_knots(ctx, w, act_f64, (hipStream_t)stream);
+    return pulse_step_ids<KnotsStepArgs>(ctx, "stg_step_knots_ids", "stg_set_pulse_knots", M, env_ids, actions, act_f64, autoreset, obs,
+                                         final_obs, reward, reward_f64, energy, terminated, truncated, status, stream);
 }
 
 extern "C++" {

@@ -4,11 +4,13 @@
 // The solvers of the reference take current_func(t) and field_func(t); a Python callable cannot run in a kernel, a table of knots can.
 // This header holds the waveform variants of the functions of stg_physics.hpp that take J as a per-solve constant (simple_solve, the
 // llgs_lane_* family); the functions in which the drive enters as an argument -- llgs_rhs, validation, the RK45 controller pieces, the
-// recorder, the normal stream -- are reused as they are.  Only stg_solve_wave.hip, stg_step_wave.hip, stg_step_shaped.hip,
-// stg_step_knots.hip and the switching trial kernel (stg_switch.hpp: stg_switch_rk4.hip / _euler.hip / _rk45.hip) instantiate anything in
-// here: the step kernels, stg_solve_kernel and the array kernels do not see this file's device code
+// recorder, the normal stream -- are reused as they are.  Only stg_solve_wave.hip, stg_step_wave.hip, the pulse-step kernel
+// (stg_step_pulse.hpp: stg_step_shaped.hip / stg_step_knots.hip) and the switching trial kernel (stg_switch.hpp: stg_switch_rk4.hip /
+// _euler.hip / _rk45.hip) instantiate anything in here: the step kernels, stg_solve_kernel and the array kernels do not see this file's
+// device code
 // (profiles/waveform_existing_kernels_unchanged.txt, profiles/step_wave_existing_kernels_unchanged.txt,
 // profiles/step_shaped_existing_kernels_unchanged.txt, profiles/step_knots_existing_kernels_unchanged.txt,
+// profiles/step_pulse_existing_kernels_unchanged.txt,
 // profiles/switch_stats_wave_existing_kernels_unchanged.txt, profiles/switch_family_existing_kernels_unchanged.txt).
 //
 // Waveform semantics (the C header states them for callers; physics.PiecewiseLinear and tests/waveform_ref.py use the same arithmetic):
@@ -51,24 +53,24 @@ constexpr int STG_SHAPE_DOUBLES = 6 * STG_MAX_KNOTS;      // tau, scale, th [STG
 struct ShapedStepArgs {
     StepArgs s;
     int32_t kj, kh;               // knot counts; 0: rectangular J while t <= T / zero field (not both 0)
-    const double* shape;          // [STG_SHAPE_DOUBLES] on the device (stg_set_pulse_shape)
+    const double* tab;            // [STG_SHAPE_DOUBLES] on the device (stg_set_pulse_shape)
 };
 
-// defined in stg_step_shaped.hip: enqueues the one kernel of a shaped step launch (s.ids != nullptr: the id form)
-void stg_step_shaped_launch(const ShapedStepArgs& a, int solver, bool thermal, bool multi, int act_f64, hipStream_t st);
 
 // K env steps whose actions carry the pulse's knot amplitudes (stg_step_knots, stg_step_knots_ids): the step launch's arguments plus the
 // knot times and the field table, which are the same for every env and every step (stg_set_pulse_knots)
 constexpr int STG_KNOTS_DOUBLES = 5 * STG_MAX_KNOTS;      // tau, th [STG_MAX_KNOTS] each, hk [STG_MAX_KNOTS][3]
 struct KnotsStepArgs {
     StepArgs s;
-    int32_t P, kh;                // amplitude knots (2 ... STG_MAX_KNOTS); field knots, 0: zero field
+    int32_t kj, kh;               // amplitude knots (2 ... STG_MAX_KNOTS); field knots, 0: zero field
     double s_limit;               // the clamp of an amplitude
-    const double* knots;          // [STG_KNOTS_DOUBLES] on the device (stg_set_pulse_knots)
+    const double* tab;            // [STG_KNOTS_DOUBLES] on the device (stg_set_pulse_knots)
 };
 
-// defined in stg_step_knots.hip: enqueues the one kernel of an agent-shaped step launch (s.ids != nullptr: the id form)
-void stg_step_knots_launch(const KnotsStepArgs& a, int solver, bool thermal, bool multi, int act_f64, hipStream_t st);
+// defined in stg_step_shaped.hip and stg_step_knots.hip: enqueues the pulse-step kernel (stg_step_pulse.hpp) of a shaped or an
+// agent-shaped step launch (s.ids != nullptr: the id form)
+void stg_step_pulse_launch(const ShapedStepArgs& a, int solver, bool thermal, bool multi, int act_f64, hipStream_t st);
+void stg_step_pulse_launch(const KnotsStepArgs& a, int solver, bool thermal, bool multi, int act_f64, hipStream_t st);
 
 namespace stg {
 

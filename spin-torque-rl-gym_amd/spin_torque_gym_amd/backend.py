@@ -138,6 +138,21 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _pulse_knots(n: int, rows, field_knots):
+    """What set_pulse_shape and set_pulse_knots marshal alike: `rows` ([n] each; not looked at with n = 0) and field_knots = (times [K],
+    values [K,3]) or None, as contiguous float64 host arrays of exactly those shapes.  Returns (K, arrays, pointers) over rows + (times,
+    values), None for what is absent; the arrays must outlive the call."""
+    def host(x, shape_):
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+        if x.shape != shape_:
+            raise ValueError(f"expected shape {shape_}, got {x.shape}")
+        return x
+    kh = 0 if field_knots is None else int(len(field_knots[0]))
+    arrays = [host(r, (n,)) if n else None for r in rows]
+    arrays += [host(field_knots[0], (kh,)), host(field_knots[1], (kh, 3))] if kh else [None, None]
+    return kh, arrays, [None if x is None else C.c_void_p(x.ctypes.data) for x in arrays]
+
+
 def alloc_final_obs(lead, m: int, device, layout: str):
     """Terminal-observation buffer of an auto-resetting step, shape `lead` + per-step: (what the kernel writes, its [.., 12, m] view).
     'records': env-major [.., m, 12] like the records (one 48-byte block per env) and the transposed view; else [.., 12, m] itself."""
@@ -329,20 +344,9 @@ class HipBackend:
         over normalised time (times tau in [0, 1], values = factors on the action's current density) or None (the rectangular pulse);
         field_knots = (times [K] in seconds, values [K,3] in A/m) or None (zero field).  Both None clears the shape.  The library copies
         the knots; called once per context, not per step."""
-        def host(x, shape_):
-            x = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
-            if x.shape != shape_:
-                raise ValueError(f"expected shape {shape_}, got {x.shape}")
-            return x
         kj = 0 if shape is None else int(len(shape.times))
-        kh = 0 if field_knots is None else int(len(field_knots[0]))
-        tau = scale = th = hk = None
-        if kj:
-            tau, scale = host(shape.times, (kj,)), host(shape.values, (kj,))
-        if kh:
-            th, hk = host(field_knots[0], (kh,)), host(field_knots[1], (kh, 3))
-        hp = lambda x: None if x is None else C.c_void_p(x.ctypes.data)               # noqa: E731
-        _lib.check(self.lib.stg_set_pulse_shape(self._ctx, kj, hp(tau), hp(scale), kh, hp(th), hp(hk)))
+        kh, keep, (tau, scale, th, hk) = _pulse_knots(kj, (shape.times, shape.values) if kj else (None, None), field_knots)
+        _lib.check(self.lib.stg_set_pulse_shape(self._ctx, kj, tau, scale, kh, th, hk))
 
     def step_shaped_many(self, actions, out_every=True, autoreset=False):
         """step_many under the shape of set_pulse_shape (stg_step_shaped): K env steps in one launch, the drive of each env at each step
@@ -353,19 +357,9 @@ class HipBackend:
         """The knot times of step_knots_many / step_knots_ids (stg_set_pulse_knots): tau = [P] normalised knot times in [0, 1], strictly
         increasing; amplitude_limit = the clamp of an action's amplitudes; field_knots = (times [K] in seconds, values [K,3] in A/m) or
         None (zero field).  tau = None clears the knots.  The library copies them; called once per context, not per step."""
-        def host(x, shape_):
-            x = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
-            if x.shape != shape_:
-                raise ValueError(f"expected shape {shape_}, got {x.shape}")
-            return x
         p = 0 if tau is None else int(len(tau))
-        kh = 0 if field_knots is None else int(len(field_knots[0]))
-        tau = host(tau, (p,)) if p else None
-        th = hk = None
-        if kh:
-            th, hk = host(field_knots[0], (kh,)), host(field_knots[1], (kh, 3))
-        hp = lambda x: None if x is None else C.c_void_p(x.ctypes.data)               # noqa: E731
-        _lib.check(self.lib.stg_set_pulse_knots(self._ctx, p, hp(tau), float(amplitude_limit), kh, hp(th), hp(hk)))
+        kh, keep, (tau, th, hk) = _pulse_knots(p, (tau,), field_knots)
+        _lib.check(self.lib.stg_set_pulse_knots(self._ctx, p, tau, float(amplitude_limit), kh, th, hk))
         self.n_knots = p
 
     def step_knots_many(self, actions, out_every=True, autoreset=False):
@@ -431,21 +425,22 @@ class HipBackend:
         workspace: from ids_workspace(M' >= M), or None for a new one.  stream: a torch.cuda.Stream to launch on -- it first waits for
         the current stream (which produced the inputs) and the new arrays belong to it -- or None for the current stream.  Launches
         on different streams may overlap only under the header's concurrency contract (own workspace, pair-closed disjoint id sets)."""
-        return self._ids(False, actions, env_ids, autoreset, workspace, out, stream)
+        return self._ids(None, actions, env_ids, autoreset, workspace, out, stream)
 
     def step_shaped_ids(self, actions, env_ids, autoreset=False, out=None, stream=None):
         """step_ids under the shape of set_pulse_shape (stg_step_shaped_ids): one shaped env step of the envs env_ids only.  Arguments,
         outputs (alloc_ids_outputs) and the stream rules are step_ids's; there is no workspace (identity order: nothing is staged)."""
-        return self._ids(True, actions, env_ids, autoreset, None, out, stream)
+        return self._ids(self.lib.stg_step_shaped_ids, actions, env_ids, autoreset, None, out, stream)
 
     def step_knots_ids(self, actions, env_ids, autoreset=False, out=None, stream=None):
         """step_ids with actions [2+P, M] that carry the pulse's knot amplitudes (stg_step_knots_ids).  Arguments, outputs
         (alloc_ids_outputs) and the stream rules are step_shaped_ids's."""
-        return self._ids(True, actions, env_ids, autoreset, None, out, stream, entry=self.lib.stg_step_knots_ids, rows=2 + self.n_knots)
+        return self._ids(self.lib.stg_step_knots_ids, actions, env_ids, autoreset, None, out, stream, rows=2 + self.n_knots)
 
-    def _ids(self, shaped, actions, env_ids, autoreset, workspace, out, stream, entry=None, rows=2):
-        """What step_ids, step_shaped_ids and step_knots_ids share: inputs and outputs on the launch's stream, the call.  shaped: an
-        entry without a workspace (stg_step_shaped_ids, or `entry`, which has its signature); rows: the rows of an action block."""
+    def _ids(self, entry, actions, env_ids, autoreset, workspace, out, stream, rows=2):
+        """What step_ids, step_shaped_ids and step_knots_ids share: inputs and outputs on the launch's stream, the call.  entry: a
+        pulse-step entry, which takes no workspace (stg_step_shaped_ids' signature), or None for stg_step_ids; rows: the rows of an
+        action block."""
         cur = torch.cuda.current_stream(self.device)
         s = cur if stream is None else stream
         if s is not cur:
@@ -459,14 +454,14 @@ class HipBackend:
             if s is not cur:
                 a.record_stream(s)
                 ids.record_stream(s)
-            ws = None if shaped else (self.ids_workspace(m) if workspace is None else workspace)
+            ws = None if entry else (self.ids_workspace(m) if workspace is None else workspace)
             if out is None:
                 out = self.alloc_ids_outputs(m, autoreset)
             outs = self._out_ptrs(out["buf"], out["final_buf"] if autoreset else None, out["reward"], out["reward64"], out["energy"],
                                   out["terminated"], out["truncated"], out["status"])
             head = (self._ctx, m, _ptr(ids), _ptr(a), int(f64), int(bool(autoreset)))
-            if shaped:
-                _lib.check((entry or self.lib.stg_step_shaped_ids)(*head, *outs, C.c_void_p(s.cuda_stream)))
+            if entry:
+                _lib.check(entry(*head, *outs, C.c_void_p(s.cuda_stream)))
             else:
                 _lib.check(self.lib.stg_step_ids(*head, _ptr(ws), *outs, C.c_void_p(s.cuda_stream)))
         out["_keep"] = (a, ids, ws)           # inputs stay alive while the launch may still read them

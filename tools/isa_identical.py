@@ -2,7 +2,11 @@
 """Are the kernels of two hipcc -S listings the same machine code?  Every function (`_Z...:` up to its .Lfunc_end) of `before` is
 compared as text with the function of the same name in `after`: comments stripped, basic-block labels .LBB<f>_<n> renumbered to
 .LBB_<n> (the function index moves when a translation unit gains or loses a function).  Functions only `after` has are listed.
-usage: python tools/isa_identical.py <before.s> <after.s> [name-substring ...]     (exit status 1 if a body differs or is missing)"""
+--rename OLD=NEW (repeatable) replaces the substring OLD by NEW in the names and bodies of `before`, so that a body can be held against
+the differently named one that took its place: a kernel that became an instantiation of a merged template.  Names are mangled, so the
+length prefix belongs to the substring: --rename 22stg_step_shaped_kernel=21stg_step_pulse_kernel.
+usage: python tools/isa_identical.py [--rename OLD=NEW ...] <before.s> <after.s> [name-substring ...]
+(exit status 1 if a body differs or is missing)"""
 import re
 import sys
 
@@ -26,7 +30,18 @@ def functions(path):
 
 
 def main():
+    renames = []
+    while len(sys.argv) > 2 and sys.argv[1] == "--rename":
+        renames.append(sys.argv[2].split("=", 1))
+        del sys.argv[1:3]
+
+    def renamed(t):
+        for old, new in renames:
+            t = t.replace(old, new)
+        return t
+
     before, after, keys = functions(sys.argv[1]), functions(sys.argv[2]), sys.argv[3:]
+    before = {renamed(k): [renamed(t) for t in v] for k, v in before.items()}
     pick = lambda d: {k: v for k, v in d.items() if not keys or any(s in k for s in keys)}      # noqa: E731
     before, after = pick(before), pick(after)
     same = diff = missing = lines = 0
