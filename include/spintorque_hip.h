@@ -412,6 +412,48 @@ int stg_switch_stats(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t
                      const double* target, double threshold, int32_t n_bins, unsigned long long* n_switched,
                      unsigned long long* n_failed, unsigned long long* hist, void* stream);
 
+/* Write - verify - write switching statistics, reduced on the device: the write-error rate after at most A attempts and the number
+ * of pulses that costs, which is how an MRAM macro writes -- after the pulse the bit is read, and only a bit that failed gets another,
+ * usually stronger or longer, pulse.  Like stg_switch_stats it holds no per-trial memory (A chained stg_solve launches with a host-side
+ * mask cost 69 bytes per trial), so the regime where the error after a retry is a product of two small numbers is bounded by time.
+ *
+ * Trial: trial r (trial0 <= r < trial0 + R) of condition g is up to A attempts.  Attempt a is the chain of P rectangular phases of
+ * stg_switch_stats with (J[a][p][g], T[a][p][g]); J, T double[A][P][G], condition index fastest.  The first attempt starts from the
+ * condition's m0, every later attempt from the m the attempt before left behind.  1 <= A <= STG_MAX_VERIFY_ATTEMPTS.
+ * Stream rule: phase p of attempt a IS the solve of stg_solve with (m, J[a][p][g], T[a][p][g]) at Philox counter word
+ * env_step + a * P + p modulo 2^32 on the stream of env id env_id0 + g * trial_stride + r, with the context's solver, thermal field and
+ * class row (cond_cls as in stg_switch_stats).  A phase with T == 0.0 exactly is skipped (m passes through; it is not a failed solve).
+ * Verify: after every attempt the trial is classified by stg_switch_stats' arithmetic, IEEE fp64 without FMA contraction:
+ *   proj = ((m.x * target[0][g]) + (m.y * target[1][g])) + (m.z * target[2][g])
+ *   switched iff proj > threshold                                   (a NaN proj is not switched)
+ * End of a trial: it ends at attempt a when it is classified switched after attempt a, or when a phase of attempt a fails, or when
+ * a == A - 1.  A failed phase (success = 0 in stg_solve's terms) ends its attempt with the m that solve hands back, adds one to
+ * n_failed[g], and the trial is classified like any other.
+ * Outputs, all ADDED to (the caller zeroes them):
+ *   n_ended_at[A][G]      trials whose last attempt was a
+ *   n_switched_at[A][G]   those of them classified switched
+ *   n_failed[G]
+ *   hist[G][n_bins]       of the final proj, with stg_switch_stats' bin rule; NULL iff n_bins == 0
+ * Hence sum_a n_ended_at[a][g] = R; the trials that ran attempt a number R - sum_{b<a} n_ended_at[b][g]; the write-error rate after
+ * a + 1 attempts is 1 - sum_{b<=a} n_switched_at[b][g] / R.  No other memory is touched, and nothing beyond those A * G, A * G, G and
+ * G * n_bins elements.  Chunks of a trial range (trial0) and ranks of a sharded job add up to one call's integers.
+ * A == 1: n_switched_at[0], n_failed and hist are those of stg_switch_stats on the same arguments, integer for integer.
+ * Launch rule: one 64-lane wavefront per workgroup works on one condition; W wavefronts per condition,
+ * W = min(ceil(R / 64), max(1, cap / G)), cap = max_waves if max_waves > 0, else STG_SWITCH_STATS_WAVES.  Lane l of wavefront w runs its
+ * own list of trials, w * 64 + l + k * 64 * W (k = 0, 1, ...), moving on to the next one as soon as a trial ends, so a wavefront stays
+ * full until its lanes run out of trials; the counts never depend on W.  max_waves lets a caller sharing a device bound the launch's width.
+ * Enqueues kernels only (no allocation, no synchronisation).  Rectangular phases only: piecewise-linear tables, first-passage times
+ * and device populations under verify are follow-ups.  Per-env parameters (stg_set_params_per_env) return STG_E_STATE.
+ * STG_E_INVALID with nothing launched and nothing written: everything stg_switch_stats lists (n_switched_at, n_ended_at in the place
+ * of n_switched), A outside 1 ... STG_MAX_VERIFY_ATTEMPTS, max_waves < 0 or 0 < max_waves < G.  env_step + A * P is formed modulo
+ * 2^32, as in the siblings: a counter word that wraps is not an error.  R == 0 is valid and does nothing. */
+#define STG_MAX_VERIFY_ATTEMPTS 8
+int stg_switch_verify(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t A, int32_t P,
+                      const double* m0, const double* J, const double* T, const uint8_t* cond_cls, uint32_t env_step,
+                      const double* target, double threshold, int32_t n_bins, int32_t max_waves,
+                      unsigned long long* n_switched_at, unsigned long long* n_ended_at, unsigned long long* n_failed,
+                      unsigned long long* hist, void* stream);
+
 /* stg_switch_stats with ONE phase of the trial, `wave_phase`, driven by piecewise-linear tables: a shaped current pulse (rise time,
  * pre-emphasis, bipolar tails) and / or an applied field, per condition.  Like stg_switch_stats it holds no per-trial memory: a
  * condition's tables are read once per wavefront, whatever R is.

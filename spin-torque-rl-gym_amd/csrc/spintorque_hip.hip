@@ -14,6 +14,7 @@
 #include "stg_kernels.hpp"
 #include "stg_wave.hpp"
 #include "stg_switch.hpp"
+#include "stg_switch_verify.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -1146,6 +1147,28 @@ int stg_switch_times(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t
     if (int rc = switch_wave_args("watch_phase", false, watch_phase, P, kj, tj, jk, kh, th, hk, x.w)) return rc;
     if (int rc = switch_passage_args(n_tbins, n_crossed, n_returned, t_hist, false, x)) return rc;
     return switch_launch(ctx, x, true, stream);
+}
+
+// write - verify - write: the kernel of stg_switch_verify.hpp on stg_switch_stats' argument block, with the attempts in front of the phases
+int stg_switch_verify(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t A, int32_t P, const double* m0,
+                      const double* J, const double* T, const uint8_t* cond_cls, uint32_t env_step, const double* target, double threshold,
+                      int32_t n_bins, int32_t max_waves, unsigned long long* n_switched_at, unsigned long long* n_ended_at,
+                      unsigned long long* n_failed, unsigned long long* hist, void* stream) {
+    SwitchVerifyArgs x{};
+    if (int rc = switch_stats_args(ctx, "stg_switch_verify", G, R, trial0, trial_stride, P, m0, J, T, cond_cls, env_step, target, threshold, n_bins,
+                                   n_switched_at, n_failed, hist, true, x.s)) return rc;
+    if (!n_ended_at) return fail(STG_E_INVALID, "n_ended_at must not be NULL");
+    if (A < 1 || A > STG_MAX_VERIFY_ATTEMPTS) return fail(STG_E_INVALID, "A must be in 1 ... STG_MAX_VERIFY_ATTEMPTS");
+    if (max_waves < 0 || (max_waves > 0 && max_waves < G)) return fail(STG_E_INVALID, "max_waves must be 0 (the library's rule) or >= G");
+    x.A = A; x.n_ended_at = n_ended_at;
+    if (R == 0) return STG_OK;
+    x.s.L = 0;                                                                     // (the lockstep kernel's; every lane walks its own list here)
+    x.s.waves_per_cond = switch_verify_plan(G, R, max_waves);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!stg_switch_verify_launch(x, ctx->cfg.solver, thermal_flag(ctx->cfg), ctx->ncls > 1 && cond_cls != nullptr, (hipStream_t)stream))
+        return fail(STG_E_INVALID, "stg_switch_verify has no kernel for this solver");
+    HIP_TRY(hipGetLastError());
+    return STG_OK;
 }
 
 // what stg_switch_population and its diagnostic twin share: the checks of the draw's scalars

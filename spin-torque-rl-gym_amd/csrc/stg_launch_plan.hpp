@@ -59,6 +59,15 @@ static inline void switch_stats_plan(int32_t G, int64_t R, int64_t* L, int32_t* 
     *waves_per_cond = (int32_t)((w1 + *L - 1) / *L);
 }
 
+// stg_switch_verify (kernel: stg_switch_verify.hpp).  Launch rule: W = min(ceil(R / 64), max(1, cap / G)) wavefronts per condition, cap =
+// max_waves if the caller gave one (> 0), else STG_SWITCH_STATS_WAVES; lane l of wavefront w runs trials w * 64 + l + k * 64 * W.
+static inline int32_t switch_verify_plan(int32_t G, int64_t R, int32_t max_waves) {
+    const int64_t w1 = (R + 63) / 64;
+    int64_t cap = (max_waves > 0 ? (int64_t)max_waves : (int64_t)STG_SWITCH_STATS_WAVES) / (int64_t)G;
+    if (cap < 1) cap = 1;
+    return (int32_t)(w1 < cap ? w1 : cap);
+}
+
 struct StepPlan {
     bool sort;                // the plan kernel runs and the step launch follows its permutation (else: identity schedule)
     bool by_kind, regroup, skip_done;   // ... the plan kernel's arguments (read only with `sort`)

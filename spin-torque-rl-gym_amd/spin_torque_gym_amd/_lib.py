@@ -17,6 +17,7 @@ STG_MAX_KNOTS = 32       # knots of one piecewise-linear waveform (stg_solve_wav
 STG_MAX_PHASES = 4       # phases of one trial of stg_switch_stats
 STG_MAX_BINS = 64        # histogram bins of stg_switch_stats
 STG_MAX_TBINS = 1024     # time bins of stg_switch_times
+STG_MAX_VERIFY_ATTEMPTS = 8  # attempts of one trial of stg_switch_verify
 SWITCH_STATS_WAVES = 12288  # STG_SWITCH_STATS_WAVES: above this many wavefronts in a launch, the lanes of stg_switch_stats loop over trials
 ABI_VERSION = 5         # STG_ABI_VERSION of include/spintorque_hip.h this binding was written against
 STG_NPARAM = 30          # double-valued fields of stg_device_params, in declaration order
@@ -86,6 +87,8 @@ SYMBOLS = {
                                  _VP, _VP, _VP, _VP]),
     "stg_switch_stats": (C.c_int, [_VP, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _VP, _VP, _VP, _VP, C.c_uint32, _VP, C.c_double,
                                    C.c_int32, _VP, _VP, _VP, _VP]),
+    "stg_switch_verify": (C.c_int, [_VP, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_uint32, _VP,
+                                    C.c_double, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP]),
     "stg_switch_stats_wave": (C.c_int, [_VP, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP,
                                         C.c_int32, _VP, _VP, _VP, C.c_uint32, _VP, C.c_double, C.c_int32, _VP, _VP, _VP, _VP]),
     "stg_switch_times": (C.c_int, [_VP, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP,

@@ -581,6 +581,35 @@ class HipBackend:
                                              self._stream()))
         return out
 
+    def switch_verify(self, m0, J, T, target, n_trials, trial0=0, trial_stride=None, cond_cls=None, env_step=0, threshold=0.0,
+                      n_bins=0, max_waves=0, out=None):
+        """Write - verify - write counts reduced on the device (stg_switch_verify): a trial is up to A attempts of P rectangular phases,
+        J, T [A,P,G] ([A,G]: one phase per attempt); after every attempt it is classified as in switch_stats, and it ends when it has
+        switched, when a solve failed or after attempt A - 1; the next attempt starts from the m the one before left behind.  Phase p
+        of attempt a of trial r of condition g is problem g * trial_stride + r of `solve` at env_step + a * P + p.  The other arguments
+        are those of switch_stats; max_waves > 0 bounds the launch's wavefronts (>= G; the counts do not depend on it).  Returns
+        (n_switched_at [A,G], n_ended_at [A,G], n_failed [G], hist [G,n_bins] or None), int64 on the device; the call ADDS to them:
+        `out` = the tuple of an earlier call accumulates a chunked trial range, None starts from zero.  Enqueues only."""
+        m0 = self._dev(m0, torch.float64)
+        g = int(m0.shape[-1])
+        m0 = self._dev(m0, torch.float64, (3, g))
+        J, T = (x[:, None, :] if x.dim() == 2 else x for x in (self._dev(J, torch.float64), self._dev(T, torch.float64)))
+        a, p = int(T.shape[0]), int(T.shape[1])
+        J, T = self._dev(J, torch.float64, (a, p, g)), self._dev(T, torch.float64, (a, p, g))
+        target = self._dev(target, torch.float64, (3, g))
+        cond_cls = self._dev(cond_cls, torch.uint8, (g,))
+        r, t0 = int(n_trials), int(trial0)
+        stride = t0 + r if trial_stride is None else int(trial_stride)
+        if out is None:
+            zeros = lambda *shape: torch.zeros(shape, dtype=torch.int64, device=self.device)      # noqa: E731
+            out = (zeros(a, g), zeros(a, g), zeros(g), zeros(g, int(n_bins)) if n_bins > 0 else None)
+        n_sw, n_end, n_failed, hist = out
+        self._keep = (m0, J, T, target, cond_cls)
+        _lib.check(self.lib.stg_switch_verify(self._ctx, g, r, t0, stride, a, p, _ptr(m0), _ptr(J), _ptr(T), _ptr(cond_cls), int(env_step),
+                                              _ptr(target), float(threshold), int(n_bins), int(max_waves), _ptr(n_sw), _ptr(n_end),
+                                              _ptr(n_failed), _ptr(hist), self._stream()))
+        return out
+
     def switch_stats_wave(self, m0, J, T, target, n_trials, wave, wave_phase=0, trial0=0, trial_stride=None, cond_cls=None, env_step=0,
                           threshold=0.0, n_bins=0, out=None):
         """switch_stats with phase `wave_phase` driven by piecewise-linear tables (stg_switch_stats_wave): wave = dict(current=(tj [K,G],

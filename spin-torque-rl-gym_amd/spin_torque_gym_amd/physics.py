@@ -429,6 +429,95 @@ class _GpuSolverBase:
                 res.update({"dev_switched": dev_sw, "dev_trials": dev_trials, "dev_p_switch": dev_sw / dev_trials})
         return res
 
+    def write_verify_statistics(self, m_initial, current, duration, device_params, n_trials: int, *, relax=0.0,
+                                target=(0.0, 0.0, -1.0), threshold: float = 0.0, n_bins: int = 0, temperature: float = 300.0,
+                                device_type="stt_mram", class_index=None, env_step: int = 0, trial_offset: int = 0, trial_stride=None,
+                                max_trials_per_launch: int = 2 ** 22) -> Dict[str, Any]:
+        """Write - verify - write statistics of G conditions with R = n_trials thermal trials each, reduced on the GPU
+        (stg_switch_verify): how an MRAM macro writes.  A trial is up to A attempts; after every attempt the bit is read -- the
+        trial is classified as in switching_statistics, proj = m . target > threshold -- and only a trial that has not switched runs
+        the next attempt, from the m the attempt before left behind.  A trial ends at attempt a when it is switched after it, when one
+        of its solves failed (counted in n_failed, classified like any other) or when a = A - 1.  No per-trial array exists.
+
+        m_initial [G,3]; current and duration are [A] (the same for all conditions), [A,G], or [A,P,G] (P phases per attempt, run
+        back to back); at most 8 attempts.  relax > 0 (scalar or [G]) appends a J = 0 phase to every attempt; at most 4 phases per
+        attempt in all; a phase of duration exactly 0 is skipped.  Phase p of attempt a runs on Philox counter word
+        env_step + a * P + p.  device_params, device_type, class_index, target, threshold, n_bins, temperature, trial_offset,
+        trial_stride and max_trials_per_launch are those of switching_statistics: trial r of condition g has the stream of problem
+        g * trial_stride + trial_offset + r, disjoint trial ranges add up, and the counts do not depend on the chunking.
+
+        Returns dict(n_switched_at [A,G], n_ended_at [A,G] (trials whose last attempt was a, and those of them that switched),
+        n_failed [G], n_attempted [A,G] = R - sum_{b<a} n_ended_at[b], wer_after [A,G] = 1 - cumsum(n_switched_at) / R with
+        stderr [A,G] = sqrt(wer (1 - wer) / R), p_switch [G] = 1 - wer_after[-1], mean_attempts [G] =
+        sum_a (a + 1) n_ended_at[a] / R, hist [G,n_bins] of the final proj, bin_edges [n_bins + 1] (empty without bins))."""
+        m0 = np.asarray(m_initial.cpu() if torch.is_tensor(m_initial) else m_initial, dtype=np.float64).reshape(-1, 3)
+        g, r = int(m0.shape[0]), int(n_trials)
+        if r < 1:
+            raise ValueError("n_trials must be >= 1")
+        if int(max_trials_per_launch) < 1:
+            raise ValueError("max_trials_per_launch must be >= 1")
+        if not 0 <= int(n_bins) <= 64:
+            raise ValueError("n_bins must be in 0 ... 64")
+        J, T = (np.asarray(x, dtype=np.float64) for x in (current, duration))
+        if not (1 <= J.ndim <= 3 and 1 <= T.ndim <= 3):
+            raise ValueError("current and duration must have shape [A], [A,G] or [A,P,G]")
+        # [A] -> [A,1,1], [A,G] -> [A,1,G]; then both to the common [A,P,G]
+        J, T = (x[:, None, None] if x.ndim == 1 else x[:, None, :] if x.ndim == 2 else x for x in (J, T))
+        if J.shape[0] != T.shape[0] or any(x.shape[2] not in (1, g) for x in (J, T)) or (J.shape[1] != T.shape[1] and 1 not in (J.shape[1], T.shape[1])):
+            raise ValueError(f"current and duration must have shape [A], [A,G] or [A,P,G] with the same A (and P) and G = {g}, "
+                             f"got {np.shape(current)} and {np.shape(duration)}")
+        shape = (J.shape[0], max(J.shape[1], T.shape[1]), g)
+        J, T = np.broadcast_to(J, shape), np.broadcast_to(T, shape)
+        rl = np.broadcast_to(np.asarray(relax, dtype=np.float64), (g,))
+        if (rl < 0).any():
+            raise ValueError("relax must be >= 0")
+        if (rl > 0).any():
+            J = np.concatenate([J, np.zeros((shape[0], 1, g))], axis=1)
+            T = np.concatenate([T, np.broadcast_to(rl, (shape[0], 1, g))], axis=1)
+        J, T = np.array(J, order="C"), np.array(T, order="C")           # (copies: a broadcast view is read-only)
+        n_att = J.shape[0]
+        if not 1 <= n_att <= 8:
+            raise ValueError(f"a trial has 1 ... 8 attempts, got {n_att}")
+        if J.shape[1] > 4:
+            raise ValueError(f"an attempt has at most 4 phases (relax included), got {J.shape[1]}")
+        tgt = np.ascontiguousarray(np.broadcast_to(np.asarray(target, dtype=np.float64), (g, 3)).T)
+        tables = device_params if isinstance(device_params, (list, tuple)) else [device_params]
+        types = device_type if isinstance(device_type, (list, tuple)) else [device_type] * len(tables)
+        if not 1 <= len(tables) <= 64 or len(types) != len(tables):
+            raise ValueError("device_params is one dict or a list of 1 ... 64 dicts (with as many device types, or one)")
+        cls = None
+        if len(tables) > 1:
+            if class_index is None:
+                raise ValueError("class_index [G] is required with more than one device_params dict")
+            cls = np.asarray(class_index).reshape(g)
+            if cls.min() < 0 or cls.max() >= len(tables):
+                raise ValueError("class_index out of range")
+            cls = torch.from_numpy(cls.astype(np.uint8))
+        stride = int(trial_offset) + r if trial_stride is None else int(trial_stride)
+        if int(trial_offset) < 0 or stride < int(trial_offset) + r:
+            raise ValueError("trial_offset must be >= 0 and trial_stride >= trial_offset + n_trials")
+        cfg = EnvConfig(solver=self._solver_name, include_thermal_fluctuations=True, temperature=float(temperature), gamma=self.gamma,
+                        max_step=self.max_step, rtol=self.rtol, atol=self.atol, seed=self._seed, noise_model=self.noise_model,
+                        correlation_time=self.correlation_time)
+        b = self._backend_factory(g, cfg, self.device_index, 0)
+        try:
+            b.set_params([_flat_for(p, t, self._validate_params) for p, t in zip(tables, types)], cls)
+            out, step = None, int(max_trials_per_launch)
+            for done in range(0, r, step):
+                out = b.switch_verify(torch.from_numpy(np.ascontiguousarray(m0.T)), torch.from_numpy(J), torch.from_numpy(T),
+                                      torch.from_numpy(tgt), min(step, r - done), trial0=int(trial_offset) + done, trial_stride=stride,
+                                      cond_cls=cls, env_step=env_step, threshold=float(threshold), n_bins=int(n_bins), out=out)
+            n_sw, n_end, n_failed = (x.cpu().numpy().astype(np.int64) for x in out[:3])
+            hist = out[3].cpu().numpy().astype(np.int64) if n_bins > 0 else np.zeros((g, 0), dtype=np.int64)
+        finally:
+            b.close()
+        self.solve_count += g * r
+        wer = 1.0 - np.cumsum(n_sw, axis=0) / r
+        return {"n_switched_at": n_sw, "n_ended_at": n_end, "n_failed": n_failed,
+                "n_attempted": r - (np.cumsum(n_end, axis=0) - n_end), "wer_after": wer, "stderr": np.sqrt(wer * (1.0 - wer) / r),
+                "p_switch": 1.0 - wer[-1], "mean_attempts": ((np.arange(n_att, dtype=np.int64)[:, None] + 1) * n_end).sum(axis=0) / r,
+                "hist": hist, "bin_edges": np.linspace(-1.0, 1.0, int(n_bins) + 1) if n_bins > 0 else np.zeros(0)}
+
     def draw_devices(self, device_params, n_devices: int, variation, *, n_conditions: int = 1, variation_clip: float = 4.0,
                      variation_step: int = 2 ** 31, trials_per_device: int = 1, trial_stride=None, first_device: int = 0,
                      device_type="stt_mram", class_index=None, temperature: float = 300.0) -> Dict[str, Any]:
