@@ -442,8 +442,8 @@ int stg_switch_stats(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t
  * W = min(ceil(R / 64), max(1, cap / G)), cap = max_waves if max_waves > 0, else STG_SWITCH_STATS_WAVES.  Lane l of wavefront w runs its
  * own list of trials, w * 64 + l + k * 64 * W (k = 0, 1, ...), moving on to the next one as soon as a trial ends, so a wavefront stays
  * full until its lanes run out of trials; the counts never depend on W.  max_waves lets a caller sharing a device bound the launch's width.
- * Enqueues kernels only (no allocation, no synchronisation).  Rectangular phases only: piecewise-linear tables, first-passage times
- * and device populations under verify are follow-ups.  Per-env parameters (stg_set_params_per_env) return STG_E_STATE.
+ * Enqueues kernels only (no allocation, no synchronisation).  Rectangular phases only: piecewise-linear tables and first-passage
+ * times under verify are follow-ups; a population of devices is stg_switch_verify_population.  Per-env parameters (stg_set_params_per_env) return STG_E_STATE.
  * STG_E_INVALID with nothing launched and nothing written: everything stg_switch_stats lists (n_switched_at, n_ended_at in the place
  * of n_switched), A outside 1 ... STG_MAX_VERIFY_ATTEMPTS, max_waves < 0 or 0 < max_waves < G.  env_step + A * P is formed modulo
  * 2^32, as in the siblings: a counter word that wraps is not an error.  R == 0 is valid and does nothing. */
@@ -592,6 +592,37 @@ int stg_switch_population(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, in
 int stg_switch_population_devices(stg_ctx* ctx, int32_t G, int64_t D, int64_t dev0, int64_t trials_per_device, int64_t trial_stride,
                                   uint32_t var_step, double z_clip, const double* sigma, const uint8_t* cond_cls, double* params,
                                   double* z, void* stream);
+
+/* stg_switch_verify over a POPULATION of devices: write - verify - write on a chip whose bits scatter.  On one device the attempts
+ * of a trial are nearly independent and the error after A attempts falls about geometrically; on a chip a weak bit stays weak, the
+ * retries are correlated, and the residual error is set by the tail of the device distribution.  No per-trial and no per-device
+ * memory is held beyond the optional counts below.
+ *
+ * It is stg_switch_verify word for word -- trials, attempts, phases, the stream rule env_step + a * P + p, skipped and failed
+ * phases, the verify arithmetic, the bin rule, the launch rule, max_waves, outputs that are ADDED to -- with ONE difference: every
+ * trial integrates with the row of its own device.  The draw is stg_switch_population's word for word: absolute trial r of condition
+ * g belongs to device d = r / Q, Q = trials_per_device; the device's normals are calls 0 and 1 of the stream of env id
+ * env_id0 + g * trial_stride + d * Q at counter word var_step, tag 0; the five varied fields, the arithmetic, the clip and the derived
+ * row are those stated there, so stg_switch_population_devices dumps exactly these devices.  With every sigma 0 the four outputs of
+ * stg_switch_verify are reproduced integer for integer; with A == 1, n_switched_at[0], n_failed, hist and dev_switched_at[0] are
+ * those of stg_switch_population without tables and without the first passage.
+ *   sigma [dev] double[STG_NVARY][G]; z_clip finite and > 0; var_step; trials_per_device = Q >= 1;
+ *   dev_switched_at [dev] or NULL, unsigned long long[A][G][dev_stride]: element (a * G + g) * dev_stride + d gains one per trial of
+ *   device d (the ABSOLUTE device id) that ended switched at attempt a.  For each (a, g) only the elements
+ *   trial0 / Q ... (trial0 + R - 1) / Q are touched, so chunks and ranks add into one array.
+ * A bad sigma column (stg_switch_population: the rule) is found on the device, once per wavefront: every trial of that condition
+ * fails at its first phase that is not skipped -- with a phase to run in attempt 0 the trial ends at attempt 0 with m = m0, adds one
+ * to n_failed[g] and to n_ended_at[0][g], and is classified and binned like any other.  The other conditions are not affected.
+ * Enqueues kernels only.  Per-env parameters return STG_E_STATE.  STG_E_INVALID with nothing launched and nothing written: everything
+ * stg_switch_verify lists; sigma NULL; z_clip not finite or <= 0; trials_per_device < 1; var_step equal to env_step + k modulo 2^32
+ * for some k < A * P (the device's draw would reuse a thermal stream of its own first trial); dev_switched_at non-NULL with
+ * dev_stride < (trial0 + R + Q - 1) / Q; A * G * dev_stride beyond int64.  R == 0 is valid and does nothing. */
+int stg_switch_verify_population(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t A, int32_t P,
+                                 const double* m0, const double* J, const double* T, const uint8_t* cond_cls, uint32_t env_step,
+                                 const double* target, double threshold, int32_t n_bins, int32_t max_waves,
+                                 unsigned long long* n_switched_at, unsigned long long* n_ended_at, unsigned long long* n_failed,
+                                 unsigned long long* hist, const double* sigma, double z_clip, uint32_t var_step,
+                                 int64_t trials_per_device, unsigned long long* dev_switched_at, int64_t dev_stride, void* stream);
 
 /* SpinTorqueEnv.step for all N envs with the drive of stg_solve_wave: current_func(t) and field_func(t) as piecewise-linear tables
  * in place of the rectangular pulse in zero field of stg_step (spin_torque_env.py:442-447).

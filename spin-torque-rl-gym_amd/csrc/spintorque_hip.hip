@@ -1149,21 +1149,31 @@ int stg_switch_times(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t
     return switch_launch(ctx, x, true, stream);
 }
 
-// write - verify - write: the kernel of stg_switch_verify.hpp on stg_switch_stats' argument block, with the attempts in front of the phases
-int stg_switch_verify(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t A, int32_t P, const double* m0,
-                      const double* J, const double* T, const uint8_t* cond_cls, uint32_t env_step, const double* target, double threshold,
-                      int32_t n_bins, int32_t max_waves, unsigned long long* n_switched_at, unsigned long long* n_ended_at,
-                      unsigned long long* n_failed, unsigned long long* hist, void* stream) {
-    SwitchVerifyArgs x{};
-    if (int rc = switch_stats_args(ctx, "stg_switch_verify", G, R, trial0, trial_stride, P, m0, J, T, cond_cls, env_step, target, threshold, n_bins,
+// write - verify - write: the kernels of stg_switch_verify.hpp on stg_switch_stats' argument block, with the attempts in front of the phases.
+// What stg_switch_verify and stg_switch_verify_population share: the checks, the argument block and the launch rule
+static int switch_verify_args(stg_ctx* ctx, const char* what, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t A, int32_t P,
+                              const double* m0, const double* J, const double* T, const uint8_t* cond_cls, uint32_t env_step,
+                              const double* target, double threshold, int32_t n_bins, int32_t max_waves, unsigned long long* n_switched_at,
+                              unsigned long long* n_ended_at, unsigned long long* n_failed, unsigned long long* hist, SwitchVerifyArgs& x) {
+    if (int rc = switch_stats_args(ctx, what, G, R, trial0, trial_stride, P, m0, J, T, cond_cls, env_step, target, threshold, n_bins,
                                    n_switched_at, n_failed, hist, true, x.s)) return rc;
     if (!n_ended_at) return fail(STG_E_INVALID, "n_ended_at must not be NULL");
     if (A < 1 || A > STG_MAX_VERIFY_ATTEMPTS) return fail(STG_E_INVALID, "A must be in 1 ... STG_MAX_VERIFY_ATTEMPTS");
     if (max_waves < 0 || (max_waves > 0 && max_waves < G)) return fail(STG_E_INVALID, "max_waves must be 0 (the library's rule) or >= G");
     x.A = A; x.n_ended_at = n_ended_at;
-    if (R == 0) return STG_OK;
     x.s.L = 0;                                                                     // (the lockstep kernel's; every lane walks its own list here)
-    x.s.waves_per_cond = switch_verify_plan(G, R, max_waves);
+    if (R > 0) x.s.waves_per_cond = switch_verify_plan(G, R, max_waves);
+    return STG_OK;
+}
+
+int stg_switch_verify(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t A, int32_t P, const double* m0,
+                      const double* J, const double* T, const uint8_t* cond_cls, uint32_t env_step, const double* target, double threshold,
+                      int32_t n_bins, int32_t max_waves, unsigned long long* n_switched_at, unsigned long long* n_ended_at,
+                      unsigned long long* n_failed, unsigned long long* hist, void* stream) {
+    SwitchVerifyArgs x{};
+    if (int rc = switch_verify_args(ctx, "stg_switch_verify", G, R, trial0, trial_stride, A, P, m0, J, T, cond_cls, env_step, target, threshold,
+                                    n_bins, max_waves, n_switched_at, n_ended_at, n_failed, hist, x)) return rc;
+    if (R == 0) return STG_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     if (!stg_switch_verify_launch(x, ctx->cfg.solver, thermal_flag(ctx->cfg), ctx->ncls > 1 && cond_cls != nullptr, (hipStream_t)stream))
         return fail(STG_E_INVALID, "stg_switch_verify has no kernel for this solver");
@@ -1207,6 +1217,36 @@ int stg_switch_population(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, in
     if (R == 0) return STG_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     stg_switch_vary_launch(x, n_crossed != nullptr, ctx->cfg.solver, thermal_flag(ctx->cfg), (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return STG_OK;
+}
+
+// stg_switch_verify over a population: the checks of both parents, then the sibling kernel of stg_switch_verify.hpp
+int stg_switch_verify_population(stg_ctx* ctx, int32_t G, int64_t R, int64_t trial0, int64_t trial_stride, int32_t A, int32_t P, const double* m0,
+                                 const double* J, const double* T, const uint8_t* cond_cls, uint32_t env_step, const double* target,
+                                 double threshold, int32_t n_bins, int32_t max_waves, unsigned long long* n_switched_at,
+                                 unsigned long long* n_ended_at, unsigned long long* n_failed, unsigned long long* hist, const double* sigma,
+                                 double z_clip, uint32_t var_step, int64_t trials_per_device, unsigned long long* dev_switched_at,
+                                 int64_t dev_stride, void* stream) {
+    SwitchVerifyPopArgs x{};
+    if (int rc = switch_verify_args(ctx, "stg_switch_verify_population", G, R, trial0, trial_stride, A, P, m0, J, T, cond_cls, env_step, target,
+                                    threshold, n_bins, max_waves, n_switched_at, n_ended_at, n_failed, hist, x.y)) return rc;
+    if (int rc = switch_vary_scalars(sigma, z_clip, trials_per_device)) return rc;
+    if (var_step - env_step < (uint32_t)(A * P))                                   // (modulo 2^32, as the counter words are formed)
+        return fail(STG_E_INVALID, "var_step must differ from env_step + a * P + p for every phase of every attempt (the device's draw would reuse a thermal stream)");
+    const int64_t Q = trials_per_device;
+    if (dev_switched_at) {
+        // devices 0 ... (trial0 + R - 1) / Q of a condition must fit a row: ceil((trial0 + R) / Q), formed without overflow
+        const int64_t end = trial0 + R, need = end / Q + (end % Q != 0 ? 1 : 0);
+        if (dev_stride < need) return fail(STG_E_INVALID, "dev_stride must be >= (trial0 + R + Q - 1) / Q");
+        if (dev_stride > INT64_MAX / ((int64_t)A * G)) return fail(STG_E_INVALID, "A * G * dev_stride exceeds int64");
+    }
+    x.v.sigma = sigma; x.v.ptab = ctx->ptab; x.v.z_clip = z_clip; x.v.gamma = ctx->cfg.gamma; x.v.Q = Q; x.v.var_step = var_step;
+    x.v.dev_switched = dev_switched_at; x.v.dev_stride = dev_stride;
+    if (R == 0) return STG_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!stg_switch_verify_population_launch(x, ctx->cfg.solver, thermal_flag(ctx->cfg), (hipStream_t)stream))
+        return fail(STG_E_INVALID, "stg_switch_verify_population has no kernel for this solver");
     HIP_TRY(hipGetLastError());
     return STG_OK;
 }

@@ -97,6 +97,9 @@ SYMBOLS = {
     "stg_switch_population": (C.c_int, [_VP, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP,
                                         C.c_int32, _VP, _VP, _VP, C.c_uint32, _VP, C.c_double, C.c_int32, _VP, _VP, _VP, C.c_int32, _VP, _VP, _VP,
                                         _VP, C.c_double, C.c_uint32, C.c_int64, _VP, C.c_int64, _VP]),
+    "stg_switch_verify_population": (C.c_int, [_VP, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_uint32,
+                                               _VP, C.c_double, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, C.c_double, C.c_uint32, C.c_int64,
+                                               _VP, C.c_int64, _VP]),
     "stg_switch_population_devices": (C.c_int, [_VP, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, C.c_double, _VP, _VP, _VP,
                                                 _VP, _VP]),
     "stg_step_wave": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,

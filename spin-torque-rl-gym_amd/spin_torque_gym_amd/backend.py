@@ -610,6 +610,44 @@ class HipBackend:
                                               _ptr(n_failed), _ptr(hist), self._stream()))
         return out
 
+    def switch_verify_population(self, m0, J, T, target, n_trials, sigma, z_clip=4.0, var_step=2 ** 31, trials_per_device=1,
+                                 dev_switched_at=None, trial0=0, trial_stride=None, cond_cls=None, env_step=0, threshold=0.0, n_bins=0,
+                                 max_waves=0, out=None):
+        """switch_verify over a population of devices (stg_switch_verify_population): trial r (absolute) of condition g belongs to
+        device r // trials_per_device, drawn as switch_population draws it (sigma float64 [5, G], z_clip, var_step -- which must differ
+        from env_step + k of all A * P phases), and every attempt of the trial integrates with that device's own constants.
+        dev_switched_at int64 [A, G, dev_stride] on the device, indexed by the absolute device id, gains one per trial of the device
+        that ended switched at attempt a, when given.  Everything else, the returned tuple and `out` included, as switch_verify.
+        Enqueues only."""
+        m0 = self._dev(m0, torch.float64)
+        g = int(m0.shape[-1])
+        m0 = self._dev(m0, torch.float64, (3, g))
+        J, T = (x[:, None, :] if x.dim() == 2 else x for x in (self._dev(J, torch.float64), self._dev(T, torch.float64)))
+        a, p = int(T.shape[0]), int(T.shape[1])
+        J, T = self._dev(J, torch.float64, (a, p, g)), self._dev(T, torch.float64, (a, p, g))
+        target = self._dev(target, torch.float64, (3, g))
+        cond_cls = self._dev(cond_cls, torch.uint8, (g,))
+        sigma = self._dev(sigma, torch.float64, (_lib.STG_NVARY, g))
+        r, t0 = int(n_trials), int(trial0)
+        stride = t0 + r if trial_stride is None else int(trial_stride)
+        if out is None:
+            zeros = lambda *shape: torch.zeros(shape, dtype=torch.int64, device=self.device)      # noqa: E731
+            out = (zeros(a, g), zeros(a, g), zeros(g), zeros(g, int(n_bins)) if n_bins > 0 else None)
+        n_sw, n_end, n_failed, hist = out
+        dev_stride = 0
+        if dev_switched_at is not None:
+            if (not torch.is_tensor(dev_switched_at) or dev_switched_at.dtype != torch.int64 or dev_switched_at.dim() != 3
+                    or tuple(dev_switched_at.shape[:2]) != (a, g) or not dev_switched_at.is_contiguous() or not dev_switched_at.is_cuda):
+                raise ValueError(f"dev_switched_at must be a contiguous int64 tensor [A = {a}, G = {g}, dev_stride] on {self.device}")
+            dev_stride = int(dev_switched_at.shape[2])
+        self._keep = (m0, J, T, target, cond_cls, sigma)
+        _lib.check(self.lib.stg_switch_verify_population(self._ctx, g, r, t0, stride, a, p, _ptr(m0), _ptr(J), _ptr(T), _ptr(cond_cls),
+                                                         int(env_step), _ptr(target), float(threshold), int(n_bins), int(max_waves),
+                                                         _ptr(n_sw), _ptr(n_end), _ptr(n_failed), _ptr(hist), _ptr(sigma), float(z_clip),
+                                                         int(var_step), int(trials_per_device), _ptr(dev_switched_at), dev_stride,
+                                                         self._stream()))
+        return out
+
     def switch_stats_wave(self, m0, J, T, target, n_trials, wave, wave_phase=0, trial0=0, trial_stride=None, cond_cls=None, env_step=0,
                           threshold=0.0, n_bins=0, out=None):
         """switch_stats with phase `wave_phase` driven by piecewise-linear tables (stg_switch_stats_wave): wave = dict(current=(tj [K,G],

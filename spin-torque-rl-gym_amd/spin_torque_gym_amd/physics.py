@@ -432,7 +432,8 @@ class _GpuSolverBase:
     def write_verify_statistics(self, m_initial, current, duration, device_params, n_trials: int, *, relax=0.0,
                                 target=(0.0, 0.0, -1.0), threshold: float = 0.0, n_bins: int = 0, temperature: float = 300.0,
                                 device_type="stt_mram", class_index=None, env_step: int = 0, trial_offset: int = 0, trial_stride=None,
-                                max_trials_per_launch: int = 2 ** 22) -> Dict[str, Any]:
+                                max_trials_per_launch: int = 2 ** 22, variation=None, variation_clip: float = 4.0,
+                                variation_step: int = 2 ** 31, trials_per_device: int = 1, per_device: bool = False) -> Dict[str, Any]:
         """Write - verify - write statistics of G conditions with R = n_trials thermal trials each, reduced on the GPU
         (stg_switch_verify): how an MRAM macro writes.  A trial is up to A attempts; after every attempt the bit is read -- the
         trial is classified as in switching_statistics, proj = m . target > threshold -- and only a trial that has not switched runs
@@ -449,7 +450,17 @@ class _GpuSolverBase:
         Returns dict(n_switched_at [A,G], n_ended_at [A,G] (trials whose last attempt was a, and those of them that switched),
         n_failed [G], n_attempted [A,G] = R - sum_{b<a} n_ended_at[b], wer_after [A,G] = 1 - cumsum(n_switched_at) / R with
         stderr [A,G] = sqrt(wer (1 - wer) / R), p_switch [G] = 1 - wer_after[-1], mean_attempts [G] =
-        sum_a (a + 1) n_ended_at[a] / R, hist [G,n_bins] of the final proj, bin_edges [n_bins + 1] (empty without bins))."""
+        sum_a (a + 1) n_ended_at[a] / R, hist [G,n_bins] of the final proj, bin_edges [n_bins + 1] (empty without bins)).
+
+        variation, variation_clip, variation_step, trials_per_device and per_device are those of switching_statistics: with
+        variation = {...} the R trials of a condition are trials of a POPULATION of devices around device_params
+        (stg_switch_verify_population) -- trial r (trial_offset included) belongs to device r // trials_per_device, drawn exactly as
+        there, so `draw_devices` returns these devices -- and every attempt of a trial runs on its own device: a weak bit stays weak
+        over its retries, and the residual wer_after is set by the tail of the device distribution.  variation_step must differ from
+        env_step + k of all A * P counter words of a trial.  The returned dict is the one above; per_device = True adds, for devices
+        trial_offset // trials_per_device onwards, dev_switched_at [A,G,n_dev] (trials of the device that ended switched at attempt
+        a), dev_trials [G,n_dev] (the first and the last device may be partial) and dev_wer_after [A,G,n_dev] =
+        1 - cumsum(dev_switched_at) / dev_trials.  variation = None is exactly the call above."""
         m0 = np.asarray(m_initial.cpu() if torch.is_tensor(m_initial) else m_initial, dtype=np.float64).reshape(-1, 3)
         g, r = int(m0.shape[0]), int(n_trials)
         if r < 1:
@@ -496,27 +507,54 @@ class _GpuSolverBase:
         stride = int(trial_offset) + r if trial_stride is None else int(trial_stride)
         if int(trial_offset) < 0 or stride < int(trial_offset) + r:
             raise ValueError("trial_offset must be >= 0 and trial_stride >= trial_offset + n_trials")
+        sigma, q, dev_first, n_dev = None, int(trials_per_device), 0, 0
+        if variation is not None:
+            sigma = _variation_sigma(variation, g, variation_clip)
+            if q < 1:
+                raise ValueError("trials_per_device must be >= 1")
+            if not 0 <= int(variation_step) < 2 ** 32 or (int(variation_step) - int(env_step)) % 2 ** 32 < n_att * J.shape[1]:
+                raise ValueError("variation_step must be a 32-bit counter word other than env_step + a * P + p of the trial's phases")
+            dev_first = int(trial_offset) // q
+            n_dev = (int(trial_offset) + r - 1) // q - dev_first + 1
         cfg = EnvConfig(solver=self._solver_name, include_thermal_fluctuations=True, temperature=float(temperature), gamma=self.gamma,
                         max_step=self.max_step, rtol=self.rtol, atol=self.atol, seed=self._seed, noise_model=self.noise_model,
                         correlation_time=self.correlation_time)
         b = self._backend_factory(g, cfg, self.device_index, 0)
+        dev_sw = None
         try:
             b.set_params([_flat_for(p, t, self._validate_params) for p, t in zip(tables, types)], cls)
             out, step = None, int(max_trials_per_launch)
+            launch = b.switch_verify
+            if sigma is not None:
+                # the chunks below keep absolute trial indices, so every launch sees the same devices and adds into the same counts
+                if per_device:
+                    dev_sw = torch.zeros((n_att, g, dev_first + n_dev), dtype=torch.int64, device=b.device)
+                launch = functools.partial(b.switch_verify_population, sigma=torch.from_numpy(sigma), z_clip=float(variation_clip),
+                                           var_step=int(variation_step), trials_per_device=q, dev_switched_at=dev_sw)
             for done in range(0, r, step):
-                out = b.switch_verify(torch.from_numpy(np.ascontiguousarray(m0.T)), torch.from_numpy(J), torch.from_numpy(T),
-                                      torch.from_numpy(tgt), min(step, r - done), trial0=int(trial_offset) + done, trial_stride=stride,
-                                      cond_cls=cls, env_step=env_step, threshold=float(threshold), n_bins=int(n_bins), out=out)
+                out = launch(torch.from_numpy(np.ascontiguousarray(m0.T)), torch.from_numpy(J), torch.from_numpy(T),
+                             torch.from_numpy(tgt), min(step, r - done), trial0=int(trial_offset) + done, trial_stride=stride,
+                             cond_cls=cls, env_step=env_step, threshold=float(threshold), n_bins=int(n_bins), out=out)
             n_sw, n_end, n_failed = (x.cpu().numpy().astype(np.int64) for x in out[:3])
             hist = out[3].cpu().numpy().astype(np.int64) if n_bins > 0 else np.zeros((g, 0), dtype=np.int64)
+            if dev_sw is not None:
+                dev_sw = dev_sw[:, :, dev_first:].cpu().numpy().astype(np.int64)
         finally:
             b.close()
         self.solve_count += g * r
         wer = 1.0 - np.cumsum(n_sw, axis=0) / r
-        return {"n_switched_at": n_sw, "n_ended_at": n_end, "n_failed": n_failed,
-                "n_attempted": r - (np.cumsum(n_end, axis=0) - n_end), "wer_after": wer, "stderr": np.sqrt(wer * (1.0 - wer) / r),
-                "p_switch": 1.0 - wer[-1], "mean_attempts": ((np.arange(n_att, dtype=np.int64)[:, None] + 1) * n_end).sum(axis=0) / r,
-                "hist": hist, "bin_edges": np.linspace(-1.0, 1.0, int(n_bins) + 1) if n_bins > 0 else np.zeros(0)}
+        res = {"n_switched_at": n_sw, "n_ended_at": n_end, "n_failed": n_failed,
+               "n_attempted": r - (np.cumsum(n_end, axis=0) - n_end), "wer_after": wer, "stderr": np.sqrt(wer * (1.0 - wer) / r),
+               "p_switch": 1.0 - wer[-1], "mean_attempts": ((np.arange(n_att, dtype=np.int64)[:, None] + 1) * n_end).sum(axis=0) / r,
+               "hist": hist, "bin_edges": np.linspace(-1.0, 1.0, int(n_bins) + 1) if n_bins > 0 else np.zeros(0)}
+        if dev_sw is not None:
+            # trials of each touched device inside [trial_offset, trial_offset + R): the first and the last may be partial
+            lo = np.maximum((dev_first + np.arange(n_dev, dtype=np.int64)) * q, int(trial_offset))
+            hi = np.minimum((dev_first + np.arange(n_dev, dtype=np.int64) + 1) * q, int(trial_offset) + r)
+            dev_trials = np.broadcast_to(hi - lo, (g, n_dev)).copy()
+            res.update({"dev_switched_at": dev_sw, "dev_trials": dev_trials,
+                        "dev_wer_after": 1.0 - np.cumsum(dev_sw, axis=0) / dev_trials[None]})
+        return res
 
     def draw_devices(self, device_params, n_devices: int, variation, *, n_conditions: int = 1, variation_clip: float = 4.0,
                      variation_step: int = 2 ** 31, trials_per_device: int = 1, trial_stride=None, first_device: int = 0,
